@@ -35,11 +35,15 @@ A "step" is one engine iteration (one continuous-batching forward over the mixed
 included). W untimed warmup steps, then exactly K timed steps between barrier + synchronize; value = total output
 tokens of all ranks / max rank time.
 
+A plain run sets up, warms up, times the K steps and prints the result line. ``--dump-outputs DIR`` also writes what
+the last timed step computed as ``DIR/*.npy`` (``dump_outputs``); the inputs depend on the arguments only.
+
 TTFT (first token of a new turn, engine-level: request arrival -> sampled token on the host; the first content
-frame of /root/reference/server.py:338-356) is sampled from every new turn that ARRIVES at or after the start of
-the timed window; completions are ~threads/mean(reply) per step (~0.25 at 64 threads), so after the K timed steps
-the engine keeps stepping under the same load (untimed, not counted in ``value``) until ``--ttft-samples`` turns
-have their first token (``ttft_extra_steps`` reports how many steps that took).
+frame of the reference server's stream) is sampled from every new turn that ARRIVES at or after the start of
+the timed window; completions are ~threads/mean(reply) per step (~0.25 at 64 threads), so a plain run reports the
+few samples of its window. With ``--full`` the engine keeps stepping after the K timed steps under the same load
+(untimed, not counted in ``value``) until ``--ttft-samples`` turns have their first token (``ttft_extra_steps``
+reports how many steps that took).
 
 vs_baseline: the reference publishes no number for this metric; the ratio is to the derived
 MI355X bound for exactly this workload (~17k tok/s on one GPU with cascade attention, BASELINE.md §3 /
@@ -94,6 +98,10 @@ def parse(argv=None):
                     help="paged KV cache precision (fp8 = e4m3 + per-token scales; an opt-in A/B, not the headline)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure TTFT to --ttft-samples new turns: keeps stepping (untimed) after the timed steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (sampled ids, the logits behind them) as DIR/*.npy")
     return ap.parse_args(argv)
 
 
@@ -252,6 +260,39 @@ def stratified_budgets(threads, args, rng: random.Random) -> list[tuple[int, int
     return out
 
 
+DUMP_LOGITS_BYTES = 48 << 20  # --dump-outputs: the float32 logits kept (whole rows, or a fixed column sample)
+
+
+def dump_outputs(path: str, last: dict) -> None:
+    """``--dump-outputs DIR``: what rank 0's timed path computed last, as ``DIR/<name>.npy``:
+
+      * ``step_tokens`` (n, 2) float64 — what the last timed ``step()`` returned to its caller: (thread slot, token id)
+        per streamed token, ordered by slot;
+      * ``logits`` (rows, V) float32 and ``sampled_ids`` (rows,) float64 — the last step launched inside the timed
+        window: the logits its sampler drew from and the ids it drew, rows in the step's sampling order. Past
+        DUMP_LOGITS_BYTES the logits keep a seeded column sample, listed in ``logits_columns`` (float64).
+
+    Seeds, prompts and reply lengths depend on the arguments only, so two runs with the same arguments feed the
+    timed path the same inputs and two builds can be compared array for array."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"step_tokens": np.asarray(sorted(last.get("step", [])), dtype=np.float64).reshape(-1, 2)}
+    if "sampled" in last:
+        logits, toks = last["sampled"]
+        logits = logits.detach().float().cpu().numpy()
+        rows, vocab = logits.shape
+        keep = DUMP_LOGITS_BYTES // (4 * max(1, rows))
+        if keep < vocab:
+            cols = np.sort(np.random.default_rng(0).choice(vocab, size=keep, replace=False))
+            logits = np.ascontiguousarray(logits[:, cols])
+            arrays["logits_columns"] = cols.astype(np.float64)
+        arrays["logits"] = logits
+        arrays["sampled_ids"] = toks.detach().cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main(argv=None):
     args = parse(argv)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -369,6 +410,16 @@ def main(argv=None):
     window = [float("inf")]
 
     steplog = [] if os.environ.get("KAFKA_BENCH_STEPLOG") else None  # per-step trace for the stationarity check
+    last = {}  # --dump-outputs: the newest sampler call's (logits, ids) and the newest timed step's returned tokens
+    if args.dump_outputs:
+        sampler = eng.runner.sample_device
+
+        def sample_device(logits, sp):  # keeps references only: no copy, no synchronisation inside the timed steps
+            toks = sampler(logits, sp)
+            last["sampled"] = (logits, toks)
+            return toks
+
+        eng.runner.sample_device = sample_device
 
     def run_step(record: bool):
         ts = time.perf_counter()
@@ -377,6 +428,8 @@ def main(argv=None):
             st = getattr(eng.runner, "last_stats", None) or {}  # the step launched by this call (outs lag one step)
             steplog.append((ts, len(outs), sum(1 for o in outs if o.num_output_tokens == 1), st.get("T"),
                             st.get("s_total")))
+        if record and args.dump_outputs:
+            last["step"] = [(req_thread[o.request_id][0].tid, t) for o in outs for t in o.new_token_ids]
         for o in outs:
             th, seq, resumed = req_thread[o.request_id]
             if record:
@@ -428,10 +481,12 @@ def main(argv=None):
             ps = pstats.Stats(prof, stream=f)
             ps.sort_stats("tottime").print_stats(50)
             ps.sort_stats("cumtime").print_stats(60)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     _barrier(leaders)
-    # ---- TTFT: keep the same load running (untimed) until enough new turns have produced their first token
+    # ---- TTFT (--full): keep the same load running (untimed) until enough new turns have produced their first token
     def want_more() -> bool:
-        more = len(timing["ttft"]) < args.ttft_samples and timing["extra"] < args.ttft_max_steps
+        more = args.full and len(timing["ttft"]) < args.ttft_samples and timing["extra"] < args.ttft_max_steps
         if dpa:  # the group keeps stepping while any rank still needs samples
             more = bool(agree((int(more),))[0])
         return more

@@ -95,7 +95,7 @@ def test_bench_spawns_ranks_without_launcher():
     single JSON line, and the window contains new turns (staggered steady state) so TTFT is always sampled."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--model", "tiny-llama", "--prefix-tokens", "200", "--threads", "4", "--min-out", "4", "--max-out", "8",
-           "--user-tokens", "8", "--ttft-samples", "4"]
+           "--user-tokens", "8", "--ttft-samples", "4", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["OMP_NUM_THREADS"] = "2"
     p = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=500)
@@ -105,6 +105,53 @@ def test_bench_spawns_ranks_without_launcher():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
     assert d["ttft_samples"] >= 4 and d["ttft_p50_ms"] is not None
+
+
+def _run_single(extra, cwd):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+           "--model", "tiny-llama", "--prefix-tokens", "200", "--threads", "4", "--min-out", "4", "--max-out", "8",
+           "--user-tokens", "8", "--ttft-samples", "4", *extra]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")  # the CPU path, on any machine
+    p = subprocess.run(cmd, cwd=cwd, env=env, capture_output=True, text=True, timeout=500)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_only_its_steps(tmp_path):
+    """Without ``--full`` the run ends after its timed steps: no TTFT tail, and the engine ran the prefix warm-up,
+    the setup prefill and warmup + steps (+ the one step in flight) iterations, nothing more."""
+    d = _run_single([], str(tmp_path))
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ttft_extra_steps"] == 0
+    assert d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "tok/s" and d["higher_is_better"] is True
+    assert abs(d["per_rank"][0]["out_tokens"] / (d["ms_per_step"] * 4 / 1e3) - d["value"]) <= 0.02 * d["value"] + 1
+    full = _run_single(["--full"], str(tmp_path))
+    assert full["ttft_samples"] >= 4 and full["ttft_extra_steps"] > 0
+    assert d["per_rank"][0]["steps"] + full["ttft_extra_steps"] == full["per_rank"][0]["steps"]
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's arrays as float32 / float64 ``.npy`` files, and two runs
+    with the same arguments write the same arrays (the inputs depend on the arguments only)."""
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        _run_single(["--dump-outputs", str(tmp_path / name)], str(tmp_path))
+        files = sorted(os.listdir(tmp_path / name))
+        assert {"step_tokens.npy", "logits.npy", "sampled_ids.npy"} <= set(files)
+        runs.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = runs
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["logits.npy"].dtype == np.float32 and a["logits.npy"].ndim == 2 and a["logits.npy"].shape[0] >= 1
+    assert a["sampled_ids.npy"].shape == (a["logits.npy"].shape[0],)
+    assert a["step_tokens.npy"].shape[1] == 2 and len(a["step_tokens.npy"]) >= 1
+    assert np.isfinite(a["logits.npy"]).all()
+    for f, v in a.items():
+        assert v.dtype in (np.float32, np.float64)
+        assert v.shape == b[f].shape and np.array_equal(v, b[f]), f
 
 
 def test_bench_rejects_rank_mismatch():
