@@ -231,8 +231,6 @@ def plan_prefill_items(tiles: list[tuple], hkv: int, target_wgs: int, min_chunk:
 def retile(spans: list[tuple[int, int]], tile: int) -> list[tuple[int, int]]:
     """(q0, count) token spans (ascending) -> the same tokens as (q0, count) tiles of at most ``tile`` tokens, contiguous
     spans joined first: 8 new turns of 30 tokens back to back make 4 full tiles, not 8 half-empty ones."""
-    if tile <= 0:  # (off: the spans as they are)
-        return [tuple(t) for t in spans]
     runs: list[list[int]] = []
     for q0, cnt in spans:
         if runs and runs[-1][0] + runs[-1][1] == q0:
@@ -510,12 +508,10 @@ class ModelRunner:
         # rows whose token was still being sampled at launch gather their input ids from it on the stream
         self.tok_buf = torch.zeros(max_num_seqs * 2 + 64, dtype=torch.int64, device=self.device)
         self.graphs = None  # engine/graphs.py DecodeGraphs when hipGraph decode is enabled
-        # decode_items_fixed without graphs too (equivalence tests; KAFKA_FIXED_DECODE_ITEMS=1 separates the graph
-        # plan's cost from the replay's in an eager A/B)
-        self.fixed_decode_items = os.environ.get("KAFKA_FIXED_DECODE_ITEMS", "0") == "1"
+        # decode_items_fixed without graphs too (set by the graph / eager equivalence tests)
+        self.fixed_decode_items = False
         # a joined new turn's own keys (its history behind the shared prefix) ride in the cascade launch too
         self.join_suffix = os.environ.get("KAFKA_JOIN_SUFFIX", "1") == "1"
-        self.retile_joins = os.environ.get("KAFKA_RETILE_JOINS", "1") == "1"  # (model_runner.retile)
         self.step_events: list | None = None  # (start, end) timing events per launched step when a list is set
         # grammar masks / forced tokens / penalties inside the sampler kernel (tables allocated on first use)
         self.lp = LogitsProcessor(self.device, self.vocab, max_slots=max(256, max_num_seqs))
@@ -617,8 +613,7 @@ class ModelRunner:
                 # the joined rows' prefix-pass tiles: the group's joined tokens re-tiled at token granularity (a burst
                 # of short new turns fills 64-token tiles instead of one mostly empty tile per turn; every key of the
                 # prefix is below every joined token's position, so tokens of different turns share a tile)
-                jt = {gi: retile([tiles[ti][:2] for ti in js], self.tile if self.retile_joins else 0)
-                      for gi, js in joins.items()}
+                jt = {gi: retile([tiles[ti][:2] for ti in js], self.tile) for gi, js in joins.items()}
                 # key chunks sized so the prefix pass launches ~target_wgs workgroups over all groups together
                 work = sum(-(-n // self.tile) * p * PAGE for n, p in groups) + \
                     sum(len(t) * groups[gi][1] * PAGE for gi, t in jt.items()) + sum(spans.values())

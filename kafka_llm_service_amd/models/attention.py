@@ -20,15 +20,11 @@ the decode path is hipGraph-capturable (fixed shapes per batch bucket).
 from __future__ import annotations
 
 import math
-import os
 from dataclasses import dataclass, field
 
 import torch
 
 from kafka_llm_service_amd import ops
-
-# KAFKA_FUSED_PREFILL_MERGE=0: prefill rows' partials merged by their own attn_merge launch, never by the decode launch
-FUSE_PREFILL_MERGE = os.environ.get("KAFKA_FUSED_PREFILL_MERGE", "1") == "1"
 
 
 @dataclass
@@ -87,7 +83,7 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
         # the decode kernel merges each row's prefix partials and its own pieces and writes the final rows; when
         # every prefill tile rode in the cascade launch, its extra workgroups also merge the prefill rows' partials
         merge = None
-        if meta.prefill_items is None and len(meta.prefill_merge) == 1 and FUSE_PREFILL_MERGE:
+        if meta.prefill_items is None and len(meta.prefill_merge) == 1:
             lo, hi = meta.prefill_merge[0]
             merge = (meta.prefill_part[lo:hi], meta.prefill_lse[lo:hi], out[B + lo:B + hi])
         ops.attn_decode_items(qd, k_cache, v_cache, meta.block_tables, meta.decode_items, meta.part, meta.lse,

@@ -236,8 +236,6 @@ extern "C" hipError_t kafka_car_alloc(int64_t bytes, void** out) {
   return hipMemset(*out, 0, AR_HEADER);
 }
 
-extern "C" int64_t kafka_car_header_bytes() { return AR_HEADER; }
-
 // Host copy of the timing ring ([AR_TIME_SLOTS][2] uint64 = 2 KB) and of block 0's epoch (the call count), on a
 // private stream so a /metrics request never waits behind the engine's queued steps.
 extern "C" hipError_t kafka_car_timing(const void* own, uint64_t* ring_out, int* epoch_out) {

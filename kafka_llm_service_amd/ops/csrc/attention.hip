@@ -35,22 +35,12 @@
 // quantization error for no gain in a kernel that is bound by bytes (decode) or by staging (tile).
 #include "common.h"
 
-#include <cstdlib>
+#include <cstddef>
 #include <type_traits>
 
 namespace kafka {
 
-constexpr int PAGE = 16;
-
-struct AttnWorkItem {
-  int q_start;  // first query token (row of q / out)
-  int q_count;  // tokens in this tile
-  int bt_row;   // block-table row used for the keys
-  int kv_lo;    // first key position (inclusive)
-  int kv_hi;    // last key position (exclusive)
-  int split;    // -1: write normalized bf16 to out; >= 0: write partial #split
-  int pad0, pad1;
-};
+// (PAGE, the fp8 page constants and the work-item records AttnWorkItem / DecodeItem: kafka_abi.h)
 
 // Reductions with the partner lane l ^ 32 on gfx950's v_permlane32_swap (one VALU op, no LDS crossbar round trip
 // through ds_bpermute — which also queued behind the K/V fragment reads): swapping a register with itself leaves
@@ -69,9 +59,6 @@ __device__ __forceinline__ float xor32_sum(float x) {
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-constexpr int KPAGE8 = PAGE * 128 + 32;  // fp8 K page bytes per (block, kv head): data + K/V exponents
-constexpr int VPAGE8 = PAGE * 128;
-constexpr int KEXP8 = PAGE * 128, VEXP8 = PAGE * 128 + 16;
 
 __device__ __forceinline__ float exp2i(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
 
@@ -329,9 +316,7 @@ __device__ __forceinline__ void init_acc(WaveAcc<D>& acc) {
 // long one (the host sizes pieces so every workgroup streams about the same bytes: one 3k-token history no longer
 // holds the whole launch while the short ones have finished). Row b's partials live at slots [0, npre) (cascade
 // prefix partials written by the tile kernel, for the row's prefix group) and npre + split (this piece).
-struct DecodeItem {
-  int b, lo, hi, split, nsplit, npre, pad0, pad1;
-};
+// (DecodeItem: kafka_abi.h)
 
 // LDS of one decode piece (4 waves' partial results + the fused merge's per-split weights)
 constexpr int DEC_MAXPG = 2048;  // page ids of one decode piece staged in LDS (longer pieces read the table)
@@ -339,14 +324,17 @@ template <int D>
 struct DecodeSmem {
   int pages[DEC_MAXPG];
   bf16 qs[8][D];  // bf16: the unit's G <= 8 query heads (B operand rows), read per block instead of held in VGPRs
+  bf16 so[8][D];  // OST: the final bf16 rows, stored from here as 16-B sc1 stores
   float sO[4][8][D];
   float sM[4][8];
   float sL[4][8];
   float sW[8][65];
   float sWt[8];
   int s_last;
-  bf16 so[8][D];  // OST: the final bf16 rows, stored from here as 16-B sc1 stores
 };
+// qs and so are accessed with 16-B LDS loads / stores
+static_assert(offsetof(DecodeSmem<128>, so) % 16 == 0 && offsetof(DecodeSmem<128>, qs) % 16 == 0,
+              "DecodeSmem: qs / so must be 16-B aligned");
 
 // the workgroup's G final rows from sm.so to out (every thread of the workgroup calls it)
 template <int D>
@@ -1263,12 +1251,8 @@ extern "C" hipError_t kafka_launch_attn_decode(const bf16* q, int64_t q_stride, 
   if (n_items + n_mwg > 65535) return hipErrorInvalidValue;
   const FusedMerge fm{m_part, m_lse, m_S, m_rows, m_out, m_out_stride};
   const dim3 grid(Hkv, n_items + n_mwg);
-  // KAFKA_SC1_ATTN (default 1): the bf16 rows as 16-B sc1 stores through LDS (decode_piece OST)
-  static const bool sc1 = [] {
-    const char* e = getenv("KAFKA_SC1_ATTN");
-    return e == nullptr || e[0] != '0';
-  }();
-  const bool ost = sc1 && out != nullptr && out_stride % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+  // the bf16 rows as 16-B sc1 stores through LDS (decode_piece OST) when they are 16-B aligned
+  const bool ost = out != nullptr && out_stride % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
   if (ost && !fp8)
     attn_decode_kernel<128, false, true><<<grid, 256, 0, st>>>(q, q_stride, k_cache, v_cache, Hkv, G, block_tables,
                                                                 bt_stride, di, B, out_part, lse_part, S_total,
@@ -1303,13 +1287,6 @@ static void launch_prefill(const AttnWorkItem* it, int n_items, const bf16* q, i
         it, q, q_stride, k_cache, v_cache, Hkv, G, block_tables, bt_stride, q_limit, out, out_stride, out_part,
         lse_part, S_total, scale_log2);
 }
-
-extern "C" hipError_t kafka_launch_attn_tile(const void* items, int n_items, const bf16* q, int64_t q_stride,
-                                            const void* k_cache, const void* v_cache, int Hkv, int G, int D,
-                                            const int* block_tables, int bt_stride, const int* q_limit, bf16* out,
-                                            int64_t out_stride, float* out_part, float* lse_part, int S_total,
-                                            float scale, int part_bf16, float* alt_part, float* alt_lse, int alt_S,
-                                            int alt_tok_off, hipStream_t st);
 
 extern "C" hipError_t kafka_launch_attn_prefill(const void* items, int n_items, const bf16* q, int64_t q_stride,
                                                const void* k_cache, const void* v_cache, int fp8, int Hkv, int G,

@@ -28,7 +28,6 @@
 namespace kafka {
 
 namespace tile3 {
-constexpr int PAGE = 16;
 constexpr int D = 128;
 constexpr int TK = 64;                  // keys per tile (4 pages)
 constexpr int KBYTES = TK * D * 2;      // K part of a ring slot
@@ -39,9 +38,7 @@ constexpr int lds_bytes() { return NSLOT * SLOT + MAXPG * 4 + 64; }
 constexpr float THR = 24.f;             // deferred-rescale threshold (log2 domain): P <= 2^THR, fp32-safe
 }  // namespace tile3
 
-struct TileItem {
-  int q_start, q_count, bt_row, kv_lo, kv_hi, split, alt, pad1;
-};
+// (PAGE and the work-item record AttnWorkItem: kafka_abi.h)
 
 // Second partial buffer of a launch (fp32 [rows, Hq, S, D] + lse [rows, Hq, S]) for the items flagged `alt`: the
 // cascade's prefix pass also serves the new-turn prefill rows of the step, whose prefix partials join their own
@@ -107,7 +104,7 @@ __device__ __forceinline__ void t3_wait_tiles(int n) {
 // PST = 1: the bf16 prefix partials are stored sc1 (16-B stores whose lines leave this XCD's L2: the reader, the
 // suffix decode's merge, runs on any XCD, and the launch ends with fewer dirty lines to write back)
 template <int ABL = 0, int KVAUX = 0, int PST = 0>
-__global__ __launch_bounds__(512, 2) void attn_tile_kernel(const TileItem* __restrict__ items,
+__global__ __launch_bounds__(512, 2) void attn_tile_kernel(const AttnWorkItem* __restrict__ items,
                                                            const bf16* __restrict__ q, int64_t q_stride,
                                                            const bf16* __restrict__ k_cache,
                                                            const bf16* __restrict__ v_cache, int Hkv, int G,
@@ -128,7 +125,7 @@ __global__ __launch_bounds__(512, 2) void attn_tile_kernel(const TileItem* __res
 
   uint64_t ph[5] = {0, 0, 0, 0, 0};
   if constexpr (ABL == 8) ph[0] = t3_rt();
-  const TileItem it = items[blockIdx.y];
+  const AttnWorkItem it = items[blockIdx.y];
   // an item flagged alt without an alt buffer (host bug) would write row B + q of the main buffer, past its end:
   // dropped (workgroup-uniform), as the decode kernel drops malformed items
   if (it.alt != 0 && ap.part == nullptr) return;
@@ -481,7 +478,7 @@ __global__ __launch_bounds__(512, 2) void attn_tile_kernel(const TileItem* __res
   }
 }
 
-// Host launcher (bf16 KV only; the fp8 cache keeps tile variant 0). Items: int32 [n, 8] as attn_prefill_kernel.
+// Host launcher (bf16 KV only; the fp8 cache keeps tile variant 0). Items: int32 [n, 8] AttnWorkItem records.
 extern "C" hipError_t kafka_launch_attn_tile(const void* items, int n_items, const bf16* q, int64_t q_stride,
                                             const void* k_cache, const void* v_cache, int Hkv, int G, int D,
                                             const int* block_tables, int bt_stride, const int* q_limit, bf16* out,
@@ -501,7 +498,7 @@ extern "C" hipError_t kafka_launch_attn_tile(const void* items, int n_items, con
   // the same keys.
   // Its bf16 partials are stored sc1 (16-B stores that leave this XCD's L2: +0.2..0.6 %, bench_ab_part_sc1.jsonl).
   auto kern = stamps ? attn_tile_kernel<8> : part_bf16 ? attn_tile_kernel<0, 2, 1> : attn_tile_kernel<0>;
-  kern<<<dim3(Hkv, n_items), 512, 0, st>>>(reinterpret_cast<const TileItem*>(items), q, q_stride,
+  kern<<<dim3(Hkv, n_items), 512, 0, st>>>(reinterpret_cast<const AttnWorkItem*>(items), q, q_stride,
                                            static_cast<const bf16*>(k_cache), static_cast<const bf16*>(v_cache), Hkv,
                                            G, block_tables, bt_stride, q_limit, out, out_stride, out_part, lse_part,
                                            S_total, scale_log2, part_bf16, AltPart{alt_part, alt_lse, alt_S, alt_tok_off});

@@ -5,113 +5,9 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
-typedef unsigned short bf16;  // raw bf16 storage on the host side
+#include "kafka_abi.h"  // bf16, the kernel launchers' prototypes, FinArgs, layout constants
 
-extern "C" {
-hipError_t kafka_launch_rmsnorm(bf16* out, int64_t os, const bf16* x, int64_t xs, const bf16* w, int T, int d, float eps,
-                          hipStream_t st);
-hipError_t kafka_launch_fused_add_rmsnorm(bf16* out, int64_t os, const bf16* x, int64_t xs, bf16* resid, int64_t rs,
-                                    const bf16* w, int T, int d, float eps, hipStream_t st);
-hipError_t kafka_launch_fused_add_rmsnorm_slab(bf16* out, int64_t os, const float* xp, int S, int64_t ps, bf16* resid,
-                                               int64_t rs, const bf16* w, int T, int d, float eps, hipStream_t st);
-hipError_t kafka_launch_silu_mul(bf16* out, const bf16* x, int64_t xs, int T, int F, hipStream_t st);
-hipError_t kafka_launch_silu_mul_slab(bf16* out, const float* xp, int S, int64_t ps, int T, int F, hipStream_t st);
-hipError_t kafka_launch_rope_kv(const bf16* qkv, const float* qp, int S, int64_t ps, int64_t qkv_stride,
-                                const int64_t* positions, const float* cos_sin, bf16* q_out, int64_t q_stride,
-                                bf16* k_cache, bf16* v_cache, const int64_t* slot_mapping, int T, int Hq, int Hkv,
-                                int D, int block_size, hipStream_t st);
-hipError_t kafka_launch_rope_kv_fp8(const bf16* qkv, const float* qp, int S, int64_t ps, int64_t qkv_stride,
-                                    const int64_t* positions, const float* cos_sin, bf16* q_out, int64_t q_stride,
-                                    uint8_t* k_cache, uint8_t* v_cache, const int64_t* slot_mapping, int T, int Hq,
-                                    int Hkv, int D, hipStream_t st);
-hipError_t kafka_launch_attn_decode(const bf16* q, int64_t q_stride, const void* k_cache, const void* v_cache, int fp8,
-                                    int n_items, int B, int Hkv, int G, int D, const int* block_tables, int bt_stride,
-                                    const int* items, float* out_part, float* lse_part, int S_total, float scale,
-                                    bf16* out, int64_t out_stride, int* tickets, const bf16* pre_bf16,
-                                    const float* m_part, const float* m_lse, int m_S, int m_rows, bf16* m_out,
-                                    int64_t m_out_stride, hipStream_t st);
-hipError_t kafka_launch_attn_prefill(const void* items, int n_items, const bf16* q, int64_t q_stride,
-                                     const void* k_cache, const void* v_cache, int fp8, int Hkv, int G, int D,
-                                     const int* block_tables, int bt_stride, const int* q_limit, bf16* out,
-                                     int64_t out_stride, float* out_part, float* lse_part, int S_total, float scale,
-                                     int variant, int part_bf16, float* alt_part, float* alt_lse, int alt_S,
-                                     int alt_tok_off, hipStream_t st);
-hipError_t kafka_launch_attn_merge(const float* part, const float* lse, int rows, int Hq, int S, int D, bf16* out,
-                                   int64_t out_stride, float* lse_out, const bf16* pre, int npre, hipStream_t st);
-hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int64_t stride, int B, int V, const float* temperature,
-                         const float* top_p, const int* top_k, const int64_t* seeds, const int64_t* step,
-                         int64_t* out_tokens, int* ws, int nsplit, const int* proc, const uint32_t* mask_tab,
-                         int64_t mask_ld, int* counts, int64_t cnt_ld, hipStream_t st);
-int kafka_wstream_plan(int M, int N, int K, int max_splits, int* mt, int* kc, int* splits);
-hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int mt, int kc,
-                                     int splits, int nt, int kw, int pin, int glu, bf16* Y, int64_t ldy, float* P,
-                                     hipStream_t st);
-hipError_t kafka_launch_slab_reduce(const float* P, int S, int M, int N, bf16* Y, int64_t ldy, hipStream_t st);
-// host mirror of wstream_gemm.hip's FinArgs (same field order and types; size cross-checked at first use)
-struct FinArgs {
-  int* tickets;
-  const float* ss_in;
-  int nss, ss_ld;
-  float inv_d, eps;
-  bf16* resid;
-  int64_t ldr;
-  const bf16* nw;
-  bf16* xn;
-  int64_t ldxn;
-  float* ss_out;
-  int ss_out_ld;
-  const int64_t* positions;
-  const float* cos_sin;
-  bf16* q_out;
-  int64_t q_stride;
-  bf16* k_cache;
-  bf16* v_cache;
-  const int64_t* slots;
-  int Hq, Hkv;
-  uint64_t* stamps;
-  int* err;
-};
-int kafka_fin_args_size();
-hipError_t kafka_launch_wstream_fin(int fin, const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int mt,
-                                    int kc, int splits, int kw, int pin, bf16* Y, int64_t ldy, float* P,
-                                    const FinArgs* fa, hipStream_t st);
-hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, const bf16* Wt, int e_local, int N, int K,
-                                        const int* perm_tok, const float* perm_w, const int* expert_off, int e_lo,
-                                        int max_rows, int gather, bf16* Y, int64_t ldy, float* out, int64_t ldo,
-                                        int pin, hipStream_t st);
-hipError_t kafka_launch_moe_route(const bf16* logits, int64_t ld, int T, int E, int K, int BM, float* topk_w,
-                                  int* topk_e, int* perm_tok, float* perm_w, int* expert_off, int* tile_off,
-                                  hipStream_t st);
-hipError_t kafka_launch_grouped_gemm(const bf16* X, int64_t ldx, const bf16* W, int N, int Kd, const int* perm_tok,
-                                     const float* perm_w, const int* expert_off, const int* tile_off, int e_lo,
-                                     int e_n, int max_tiles, int gather, bf16* Y, int64_t ldy, float* out,
-                                     int64_t ldo, hipStream_t st);
-hipError_t kafka_car_alloc(int64_t bytes, void** out);
-int64_t kafka_car_header_bytes();
-hipError_t kafka_car_timing(const void* own, uint64_t* ring_out, int* epoch_out);
-hipError_t kafka_car_ipc_handle(void* p, hipIpcMemHandle_t* h);
-hipError_t kafka_car_open(const hipIpcMemHandle_t* h, void** out);
-hipError_t kafka_car_close(void* p);
-hipError_t kafka_car_free(void* p);
-hipError_t kafka_launch_car_allreduce(char* const* bases, int nranks, int rank, const bf16* x, const float* xp, int S,
-                                      int64_t ps, bf16* y, int64_t n8, int64_t max_bytes, int nblocks,
-                                      hipStream_t st);
-hipError_t kafka_launch_car_a2a(char* const* bases, int nranks, int rank, const void* send, int64_t nbytes, void* recv,
-                                int64_t bpd, int bcast, int64_t max_bytes, int nblocks, hipStream_t st);
-hipError_t kafka_launch_ep_dispatch(const bf16* x, int64_t ldx, const int* topk_e, int lo, int n_pairs, int k, int El,
-                                    int ep, int C, int MR, int d, bf16* img, int* slot_map, hipStream_t st);
-hipError_t kafka_launch_ep_recv_route(const bf16* img, int ep, int C, int MR, int d, int El, int BM, int* perm_tok,
-                                      float* perm_w, int* expert_off, int* tile_off, hipStream_t st);
-hipError_t kafka_launch_ep_combine(const bf16* back, const int* slot_map, const float* topk_w, int lo, int n_own,
-                                   int k, int d, bf16* out, int64_t ldo, hipStream_t st);
-int kafka_skinny_plan(int M, int N, int K, int max_splits, int* splits);
-hipError_t kafka_launch_skinny_gemm(const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int splits,
-                                    int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st);
-hipError_t kafka_launch_car_allreduce_add_rmsnorm(char* const* bases, int nranks, int rank, const bf16* x,
-                                                  const float* xp, int S, int64_t ps, int T, int d, bf16* resid,
-                                                  int64_t rs, const bf16* w, float eps, bf16* out, int64_t os,
-                                                  int64_t max_bytes, int nblocks, const bf16* pre, int64_t pre_s, int dpre, hipStream_t st);
-}  // extern "C"
+using kafka::FinArgs;
 
 #define CHECK_CUDA(x) TORCH_CHECK((x).is_cuda(), #x " must be a GPU tensor")
 #define CHECK_DT(x, dt) TORCH_CHECK((x).scalar_type() == (dt), #x " has wrong dtype")
@@ -182,7 +78,7 @@ static void silu_mul(at::Tensor out, at::Tensor x) {
 }
 
 // Paged KV caches: bf16 K[blocks, Hkv, 16, 128] / V[blocks, Hkv, 128, 16], or fp8 (e4m3 + per-token exponents,
-// rope_kv.hip) as uint8 K[blocks, Hkv, 16 * 128 + 32] / V[blocks, Hkv, 128 * 16].
+// rope_kv.hip) as uint8 K[blocks, Hkv, KPAGE8] / V[blocks, Hkv, VPAGE8] (kafka_abi.h).
 static bool is_fp8_cache(const at::Tensor& k) { return k.scalar_type() == at::kByte; }
 
 static void check_cache_pair(const at::Tensor& k_cache, const at::Tensor& v_cache) {
@@ -190,8 +86,8 @@ static void check_cache_pair(const at::Tensor& k_cache, const at::Tensor& v_cach
   TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda(), "caches must be GPU tensors");
   if (is_fp8_cache(k_cache)) {
     CHECK_DT(v_cache, at::kByte);
-    TORCH_CHECK(k_cache.dim() == 3 && v_cache.dim() == 3 && k_cache.size(2) == 16 * 128 + 32 &&
-                    v_cache.size(2) == 128 * 16 && k_cache.size(0) == v_cache.size(0) &&
+    TORCH_CHECK(k_cache.dim() == 3 && v_cache.dim() == 3 && k_cache.size(2) == kafka::KPAGE8 &&
+                    v_cache.size(2) == kafka::VPAGE8 && k_cache.size(0) == v_cache.size(0) &&
                     k_cache.size(1) == v_cache.size(1),
                 "fp8 paged caches must be uint8 K[blocks,Hkv,2080] / V[blocks,Hkv,2048]");
     return;
@@ -254,7 +150,7 @@ static void rope_kv_write(at::Tensor qkv, at::Tensor positions, at::Tensor cos_s
                                     cur_stream()));
 }
 
-// items: int32 [n, 8] decode work items (b, lo, hi, split, nsplit, npre, 0, 0) — see attention.hip DecodeItem.
+// items: int32 [n, 8] decode work items (b, lo, hi, split, nsplit, npre, 0, 0) — see kafka_abi.h DecodeItem.
 // Their values are device data; the kernel drops an item whose b / slots fall outside the checked buffer shapes.
 static void attn_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, at::Tensor block_tables,
                         at::Tensor items, at::Tensor out_part, at::Tensor lse_part, double scale,
@@ -268,8 +164,8 @@ static void attn_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, at
   const int B = q.size(0), Hq = q.size(1), Hkv = k_cache.size(1);
   TORCH_CHECK(Hq % Hkv == 0 && Hq / Hkv <= 8, "decode kernel needs Hq/Hkv <= 8");
   TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) >= B && block_tables.stride(1) == 1, "block_tables");
-  TORCH_CHECK(items.is_cuda() && items.is_contiguous() && items.dim() == 2 && items.size(1) == 8,
-              "items must be a device int32 [n, 8]");
+  TORCH_CHECK(items.is_cuda() && items.is_contiguous() && items.dim() == 2 &&
+                  items.size(1) == kafka::ITEM_INTS, "items must be a device int32 [n, 8]");
   TORCH_CHECK(out_part.is_contiguous() && out_part.dim() == 4 && out_part.size(0) >= B && out_part.size(1) == Hq &&
                   out_part.size(3) == 128, "out_part must be [B, Hq, S_total, 128]");
   const int S_total = out_part.size(2);
@@ -335,7 +231,8 @@ static void attn_prefill(at::Tensor items, at::Tensor q, at::Tensor k_cache, at:
                          int64_t alt_tok_off) {
   CHECK_CUDA(q); CHECK_DT(q, at::kBFloat16); check_cache_pair(k_cache, v_cache);
   CHECK_DT(items, at::kInt); CHECK_DT(block_tables, at::kInt); CHECK_DT(q_limit, at::kInt);
-  TORCH_CHECK(items.is_contiguous() && items.dim() == 2 && items.size(1) == 8, "items must be [n, 8] int32");
+  TORCH_CHECK(items.is_contiguous() && items.dim() == 2 && items.size(1) == kafka::ITEM_INTS,
+              "items must be [n, 8] int32");
   TORCH_CHECK(q.dim() == 3 && q.stride(2) == 1 && q.stride(1) == 128 && q.size(2) == 128, "q must be [T, Hq, 128]");
   const int T = q.size(0), Hq = q.size(1), Hkv = k_cache.size(1);
   TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
@@ -542,8 +439,6 @@ static void wstream_fin(int64_t fin, at::Tensor x, at::Tensor wt, c10::optional<
                         c10::optional<at::Tensor> k_cache, c10::optional<at::Tensor> v_cache,
                         c10::optional<at::Tensor> slots, int64_t Hq, int64_t Hkv, int64_t max_splits,
                         c10::optional<at::Tensor> stamps) {
-  static const bool abi_ok = kafka_fin_args_size() == (int)sizeof(FinArgs);
-  TORCH_CHECK(abi_ok, "wstream_fin: FinArgs layout differs between the kernel and the bindings");
   TORCH_CHECK(fin >= 1 && fin <= 3, "wstream_fin: fin must be 1, 2 or 3");
   CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_DT(wt, at::kBFloat16); CHECK_LASTDIM(x);
   TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "wstream_fin: x must be [M, K] with 16-B rows");

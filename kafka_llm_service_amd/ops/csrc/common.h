@@ -14,7 +14,8 @@
 
 #include <cstdlib>
 
-typedef __bf16 bf16;
+#include "kafka_abi.h"  // bf16, the launchers' prototypes, shared structs and layout constants
+
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -99,14 +99,10 @@ static hipError_t launch_rmsnorm_t(bf16* out, int64_t os, const bf16* x, const f
   dim3 grid(T), block(256);
   if (T == 0) return hipSuccess;
   // outputs (normalised rows and the in-place residual) as 16-B sc1 stores — the lines leave this XCD's L2, so the
-  // launch ends with none of them dirty (+2.1 % on the headline with RoPE's, profiles/r06/ab/); KAFKA_SC1_NORM=0 keeps
-  // plain stores. Needs 16-B aligned rows. common.h "Store / load scopes"
-  static const bool sc1 = [] {
-    const char* e = getenv("KAFKA_SC1_NORM");
-    return e == nullptr || e[0] != '0';
-  }();
+  // launch ends with none of them dirty (+2.1 % on the headline with RoPE's, profiles/r06/ab/). Needs 16-B aligned
+  // rows; others keep plain stores. common.h "Store / load scopes"
   if (nvec <= 512 && nvec > 256) {  // e.g. d = 4096: one 16-B vector per thread, twice the loads in flight per row
-    if (sc1 && os % 8 == 0 && rs % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
+    if (os % 8 == 0 && rs % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
         (!RESID || reinterpret_cast<uintptr_t>(r) % 16 == 0))
       rmsnorm_kernel<1, RESID, 512, true><<<grid, 512, 0, st>>>(out, os, x, xp, S, ps, xs, r, rs, w, d, eps);
     else

@@ -102,8 +102,7 @@ __global__ __launch_bounds__(1024) void rope_kv_kernel(const bf16* __restrict__ 
   }
 }
 
-constexpr int KPAGE8 = 16 * 128 + 32;
-constexpr int MAX_HKV8 = 64;
+constexpr int MAX_HKV8 = 64;  // (fp8 page constants KPAGE8 / VPAGE8 / KEXP8 / VEXP8: kafka_abi.h)
 
 // e such that amax * 2^-e <= 448 (frexp of amax / 448); 0 for an all-zero vector
 __device__ __forceinline__ int fp8_exponent(float amax) {
@@ -212,16 +211,16 @@ __global__ __launch_bounds__(1024) void rope_kv_fp8_kernel(const bf16* __restric
       const int p = 2 * (q8 >> 2) + (q8 & 1), second = (q8 >> 1) & 1;
       *reinterpret_cast<uint2*>(kpage + (p * 16 + off) * 16 + 8 * second) = pack_fp8x8(z);
     }
-    if (c == 0) kpage[2048 + off] = (uint8_t)(int8_t)e;
+    if (c == 0) kpage[KEXP8 + off] = (uint8_t)(int8_t)e;
   } else {
     float z[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) z[j] = y1[j] * inv;
     const uint2 w = pack_fp8x8(z);
-    uint8_t* dst = v_cache + (blk * Hkv + head) * (int64_t)(D * 16) + vt_pos(off);
+    uint8_t* dst = v_cache + (blk * Hkv + head) * (int64_t)VPAGE8 + vt_pos(off);
 #pragma unroll
     for (int j = 0; j < 8; ++j) dst[(c + j) * 16] = (uint8_t)(((j < 4 ? w.x : w.y) >> (8 * (j & 3))) & 0xff);
-    if (c == 0) kpage[2064 + vt_pos(off)] = (uint8_t)(int8_t)e;
+    if (c == 0) kpage[VEXP8 + vt_pos(off)] = (uint8_t)(int8_t)e;
   }
 }
 
@@ -255,12 +254,8 @@ extern "C" hipError_t kafka_launch_rope_kv(const bf16* qkv, const float* qp, int
   const int units = (Hq + Hkv) * (D / 16) + Hkv * (D / 8);
   const int nt = 64, ny = (units + nt - 1) / nt;
   const dim3 grid(T, ny);
-  // q and K rows as 16-B sc1 stores (KAFKA_SC1_ROPE=0: plain; with the RMSNorm outputs +2.1 %, common.h)
-  static const bool sc1 = [] {
-    const char* e = getenv("KAFKA_SC1_ROPE");
-    return e == nullptr || e[0] != '0';
-  }();
-  if (D == 128 && sc1 && q_stride % 8 == 0)
+  // q and K rows as 16-B sc1 stores when q's rows are 16-B aligned (with the RMSNorm outputs +2.1 %, common.h)
+  if (D == 128 && q_stride % 8 == 0)
     rope_kv_kernel<128, true><<<grid, nt, 0, st>>>(qkv, qp, S, ps, qkv_stride, positions, cos_sin, q_out, q_stride,
                                                 k_cache, v_cache, slot_mapping, Hq, Hkv, block_size);
   else if (D == 128)

@@ -47,29 +47,7 @@ namespace kafka {
 // workgroup. Memory-model notes: common.h "Store / load scopes".
 enum { FIN_NONE = 0, FIN_RES = 1, FIN_ROPE = 2, FIN_GLU = 3 };
 
-struct FinArgs {
-  int* tickets;                 // [N / 128] zeroed once, re-armed by each column block's finisher
-  const float* ss_in;           // [nss][ss_ld] partial sums of h^2 of X's rows (nullptr: X is already normalised)
-  int nss, ss_ld;
-  float inv_d, eps;
-  bf16* resid;                  // FIN_RES: residual stream [M, N] (row stride ldr), updated in place
-  int64_t ldr;
-  const bf16* nw;               // FIN_RES: the next RMSNorm's weight [N]
-  bf16* xn;                     // FIN_RES: bf16(h (.) nw) [M, N] (row stride ldxn): the next GEMM's A operand
-  int64_t ldxn;
-  float* ss_out;                // FIN_RES: [N / 128][ss_out_ld]
-  int ss_out_ld;
-  const int64_t* positions;     // FIN_ROPE
-  const float* cos_sin;         // [max_pos, 128]: cos in [0, 64), sin in [64, 128)
-  bf16* q_out;                  // [M, Hq, 128] (row stride q_stride)
-  int64_t q_stride;
-  bf16* k_cache;                // [blocks, Hkv, 16, 128] in D/8 chunk planes (rope_kv.hip)
-  bf16* v_cache;                // [blocks, Hkv, 128, 16] V^T, key o at vt_pos(o)
-  const int64_t* slots;         // [M] (-1: no KV write) or nullptr
-  int Hq, Hkv;
-  uint64_t* stamps;             // optional phase stamps [grid][8] (100 MHz clock; benchmarks/fused_bench.py)
-  int* err;                     // bit 0 set if a finisher could not reach a split's slab (see "home XCD" below)
-};
+// (FinArgs, the launchers' argument block for these epilogues: kafka_abi.h)
 
 // split s's 16 B: from this XCD's L2 (the split stored it there: same XCD) or, flagged, agent-coherent (sc1)
 template <bool MIXED>
@@ -234,12 +212,19 @@ __device__ __forceinline__ void fin_rope(const float* tp, const float* P, int by
   }
 }
 
+// wide (per call): which outputs may leave as 16-B sc1 stores — WIDE_P: the split-K slabs P (both launchers' slabs
+// are contiguous fp32, so kafka_launch_wstream_gemm always sets it; the FIN_RES / FIN_ROPE finishers store their
+// slabs themselves and never consult it), WIDE_Y: the un-split bf16 outputs (Y's rows 16-B aligned). Without the
+// bit an output is written one element per accumulator. (No launcher reaches the per-element P stores today; the arm
+// stays because dropping it changes register allocation — MT = 3 FIN_GLU gains 4 VGPR spills — which wants its own
+// measurement.)
+enum { WIDE_P = 1, WIDE_Y = 2 };
 template <int MT, int KC, bool NT, int KW, bool PIN, int FIN = FIN_NONE>
 __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __restrict__ X, int64_t ldx,
                                                                  const bf16x8* __restrict__ Wt, int M, int N, int K,
                                                                  int ks, bf16* __restrict__ Y, int64_t ldy,
                                                                  float* __restrict__ P, int glu, int row_tiles,
-                                                                 int slab16, FinArgs fa) {
+                                                                 int wide, FinArgs fa) {
   constexpr int NTH = 256 * KW;
   constexpr int ROWS = 32 * MT;
   constexpr int CPR = KC / 8;             // 16-B chunks per X row of one K chunk
@@ -561,7 +546,7 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
         for (int i = 0; i < 16; ++i) red[(((ct >> 1) * MT + mt) * 16 + i) * 64 + lane] = acc[mt][i];
     }
     __syncthreads();
-    if (slab16 & 2) {
+    if (wide & WIDE_Y) {
       // the workgroup's 64 output columns (128 B per row) through an LDS tile, then 16-B sc1 stores: 8 lanes per row
       bf16* ty = reinterpret_cast<bf16*>(red + 2 * MT * 16 * 64);  // [ROWS][64], after the up-tile exchange
       if (active && kh == 0 && !(ct & 1)) {
@@ -597,11 +582,11 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
           }
         }
     }
-  } else if (P == nullptr && !glu && (slab16 & 2)) {
+  } else if (P == nullptr && !glu && (wide & WIDE_Y)) {
     // un-split bf16 output (the lm_head): the workgroup's 128 columns (256 B per row) through an LDS tile, then
     // 16-B sc1 stores, 8 lanes per 128-B line
     bf16* ty = reinterpret_cast<bf16*>(&xs[0][0]);  // [ROWS][128]
-    __syncthreads();  // (workgroup-uniform: P, glu and slab16 are kernel arguments)
+    __syncthreads();  // (workgroup-uniform: P, glu and wide are kernel arguments)
     if (active && kh == 0) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
@@ -616,12 +601,12 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
         store16_slab(reinterpret_cast<float*>(Y + (int64_t)row * ldy + c0 + 8 * c),
                      *reinterpret_cast<const f32x4*>(ty + row * 128 + 8 * c));
     }
-  } else if (P != nullptr && (slab16 & 1)) {
+  } else if (P != nullptr && (wide & WIDE_P)) {
     // split-K slab through a per-wave LDS transpose (the X stage is dead): each lane then holds 4 consecutive columns
     // of a row and writes them with one 16-B sc1 store (the line leaves this XCD's L2 — the consumer kernel runs on
     // every XCD — and the launch ends with fewer dirty lines to write back)
     float* tp = reinterpret_cast<float*>(&xs[0][0]) + ct * (ROWS * 32);
-    __syncthreads();  // (workgroup-uniform: P and slab16 are kernel arguments)
+    __syncthreads();  // (workgroup-uniform: P and wide are kernel arguments)
     if (active && kh == 0) {
       const int cbase = glu ? ((nb & 1) ? (N >> 1) : 0) + (nb >> 1) * 32 : nb * 32;
 #pragma unroll
@@ -875,16 +860,12 @@ extern "C" hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, cons
   float* p = splits > 1 ? P : nullptr;
   // split-K slabs leave as 16-B sc1 stores through an LDS transpose (was one 4-B store per accumulator, the lines
   // kept dirty in the XCD's L2): +2.0 % on the headline, in-step GPU time 7.50 vs 7.65 ms
-  // (profiles/r05/bench_ab_wstream_slab16_sc1.jsonl); KAFKA_WSTREAM_SLAB16=0 restores the old epilogue
-  // bit 1: the un-split bf16 outputs (fused SwiGLU, lm_head) the same way through a workgroup LDS tile, whole 128-B
-  // lines per store instruction (was one 2-B store per accumulator, half lines): +1.1..2.1 %, in-step GPU time 7.37
-  // vs 7.45-7.49 ms (profiles/r05/bench_ab_wstream_wide_y.jsonl)
-  static const int slab16 = [] {
-    const char* e = getenv("KAFKA_WSTREAM_SLAB16");
-    return e ? atoi(e) : 3;
-  }();
-  // (16-B stores of Y need 16-B aligned rows)
-  const int wide = (Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0)) ? (slab16 & 1) : slab16;
+  // (profiles/r05/bench_ab_wstream_slab16_sc1.jsonl).
+  // The un-split bf16 outputs (fused SwiGLU, lm_head) the same way through a workgroup LDS tile, whole 128-B lines
+  // per store instruction (was one 2-B store per accumulator, half lines): +1.1..2.1 %, in-step GPU time 7.37 vs
+  // 7.45-7.49 ms (profiles/r05/bench_ab_wstream_wide_y.jsonl) — 16-B stores of Y need 16-B aligned rows
+  const bool y_unaligned = Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0);
+  const int wide = y_unaligned ? WIDE_P : (WIDE_P | WIDE_Y);
 #define KAFKA_WS(MT_, KC_, KW_, PIN_)                                                                            \
   do {                                                                                                          \
     if (nt)                                                                                                     \
@@ -915,8 +896,6 @@ extern "C" hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, cons
   return hipGetLastError();
 }
 
-extern "C" int kafka_fin_args_size() { return (int)sizeof(FinArgs); }
-
 // Fused decode-layer GEMMs (FIN_RES / FIN_ROPE / FIN_GLU above): one row tile (M <= 128), N % 128 == 0, S in
 // {1, 2, 4, 8}; P = [S][M][N] fp32 scratch (unused for S == 1); FIN_GLU needs S == 1.
 extern "C" hipError_t kafka_launch_wstream_fin(int fin, const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K,
@@ -946,11 +925,8 @@ extern "C" hipError_t kafka_launch_wstream_fin(int fin, const bf16* X, int64_t l
   const int ks = K / splits;
   const auto* wt = reinterpret_cast<const bf16x8*>(Wt);
   float* p = splits > 1 ? P : nullptr;
-  static const int slab16 = [] {
-    const char* e = getenv("KAFKA_WSTREAM_SLAB16");
-    return e ? atoi(e) : 3;
-  }();
-  const int wide = (Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0)) ? 0 : (slab16 & 2);
+  // (only FIN_GLU's Y consults it: wide stores when its rows are 16-B aligned)
+  const int wide = (Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0)) ? 0 : WIDE_Y;
   const int glu = fin == FIN_GLU ? 1 : 0;
 #define KAFKA_WF(MT_, KC_, KW_, PIN_, FIN_)                                                                      \
   wstream_gemm_kernel<MT_, KC_, true, KW_, PIN_, FIN_><<<grid, 256 * KW_, 0, st>>>(X, ldx, wt, M, N, K, ks, Y, ldy, p, \
@@ -1007,15 +983,10 @@ extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, c
   // MT = 4 (128-row tiles on 128-deep K chunks) for large steps: with 64-row tiles every
   // row tile of an expert re-streams its weights, and those tiles run far apart in dispatch order (blockIdx.z is the
   // slowest dimension), so no cache keeps the slice between them — an expert with 65..128 rows read its 352 MB twice.
-  // KAFKA_MOE_MT4=0 keeps 64-row tiles (A/B).
-  static const bool mt4 = [] {
-    const char* e = getenv("KAFKA_MOE_MT4");
-    return e == nullptr || e[0] != '0';
-  }();
   // (64-row tiles stay below 193 rows: an expert then rarely fills a second tile, and they stream faster there —
   // benchmarks/moe_bench.py T = 128 / 192: 493 / 522 vs 517 / 551 us per layer; T = 256 / 384 / 512: 761 / 1002 /
   // 1303 vs 601 / 691 / 1004, profiles/r06/mixtral/)
-  const int MT = max_rows <= 32 ? 1 : ((max_rows <= 192 || !mt4) ? 2 : 4);
+  const int MT = max_rows <= 32 ? 1 : (max_rows <= 192 ? 2 : 4);
   const dim3 grid((N + 127) / 128, e_local, (max_rows + 32 * MT - 1) / (32 * MT));
   const auto* wt = reinterpret_cast<const bf16x8*>(Wt);
 #define KAFKA_WG(MT_, G_, C_)                                                                                   \

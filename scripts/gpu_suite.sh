@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU validation of the tree as it is: the GPU test suite (once per SUITE_ENVS set, e.g. "base:KAFKA_X=0
-# sc1:KAFKA_SC1_NORM=1,KAFKA_SC1_ROPE=1"), smoke(), and bench runs (BENCHES="200/20 200/20 20/5"). Output under
+# nojoin:KAFKA_JOIN_SUFFIX=0,KAFKA_FUSED_DECODE=0"), smoke(), and bench runs (BENCHES="200/20 200/20 20/5"). Output under
 # gpurun_out/suite/. Stops at the first failure of the default set; later env sets only report.
 # Usage: gpurun --timeout 1200 -- 'SUITE_ENVS="base:KAFKA_X=0" BENCHES="20/5" bash scripts/gpu_suite.sh'
 set -o pipefail

@@ -594,6 +594,22 @@ def test_retile_joins_contiguous_spans():
     assert retile([], 64) == []
 
 
+def test_retired_switches_stay_retired():
+    """The decided A/B switches are gone from the hot path (kernels, models, model runner): no file there names one."""
+    from pathlib import Path
+
+    import kafka_llm_service_amd as pkg
+
+    retired = ["KAFKA_SC1_NORM", "KAFKA_SC1_ROPE", "KAFKA_SC1_ATTN", "KAFKA_WSTREAM_SLAB16", "KAFKA_MOE_MT4",
+               "KAFKA_FUSED_PREFILL_MERGE", "KAFKA_RETILE_JOINS", "KAFKA_FIXED_DECODE_ITEMS"]
+    root = Path(pkg.__file__).resolve().parent
+    files = [p for d in ("ops", "models") for p in (root / d).rglob("*")
+             if p.suffix in (".py", ".hip", ".h", ".cpp")] + [root / "engine" / "model_runner.py"]
+    assert len(files) > 10
+    found = [(p.name, n) for p in files for n in retired if n in p.read_text(errors="replace")]
+    assert not found, found
+
+
 def test_plan_prefill_items_with_prefix_offset():
     """A tile behind a cascade prefix (lo > 0) attends only [lo, extent) and writes partials from slot s0 on."""
     from kafka_llm_service_amd.engine.model_runner import plan_prefill_items

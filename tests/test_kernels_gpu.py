@@ -840,3 +840,108 @@ def test_cascade_pass_with_new_turn_rows(cuda):
             p_ = torch.softmax(s_, -1)
             o_ref[t, h * G:(h + 1) * G] = p_ @ vv[:pos + 1, h].float()
     _close(out, o_ref, atol=0.02, msg="new-turn rows through the cascade pass")
+
+
+# ---- outputs whose rows are not 16-B aligned: the launchers fall back from the 16-B sc1 stores to the plain-store
+# kernel variants. Each case at the smallest shape that takes the branch; SENTINEL fills the bytes around the output.
+SENTINEL = 7.0
+
+
+def _offset_rows(T, d, device):
+    """bf16 [T, d] view starting 4 elements (8 bytes) into its buffer, and the buffer."""
+    buf = torch.full((4 + T * d,), SENTINEL, device=device, dtype=torch.bfloat16)
+    return buf[4:].view(T, d), buf
+
+
+def _padded_rows(T, d, device):
+    """bf16 [T, d] view with row stride d + 4 (rows 8-B aligned only), and the buffer."""
+    buf = torch.full((T, d + 4), SENTINEL, device=device, dtype=torch.bfloat16)
+    return buf[:, :d], buf
+
+
+def test_rmsnorm_unaligned_out(cuda):
+    torch.manual_seed(20)
+    T, d = 3, 4096
+    x = torch.randn(T, d, device=cuda, dtype=torch.bfloat16)
+    w = torch.randn(d, device=cuda, dtype=torch.bfloat16)
+    out, buf = _offset_rows(T, d, cuda)
+    ops.rmsnorm(x, w, 1e-5, out=out)
+    _close(out, ref.rmsnorm(x.cpu(), w.cpu(), 1e-5), atol=0.05, rtol=0.01, msg="rmsnorm")
+    assert (buf[:4] == SENTINEL).all()
+
+
+def test_fused_add_rmsnorm_unaligned_out(cuda):
+    torch.manual_seed(21)
+    T, d = 3, 4096
+    x = torch.randn(T, d, device=cuda, dtype=torch.bfloat16)
+    w = torch.randn(d, device=cuda, dtype=torch.bfloat16)
+    r, rbuf = _offset_rows(T, d, cuda)
+    r.copy_(torch.randn(T, d, device=cuda))
+    out, obuf = _offset_rows(T, d, cuda)
+    y_ref, s_ref = ref.fused_add_rmsnorm(x.cpu(), r.cpu(), w.cpu(), 1e-5)
+    ops.fused_add_rmsnorm(x, r, w, 1e-5, out=out)
+    _close(r, s_ref, atol=1e-2, msg="residual")
+    _close(out, y_ref, atol=0.05, rtol=0.01, msg="norm")
+    assert (rbuf[:4] == SENTINEL).all() and (obuf[:4] == SENTINEL).all()
+
+
+def test_rope_kv_write_unaligned_q_rows(cuda):
+    torch.manual_seed(22)
+    D, T, nb, Hq, Hkv = 128, 2, 2, 2, 1
+    qkv = torch.randn(T, (Hq + 2 * Hkv) * D, device=cuda, dtype=torch.bfloat16)
+    pos = torch.tensor([5, 1234], device=cuda, dtype=torch.long)
+    cs = ref.rope_cos_sin(2048, D, 500000.0, None, device=cuda)
+    slots = torch.tensor([17, 3], device=cuda, dtype=torch.long)
+    q2d, qbuf = _padded_rows(T, Hq * D, cuda)
+    q = q2d.unflatten(1, (Hq, D))
+    assert q.stride(0) == Hq * D + 4
+    k, v = _make_cache(nb, Hkv, D, cuda)
+    ops.rope_kv_write(qkv, pos, cs, q, k, v, slots, Hq, Hkv)
+    q2 = torch.empty(T, Hq, D, dtype=torch.bfloat16)
+    k2, v2 = _make_cache(nb, Hkv, D)
+    ref.rope_kv_write(qkv.cpu(), pos.cpu(), cs.cpu(), q2, k2, v2, slots.cpu(), Hq, Hkv)
+    _close(q, q2, atol=0.03, rtol=0.01, msg="q")
+    _close(k, k2, atol=0.03, rtol=0.01, msg="k")
+    assert torch.equal(v.cpu(), v2), "v cache"
+    assert (qbuf[:, Hq * D:] == SENTINEL).all()
+
+
+@pytest.mark.parametrize("pieces", [1, 2])
+def test_attn_decode_fused_merge_unaligned_out(cuda, pieces):
+    """Final bf16 rows with a row stride that is not a multiple of 16 B: one item per row, and each row split in two
+    pieces ([0, 16) and [16, 20)) that merge through the ticket counters."""
+    torch.manual_seed(23)
+    B, Hkv, G, D, L = 2, 1, 2, 128, 20
+    Hq = Hkv * G
+    k, v, bt = _random_paged(B, [L] * B, Hkv, cuda, seed=23)
+    q = torch.randn(B, Hq, D, device=cuda, dtype=torch.bfloat16)
+    scale = 1 / math.sqrt(D)
+    bounds = [0, L] if pieces == 1 else [0, 16, L]
+    items = torch.tensor([[b, bounds[s], bounds[s + 1], s, pieces, 0, 0, 0] for b in range(B) for s in range(pieces)],
+                         dtype=torch.int32, device=cuda)
+    part = torch.empty(B, Hq, pieces, D, device=cuda)
+    lse = torch.empty(B, Hq, pieces, device=cuda)
+    o2d, obuf = _padded_rows(B, Hq * D, cuda)
+    out = o2d.unflatten(1, (Hq, D))
+    assert out.stride(0) == Hq * D + 4
+    ops.attn_decode_items(q, k, v, bt, items, part, lse, scale, out=out)
+    sl = torch.full((B,), L, dtype=torch.int32)
+    o_ref, _ = ref.attn_decode_full(q.cpu(), k.cpu(), v.cpu(), bt.cpu(), sl, scale)
+    _close(out, o_ref, atol=0.02, msg=f"fused merge, unaligned out, {pieces} piece(s)")
+    assert (obuf[:, Hq * D:] == SENTINEL).all()
+
+
+def test_wstream_gemm_unaligned_y(cuda):
+    """Un-split bf16 output with ldy = N + 4 (the extension entry is the one that takes y; ops.linear_stream
+    allocates its own): one store per accumulator instead of the 16-B row stores."""
+    from kafka_llm_service_amd.ops._ext import ext
+
+    torch.manual_seed(24)
+    M, N, K = 5, 128, 256
+    x = torch.randn(M, K, device=cuda, dtype=torch.bfloat16)
+    w = (torch.randn(N, K, device=cuda) * 0.05).to(torch.bfloat16)
+    assert ops.stream_plan(M, N, K, 1)[2] == 1
+    y, ybuf = _padded_rows(M, N, cuda)
+    ext().wstream_gemm(x, ops.tile_weight(w), y, None, 1, True, False)
+    _close(y, x.float() @ w.float().t(), atol=0.02, rtol=0.01, msg="wstream, unaligned y")
+    assert (ybuf[:, N:] == SENTINEL).all()
