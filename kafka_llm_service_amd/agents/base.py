@@ -134,8 +134,11 @@ class Agent:
                         token_ids.extend(ch.token_ids)
                     if ch.usage:
                         usage = ch.usage
+                    choice = {"index": 0, "delta": delta, "finish_reason": ch.finish_reason or None}
+                    if getattr(ch, "logprobs", None):  # (requests with ``logprobs``: the chunk's token entries)
+                        choice["logprobs"] = {"content": ch.logprobs}
                     yield {"id": cid, "object": "chat.completion.chunk", "created": created, "model": model,
-                           "choices": [{"index": 0, "delta": delta, "finish_reason": ch.finish_reason or None}]}
+                           "choices": [choice]}
             except Exception as e:
                 if first and not compacted and is_context_length_error(e) and self.context_compaction_provider:
                     self.logger.info("context length exceeded (%s); compacting", e)

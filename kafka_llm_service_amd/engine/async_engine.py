@@ -177,14 +177,17 @@ def _merge(first: StepOutput, q: asyncio.Queue):
     """Fold the outputs already waiting in ``q`` into ``first`` (token ids concatenated, the last one's status): one
     pass through the provider / agent / SSE layers per wakeup instead of one per token when the API loop is busy."""
     ids = list(first.new_token_ids)
+    lps = list(first.logprobs) if first.logprobs is not None else None
     last = first
     while not q.empty():
         o = q.get_nowait()
         if isinstance(o, BaseException):
             return o
         ids += o.new_token_ids
+        if o.logprobs is not None:
+            lps = (lps or []) + list(o.logprobs)
         last = o
         if o.finished:
             break
     return StepOutput(last.request_id, ids, last.finished, last.finish_reason, last.num_prompt_tokens,
-                      last.num_output_tokens, last.num_cached_tokens)
+                      last.num_output_tokens, last.num_cached_tokens, logprobs=lps)

@@ -200,7 +200,9 @@ def _serve_pipe(eng, conn) -> None:
             outs = eng.step()
             if outs:
                 conn.send(("out", [(o.request_id, o.new_token_ids, o.finished, o.finish_reason, o.num_prompt_tokens,
-                                    o.num_output_tokens, o.num_cached_tokens) for o in outs], time.perf_counter()))
+                                    o.num_output_tokens, o.num_cached_tokens)
+                                   + ((o.logprobs,) if o.logprobs is not None else ())  # records, only if asked
+                                   for o in outs], time.perf_counter()))
 
 
 class DPClient:
@@ -432,12 +434,13 @@ class DPClient:
                                 {"outs": len(msg[1])})
                 batches: dict = {}
                 with self._lock:
-                    for rid, toks, fin, reason, npt, nout, ncached in msg[1]:
+                    for rid, toks, fin, reason, npt, nout, ncached, *lp in msg[1]:  # (+ logprob records if asked)
                         s = self._streams.get(rid)
                         if s is None:
                             continue
                         batches.setdefault(s[0], []).append(
-                            (s[1], StepOutput(rid, toks, fin, reason, npt, nout, ncached)))
+                            (s[1], StepOutput(rid, toks, fin, reason, npt, nout, ncached,
+                                              logprobs=lp[0] if lp else None)))
                         if fin:
                             self._streams.pop(rid, None)
                             self._loads[r] -= 1

@@ -224,7 +224,9 @@ def serve_pipe_lockstep(eng, st, conn) -> None:
             idle_since = None
         if outs:
             conn.send(("out", [(o.request_id, o.new_token_ids, o.finished, o.finish_reason, o.num_prompt_tokens,
-                                o.num_output_tokens, o.num_cached_tokens) for o in outs], time.perf_counter()))
+                                o.num_output_tokens, o.num_cached_tokens)
+                               + ((o.logprobs,) if o.logprobs is not None else ())  # records, only if asked
+                               for o in outs], time.perf_counter()))
         if stopping:
             conn.send(("stopped",))
             return

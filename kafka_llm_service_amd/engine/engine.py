@@ -410,6 +410,7 @@ class LLMEngine:
         t_w = time.perf_counter()
         with trace.span("collect"):
             toks = self.runner.collect(cur.launched)
+            lps = self.runner.collect_logprobs(cur.launched) if cur.launched.logprobs is not None else None
         now = time.perf_counter()
         self.host_s["wait"] += now - t_w
         if now - self._t_done < 1.0:  # back-to-back steps: the interval is this GPU's step time
@@ -418,8 +419,8 @@ class LLMEngine:
         self.stats["step_time"] += now - cur.t0
         self.stats["steps"] += 1
         outs: list[StepOutput] = []
-        for s, idx, t in zip(cur.sampled, cur.slots, toks):
-            if s.finished:  # ended (stop / abort) while this step was in flight: its row was void
+        for row, (s, idx, t) in enumerate(zip(cur.sampled, cur.slots, toks)):
+            if s.finished:  # ended (stop / abort) while this step was in flight: its row was void (its record too)
                 continue
             rb = getattr(s.params.allowed_tokens_fn, "rollback_at", None)
             if rb is not None and rb(s.output_ids, idx):
@@ -447,8 +448,15 @@ class LLMEngine:
                 self.sched.finish(s, reason)
                 self.requests.pop(s.request_id, None)
                 trace.request_span(s, now)
+            rec = None
+            if lps is not None and s.params.logprobs:
+                # the token's raw log-probability (a grammar-forced token's too) and the request's own number of
+                # alternatives (the step computed its largest top_logprobs); a rolled-back row never gets here
+                lp, ids, vals = lps[row]
+                k = s.params.top_logprobs
+                rec = [(t, lp, ids[:k], vals[:k])]
             outs.append(StepOutput(s.request_id, [t], reason is not None, reason, len(s.prompt_ids), n_out,
-                                   s.num_cached))
+                                   s.num_cached, logprobs=rec))
         self.host_s["finish"] += time.perf_counter() - now
         return outs
 

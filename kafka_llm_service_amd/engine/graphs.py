@@ -67,6 +67,11 @@ class DecodeGraphs:
                 h.n_late, h.late_off, sp.greedy, sp.proc is not None, cap)
 
     def eligible(self, h, sp) -> bool:
+        if sp.lp_rows is not None and self.runner.model.tp == 1:
+            # logprob rows read the step's logits, which at TP = 1 are internal to the captured graph: such a step
+            # runs eagerly. Under TP the graph ends at the logit shard and the sampler is eager anyway, so the
+            # decision stays what every rank takes from the broadcast plan (followers never see lp_rows)
+            return False
         return not self.disabled and h.B > 0 and h.T == h.B and h.n_items == 0
 
     # ------------------------------------------------------------------------------------------------------------
@@ -97,6 +102,7 @@ class DecodeGraphs:
         logits = pstate.tp_all_gather_lastdim(local)[:, :r.vocab]
         toks = r.sample_device(logits, sp)
         r.tok_buf[:toks.shape[0]].copy_(toks)
+        r._lp_dev = r.logprobs_device(logits, toks, sp)  # (only the leader's SampleParams carry logprob rows)
         return toks
 
     def _agree(self, ok: bool) -> bool:

@@ -70,6 +70,10 @@ class SampleParams:
     greedy: bool
     upd: ProcUpdates | None = None  # table writes (new grammar mask rows, penalty slots to clear) before sampling
     known: dict | None = None       # row -> token fixed by the grammar (forced): the host knows it at launch
+    # per-token logprobs (ops.token_logprobs): the sampled rows whose request asked (int32, ascending) and the step's
+    # largest top_logprobs. NOT part of pack_plan / unpack_plan: only the rank that returns tokens computes them
+    lp_rows: np.ndarray | None = None
+    lp_k: int = 0
 
 
 _PLAN_SCALARS = ("B", "T", "nbt", "bt_w", "n_rows", "s_total", "n_dec_items", "n_prefix_items", "cascade_prefix",
@@ -153,6 +157,9 @@ class Launched:
     rows: dict | None = None        # seq_id -> row of dev_tokens
     err_idx: int | None = None      # slot of ModelRunner._err_host holding the custom all-reduce error word
     known: dict | None = None       # row -> token the grammar forced (known on the host at launch)
+    # (packed records [R, 1 + 2k] float32 — pinned host buffer on GPU —, k, sampled rows [R]) of a step with
+    # logprob rows; lands with ``event`` like the tokens
+    logprobs: tuple | None = None
 
 
 MIN_DECODE_KEYS = 256      # smallest key range of one decode work item
@@ -502,6 +509,8 @@ class ModelRunner:
         self.rows_hist = [0] * len(ROWS_BUCKETS)  # launched steps by token rows (ROWS_BUCKETS upper bounds)
         self.broadcast = None  # set on a TP leader: callable(HostStep, SampleParams) (engine/tp_worker.py)
         self._tok_host = None  # pinned landing buffers of the sampled ids
+        self._lp_host = None   # pinned landing buffers of the logprob records (allocated by the first step that asks)
+        self._lp_dev = None    # the running step's packed logprob records on the device (_run -> launch)
         self._err_host = None  # pinned landing slots of the custom all-reduce error word (TP)
         self.stager = _Stager(self.device)
         # every step's sampled ids also land here (fixed address, so hipGraphs can read it): the next step's decode
@@ -809,6 +818,7 @@ class ModelRunner:
         seeds = np.empty(n, dtype=np.int64)
         rows = []  # (row, seq, allowed) for rows that need penalties or a token constraint
         known = None
+        lp_rows, lp_k = [], 0
         for i, s in enumerate(seqs):
             p = s.params
             temp[i] = p.temperature
@@ -816,6 +826,9 @@ class ModelRunner:
             topk[i] = p.top_k
             base = p.seed if p.seed is not None else (s.seq_id * 7919)
             seeds[i] = (base * 1000003 + len(s.output_ids)) & 0x7FFFFFFFFFFFFFFF
+            if p.logprobs:
+                lp_rows.append(i)
+                lp_k = max(lp_k, p.top_logprobs)
             allowed = None
             if p.allowed_tokens_fn is not None:
                 # (a pending last token is speculated past by the constraint, ToolCallConstraint.__call__)
@@ -830,7 +843,20 @@ class ModelRunner:
         if rows:
             proc, upd = self.lp.build(rows, n)
             upd = None if upd.empty else upd
-        return SampleParams(temp, topp, topk, seeds, proc, not temp.any(), upd, known)
+        sp = SampleParams(temp, topp, topk, seeds, proc, not temp.any(), upd, known)
+        if lp_rows:
+            sp.lp_rows, sp.lp_k = np.asarray(lp_rows, dtype=np.int32), lp_k
+        return sp
+
+    def logprobs_device(self, logits: torch.Tensor, toks: torch.Tensor, sp: "SampleParams") -> torch.Tensor | None:
+        """The step's logprob records, launched right behind its sampler: packed [R, 1 + 2k] (ops.logprob_records)
+        for the rows of ``sp.lp_rows`` over the RAW logits and the ids the sampler just wrote (a grammar-forced id
+        included). A step without such rows launches, copies and allocates nothing."""
+        if sp.lp_rows is None:
+            return None
+        buf = ops.logprob_records(sp.lp_rows.shape[0], sp.lp_k, logits.device)
+        ops.token_logprobs(logits, toks, self._h2d(sp.lp_rows), sp.lp_k, out=ops.unpack_logprob_records(buf, sp.lp_k))
+        return buf
 
     def apply_proc_updates(self, sp: "SampleParams") -> None:
         """The step's logits-processor table writes, stream-ordered before its sampler (every TP rank)."""
@@ -902,9 +928,11 @@ class ModelRunner:
             ev_s = torch.cuda.Event(enable_timing=True)
             ev_s.record()
         toks = self._run(host, sp)
+        lp, self._lp_dev = self._lp_dev, None
         rows = {s.seq_id: i for i, s in enumerate(sample_seqs)}
         if self.device.type != "cuda":
-            return Launched(toks.clone(), None, toks, rows, known=sp.known)
+            return Launched(toks.clone(), None, toks, rows, known=sp.known,
+                            logprobs=None if lp is None else (lp, sp.lp_k, sp.lp_rows))
         n = toks.shape[0]
         # a ring of pinned landing buffers: two steps can be in flight, each D2H needs its own
         ring = self._tok_host
@@ -913,6 +941,17 @@ class ModelRunner:
         self._tok_i = (getattr(self, "_tok_i", 0) + 1) % len(ring)
         out = ring[self._tok_i][:n]
         out.copy_(toks, non_blocking=True)
+        lp_out = None
+        if lp is not None:
+            # the records ride back beside the ids: their own pinned ring with the token ring's slot discipline (two
+            # steps in flight, one more buffer), one copy of the packed block, the same completion event
+            lring, need = self._lp_host, lp.numel()
+            if lring is None or lring[0].numel() < need:
+                lring = self._lp_host = [torch.empty(max(need, 256 * 41), dtype=torch.float32, pin_memory=True)
+                                         for _ in range(len(ring))]
+            host_lp = lring[self._tok_i][:need].view(lp.shape)
+            host_lp.copy_(lp, non_blocking=True)
+            lp_out = (host_lp, sp.lp_k, sp.lp_rows)
         err_idx = None
         car = self._custom_ar()
         if car is not None:  # the error word rides along with the sampled ids (4 bytes, same stream)
@@ -926,7 +965,7 @@ class ModelRunner:
             ev_e = torch.cuda.Event(enable_timing=True)
             ev_e.record()
             self.step_events.append((ev_s, ev_e))
-        return Launched(out, ev, toks, rows, err_idx, sp.known)
+        return Launched(out, ev, toks, rows, err_idx, sp.known, lp_out)
 
     def _custom_ar(self):
         """The IPC collective whose error word rides back with every step's ids: the TP group's custom all-reduce,
@@ -955,6 +994,7 @@ class ModelRunner:
         """Forward + sampling of one step (hipGraph replay for eligible decode steps): the sampled ids on the device,
         also left in ``tok_buf`` for the next step's late decode rows."""
         toks = None
+        self._lp_dev = None
         self.apply_proc_updates(sp)
         if self.graphs is not None and self.graphs.eligible(host, sp):
             toks = self.graphs.run(host, sp)
@@ -963,6 +1003,7 @@ class ModelRunner:
             logits = self.model.forward(inp, self.k_caches, self.v_caches)
             toks = self.sample_device(logits, sp)
             self.tok_buf[:toks.shape[0]].copy_(toks)
+            self._lp_dev = self.logprobs_device(logits, toks, sp)
         return toks
 
     def collect(self, h: "Launched") -> list[int]:
@@ -972,3 +1013,12 @@ class ModelRunner:
             raise CollectiveError("custom all-reduce / all-to-all: a peer did not arrive within 2 s; failing the "
                                   "replica")
         return h.tokens.tolist()
+
+    def collect_logprobs(self, h: "Launched") -> dict:
+        """{sampled row: (logprob, top_ids, top_lps)} of a collected step (call after ``collect``: same event)."""
+        if h.logprobs is None:
+            return {}
+        buf, k, rows = h.logprobs
+        tl, pl, pi = ops.unpack_logprob_records(buf, k)
+        tl, pl, pi = tl.tolist(), pl.tolist(), pi.tolist()
+        return {int(r): (tl[j], pi[j], pl[j]) for j, r in enumerate(rows.tolist())}

@@ -35,8 +35,18 @@ class SamplingParams:
     # picklable tool-call grammar {"tools": [...], "tool_choice": ...}: the engine builds the constraint
     # (engine/constrained.py) on its own side, so it also works through the DP / TP worker pipes
     tool_grammar: dict | None = None
+    # OpenAI ``logprobs`` / ``top_logprobs``: the log-probability of every generated token and of the 0..20 most
+    # likely tokens at its position, over the model's RAW logits (before temperature, penalties and grammar masks;
+    # ops/csrc/logprobs.hip). They ride back in ``StepOutput.logprobs``.
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     def __post_init__(self):
+        if not isinstance(self.top_logprobs, int) or isinstance(self.top_logprobs, bool) \
+                or not 0 <= self.top_logprobs <= 20:
+            raise ValueError("top_logprobs must be an integer in 0..20")
+        if self.top_logprobs > 0 and not self.logprobs:
+            raise ValueError("top_logprobs requires logprobs")
         if self.temperature < 0:
             raise ValueError("temperature must be >= 0")
         if not 0 < self.top_p <= 1:
@@ -123,3 +133,6 @@ class StepOutput:
     num_output_tokens: int = 0
     num_cached_tokens: int = 0
     text: str | None = None
+    # for a request with ``logprobs``: one plain tuple (token_id, logprob, top_ids, top_lps) per id of new_token_ids
+    # (plain tuples: the output stays picklable across the DP / worker pipes); None otherwise
+    logprobs: list | None = None

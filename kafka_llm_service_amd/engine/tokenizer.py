@@ -125,6 +125,40 @@ class KafkaTokenizer:
         return "".join(out)
 
 
+    def token_bytes(self, i: int) -> bytes:
+        """The raw bytes of ONE token (OpenAI's ``logprobs.content[].bytes``): exact for the shipped byte-level BPE —
+        a token is a byte string that need not be valid UTF-8 on its own, which is why ``decode`` of a single id may
+        show replacement characters. Special tokens have no bytes."""
+        j = i - self.offset
+        if self.is_special(i) or j < 0:
+            return b""
+        if j >= self.n_base:
+            return pseudo_word(i).encode("utf-8")
+        piece = self.base.id_to_token(j)
+        if piece is None:
+            return b""
+        if not self.external:
+            table = _unicode_to_byte()
+            try:
+                return bytes(table[c] for c in piece)
+            except KeyError:  # (an added token stored as plain text)
+                pass
+        return self.base.decode([j]).encode("utf-8")
+
+
+@lru_cache(maxsize=1)
+def _unicode_to_byte() -> dict:
+    """Inverse of the byte-level BPE alphabet (GPT-2's bytes_to_unicode): printable bytes stand for themselves, the
+    others are mapped to code points from 256 up."""
+    keep = list(range(ord("!"), ord("~") + 1)) + list(range(0xA1, 0xAD)) + list(range(0xAE, 0x100))
+    table, n = {chr(b): b for b in keep}, 0
+    for b in range(256):
+        if b not in keep:
+            table[chr(256 + n)] = b
+            n += 1
+    return table
+
+
 class IncrementalDetokenizer:
     """Streams text for a growing id list without re-decoding everything: decodes a short window and emits only
     text that is stable (a trailing U+FFFD means an incomplete UTF-8 byte sequence: wait for more tokens)."""

@@ -3,13 +3,14 @@
 Same field names and validation bounds (temperature in [0, 2], max_tokens > 0, top_p in [0, 1], penalties in
 [-2, 2]). ``usage`` is populated from real engine token counts (quirk Q8); ``stream_options.include_usage`` adds a
 final usage chunk like the OpenAI API; ``tool_choice`` / ``tools`` are accepted (the server's own tool set is used,
-``tool_choice`` steers constrained decoding).
+``tool_choice`` steers constrained decoding); ``logprobs`` / ``top_logprobs`` (0..20, only with ``logprobs: true``)
+return per-token log-probabilities of the model's raw logits.
 """
 from __future__ import annotations
 
 from typing import Any, Optional
 
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, model_validator
 
 
 class ChatMessage(BaseModel):
@@ -39,6 +40,15 @@ class ChatCompletionRequest(BaseModel):
     stream_options: Optional[StreamOptions] = None
     tool_choice: Optional[Any] = None
     tools: Optional[list[dict[str, Any]]] = None
+    # per-token log-probabilities of the model's raw logits, and the 0..20 most likely tokens at each position
+    logprobs: Optional[bool] = None
+    top_logprobs: Optional[int] = Field(None, ge=0, le=20)
+
+    @model_validator(mode="after")
+    def _top_logprobs_needs_logprobs(self):
+        if self.top_logprobs is not None and not self.logprobs:
+            raise ValueError("top_logprobs requires logprobs to be true")
+        return self
 
 
 class AgentRunRequest(BaseModel):

@@ -14,6 +14,7 @@ token ids so the agent can store them with the message (thread token cache).
 from __future__ import annotations
 
 import asyncio
+import math
 import os
 import time
 import uuid
@@ -70,6 +71,20 @@ class EngineLLMProvider(LLMProvider):
                     i += 1
             tc = tc[min(i, len(tc) - 1)] if tc else "auto"
         return tc
+
+    def _logprob_entry(self, rec: tuple, n_top: int) -> dict:
+        """One engine record (token_id, logprob, top_ids, top_lps) as an OpenAI ``logprobs.content`` entry: the
+        token's single-id decode (replacement characters where its bytes are no whole UTF-8 sequence), its raw
+        bytes, and the first ``n_top`` alternatives (the engine step may have computed more). JSON has no
+        infinities: a non-finite logprob (a masked-out or NaN logit) is sent as -9999.0, as OpenAI does."""
+        def one(i: int, lp: float) -> dict:
+            return {"token": self.tok.decode([i], False), "logprob": float(lp) if math.isfinite(lp) else -9999.0,
+                    "bytes": list(self.tok.token_bytes(i))}
+
+        tid, lp, ids, lps = rec
+        e = one(tid, lp)
+        e["top_logprobs"] = [one(i, v) for i, v in list(zip(ids, lps))[:n_top] if i >= 0]
+        return e
 
     def render(self, messages: list[Message], tools: list[dict] | None) -> list[int]:
         return self.template.render(messages, tools)
@@ -135,7 +150,14 @@ class EngineLLMProvider(LLMProvider):
                                 tools: list[dict] | None = None, top_p: float | None = None,
                                 frequency_penalty: float | None = None, presence_penalty: float | None = None,
                                 seed: int | None = None, routing_key: str | None = None,
-                                tool_choice: Any = None, **kwargs: Any) -> AsyncGenerator[StreamChunk, None]:
+                                tool_choice: Any = None, logprobs: bool | None = None,
+                                top_logprobs: int | None = None,
+                                **kwargs: Any) -> AsyncGenerator[StreamChunk, None]:
+        """``logprobs`` / ``top_logprobs``: every non-special token the provider consumes yields one OpenAI entry
+        ({token, logprob, bytes, top_logprobs}) over the model's RAW logits; a content chunk carries the entries of
+        the tokens landed since the last chunk that carried any, the final chunk the rest. The stop-string hold-back
+        buffers text, not entries, and a stop-string cut ends the text inside a token: past such a cut the entries'
+        bytes may run a few characters beyond the returned text. Tool-call replies carry none."""
         self.validate_messages(messages)
         if tools is None:
             tools = await self.get_tools()
@@ -150,7 +172,8 @@ class EngineLLMProvider(LLMProvider):
                                 top_p=1.0 if not top_p else float(top_p), max_tokens=max_new,
                                 frequency_penalty=float(frequency_penalty or 0.0),
                                 presence_penalty=float(presence_penalty or 0.0), seed=seed,
-                                ignore_eos=self.ignore_eos,
+                                ignore_eos=self.ignore_eos, logprobs=bool(logprobs),
+                                top_logprobs=int(top_logprobs or 0) if logprobs else 0,
                                 tool_grammar=({"tools": tools, "tool_choice": self._choice(tool_choice, messages)}
                                               if tools and self.constrain_tools else None))
         stops = [s for s in (stop or []) if s]
@@ -163,6 +186,13 @@ class EngineLLMProvider(LLMProvider):
         tool_ids: list[int] = []
         all_ids: list[int] = []
         pending = ""
+        want_lp, n_top = bool(logprobs), int(top_logprobs or 0)
+        entries: list[dict] = []  # logprob entries not yet handed to a chunk
+
+        def take() -> list[dict] | None:
+            nonlocal entries
+            got, entries = entries, []
+            return got or None
         finish = "stop"
         cached = 0
         n_out = 0
@@ -175,6 +205,8 @@ class EngineLLMProvider(LLMProvider):
                 tr.complete("api_engine_first", "api", t_sub, time.perf_counter(), f"thr:{routing_key}",
                             {"prompt_tokens": len(prompt), "cached": out.num_cached_tokens})
             all_ids.extend(ids)
+            if want_lp and out.logprobs:
+                entries.extend(self._logprob_entry(r, n_top) for r in out.logprobs if not self.tok.is_special(r[0]))
             n_out = out.num_output_tokens
             cached = out.num_cached_tokens
             if mode is None and ids:
@@ -189,17 +221,17 @@ class EngineLLMProvider(LLMProvider):
                         cut = min((pending.find(s) for s in stops if s in pending), default=-1)
                         if cut >= 0:
                             if pending[:cut]:
-                                yield StreamChunk(content=pending[:cut], id=cid)
+                                yield StreamChunk(content=pending[:cut], id=cid, logprobs=take())
                             finish, stopped = "stop", True
                             break
                     emit = pending[:len(pending) - hold] if hold else pending
                     if emit:
                         pending = pending[len(emit):]
-                        yield StreamChunk(content=emit, id=cid)
+                        yield StreamChunk(content=emit, id=cid, logprobs=take())
             if out.finished:
                 finish = out.finish_reason or "stop"
         if mode != "tool" and pending and not stopped:
-            yield StreamChunk(content=pending, id=cid)
+            yield StreamChunk(content=pending, id=cid, logprobs=take())
         calls = None
         if mode == "tool":
             body = self.tok.decode(tool_ids)
@@ -217,5 +249,6 @@ class EngineLLMProvider(LLMProvider):
             finish = "stop"
         self._maybe_pin(messages, tools)
         yield StreamChunk(finish_reason="tool_calls" if calls else finish, id=cid, token_ids=all_ids,
+                          logprobs=None if calls else take(),
                           usage=Usage(prompt_tokens=len(prompt), completion_tokens=n_out,
                                       total_tokens=len(prompt) + n_out, cached_tokens=cached))

@@ -62,6 +62,9 @@ class StreamChunk(BaseModel):
     id: Optional[str] = None
     usage: Optional[Usage] = None
     token_ids: Optional[list[int]] = None  # engine token ids of this chunk (for the thread token cache)
+    # OpenAI ``logprobs.content`` entries ({token, logprob, bytes, top_logprobs}) of the tokens landed since the last
+    # chunk that carried any (requests with ``logprobs``; None otherwise)
+    logprobs: Optional[list[dict[str, Any]]] = None
 
     @property
     def delta(self) -> str:

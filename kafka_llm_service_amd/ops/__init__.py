@@ -6,6 +6,7 @@ Kernel inventory:
   rope_kv_write (RoPE + paged KV write)         csrc/rope_kv.hip
   attn_decode / attn_prefill / attn_merge       csrc/attention.hip   (MFMA 32x32x16 bf16, paged, split-K, cascade)
   sample (greedy / temperature / top-k / top-p) csrc/sampling.hip
+  token_logprobs (logprob + top-k alternatives) csrc/logprobs.hip
   moe_* / grouped GEMM                          csrc/moe.hip
   custom all-reduce                             csrc/allreduce.hip
 """
@@ -95,7 +96,7 @@ _TICKETS: dict = {}
 def _tickets(dev: torch.device, n: int, pool: str = "decode") -> torch.Tensor:
     """Zeroed int32 counters for a kernel's ticket merge (re-armed by the kernel itself, so one buffer per device and
     pool serves every layer and step; allocated once, large, so graph capture never allocates). Pool "decode":
-    decode attention, per row x kv head."""
+    decode attention, per row x kv head; pool "logprobs": ``token_logprobs``'s tickets and split partials."""
     t = _TICKETS.get((dev, pool))
     if t is None or t.numel() < n:
         t = _TICKETS[(dev, pool)] = torch.zeros(max(n, 1 << 16), dtype=torch.int32, device=dev)
@@ -215,6 +216,69 @@ def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=No
     else:
         ref.sample(logits, temperature, top_p, top_k, seeds, step, out, proc, mask_tab, counts)
     return out
+
+
+LOGPROBS_MAX_K = 20      # OpenAI's top_logprobs bound; the kernel's register / LDS budget (csrc/logprobs.hip)
+_LP_TICKETS = 8192       # LP_MAX_ROWS of csrc/logprobs.hip: ticket counters in front of the partials
+_LP_PART = 2 + 2 * LOGPROBS_MAX_K
+
+
+def logprob_records(R: int, k: int, device) -> torch.Tensor:
+    """A packed record buffer for ``token_logprobs``: [R, 1 + 2k] 4-byte words, row = logprob | k top logprobs | k top
+    ids (int32 bits), so a step's records are ONE device->host copy. ``unpack_logprob_records`` gives the views."""
+    return torch.empty(R, 1 + 2 * k, dtype=torch.float32, device=device)
+
+
+def unpack_logprob_records(buf: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(tok_lp [R], top_lp [R, k], top_id [R, k] int32): three views of a packed record buffer [R, 1 + 2k] float32
+    (on any device, or its pinned host copy) — the ``out`` of ``token_logprobs``."""
+    return buf[:, 0], buf[:, 1:1 + k], buf.view(torch.int32)[:, 1 + k:1 + 2 * k]
+
+
+def logprobs_split(V: int) -> int:
+    """Workgroups per row: 8 like the sampler, more when a slice would not fit the kernel's registers (16,384
+    entries per workgroup); one below 16,384 entries."""
+    if V < 16384:
+        return 1
+    return min(64, max(_SAMPLE_SPLIT if _SAMPLE_SPLIT > 1 else 8, -(-V // 16384)))
+
+
+def token_logprobs(logits, tokens, rows=None, k: int = 0, out=None):
+    """Log-probabilities of the RAW logits (before temperature, penalties and grammar masks): for every scored row r
+    (``rows``: row ids of ``logits``, default all) -> (tok_lp [R] f32 = log softmax at ``tokens[row]``, top_lp [R, k]
+    f32 and top_id [R, k] i32 = the k (0..20) most likely tokens in the order (value descending, index ascending)).
+    ``tokens`` is indexed by LOGITS row (the sampler's output as it stands). ``out`` = three such tensors sharing a row
+    stride, e.g. ``unpack_logprob_records(logprob_records(R, k, device), k)`` (one packed buffer). GPU tensors run csrc/logprobs.hip (one streaming read of
+    each row, nothing allocated per call with ``out`` and device ``rows``: graph-safe); CPU tensors the fp32
+    reference."""
+    k = int(k)
+    if not 0 <= k <= LOGPROBS_MAX_K:
+        raise ValueError(f"k must be in 0..{LOGPROBS_MAX_K}")
+    B, V = logits.shape
+    dev = logits.device
+    if rows is not None and not isinstance(rows, torch.Tensor):
+        ra = np.asarray(rows, dtype=np.int64).reshape(-1)
+        if ra.size and (ra.min() < 0 or ra.max() >= B):
+            raise ValueError(f"rows must lie in [0, {B})")
+        rows = torch.from_numpy(ra.astype(np.int32)).to(dev)
+    R = B if rows is None else int(rows.numel())
+    if out is None:
+        out = unpack_logprob_records(logprob_records(R, k, dev), k)
+    tok_lp, top_lp, top_id = out
+    if _gpu(logits):
+        if rows is not None and rows.dtype != torch.int32:
+            rows = rows.to(torch.int32)
+        nsplit = logprobs_split(V)
+        # a pool of its own (tickets | partials), sized once for 1,024 rows x 8 splits so no call allocates
+        ws = _tickets(dev, _LP_TICKETS + max(R * nsplit, 1024 * 8) * _LP_PART, pool="logprobs") if nsplit > 1 else None
+        ext().token_logprobs(logits, tokens, rows, k, tok_lp, top_lp, top_id, ws, nsplit)
+    else:
+        a, b, c = ref.token_logprobs(logits, tokens, rows, k)
+        tok_lp[:R].copy_(a)
+        if k:
+            top_lp[:R, :k].copy_(b)
+            top_id[:R, :k].copy_(c)
+    return tok_lp, top_lp, top_id
 
 
 def tile_weight(w: torch.Tensor, glu: bool = False) -> torch.Tensor:

@@ -375,6 +375,53 @@ static void sample(at::Tensor logits, c10::optional<at::Tensor> temperature, c10
                                  cp, cld, cur_stream()));
 }
 
+// Per-token logprobs (logprobs.hip). rows: int32 [R] or none (rows 0..R-1); tok_lp f32 [R], top_lp f32 [R, K] and
+// top_id int32 [R, K] share one row stride (views of one packed record buffer). The row ids are trusted (the Python
+// op range-checks a host list before uploading it); everything the kernel indexes by them is sized for every row.
+static void token_logprobs(at::Tensor logits, at::Tensor tokens, c10::optional<at::Tensor> rows, int64_t K,
+                           at::Tensor tok_lp, at::Tensor top_lp, at::Tensor top_id, c10::optional<at::Tensor> ws,
+                           int64_t nsplit) {
+  CHECK_CUDA(logits); CHECK_CUDA(tokens); CHECK_CUDA(tok_lp); CHECK_CUDA(top_lp); CHECK_CUDA(top_id);
+  CHECK_DT(tokens, at::kLong); CHECK_DT(tok_lp, at::kFloat); CHECK_DT(top_lp, at::kFloat); CHECK_DT(top_id, at::kInt);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [B, V]");
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(is_bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or fp32");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V < (1ll << 31) - 8, "token_logprobs: bad vocabulary size");
+  TORCH_CHECK(logits.stride(0) >= V, "token_logprobs: overlapping logits rows");
+  TORCH_CHECK(K >= 0 && K <= 20, "token_logprobs: k must be in 0..20");
+  int64_t R = B;
+  const int* rp = nullptr;
+  if (rows.has_value()) {
+    TORCH_CHECK(rows->is_cuda() && rows->scalar_type() == at::kInt && rows->is_contiguous() && rows->dim() == 1,
+                "token_logprobs: rows must be int32 [R] on the GPU");
+    R = rows->numel();
+    rp = rows->data_ptr<int>();
+  }
+  TORCH_CHECK(R <= 8192, "token_logprobs: at most 8192 rows per call");
+  TORCH_CHECK(tokens.is_contiguous() && tokens.numel() >= B, "token_logprobs: tokens must be int64 [>= rows of logits]");
+  TORCH_CHECK(tok_lp.dim() == 1 && tok_lp.size(0) >= R, "token_logprobs: tok_lp must be [R]");
+  const int64_t ld = tok_lp.stride(0);
+  TORCH_CHECK(ld >= 1, "token_logprobs: bad record stride");
+  if (K > 0) {
+    for (const at::Tensor* t : {&top_lp, &top_id})
+      TORCH_CHECK(t->dim() == 2 && t->size(0) >= R && t->size(1) >= K && t->stride(1) == 1 &&
+                      (t->stride(0) == ld || R <= 1), "token_logprobs: top_lp / top_id must be [R, >= k] with "
+                  "tok_lp's row stride");
+  }
+  int* wp = nullptr;
+  if (ws.has_value() && nsplit > 1 && V >= 16384) {  // split rows: tickets [8192] | partials [R][nsplit][42]
+    TORCH_CHECK(ws->is_cuda() && ws->scalar_type() == at::kInt && ws->is_contiguous() && nsplit <= 64 &&
+                    ws->numel() >= 8192 + R * nsplit * 42,
+                "token_logprobs: workspace must be int32 [>= 8192 + 42 * R * nsplit]");
+    wp = ws->data_ptr<int>();
+  }
+  CHECK_HIP(kafka_launch_token_logprobs(logits.data_ptr(), is_bf16, logits.stride(0), (int)V, rp, (int)R,
+                                         tokens.data_ptr<int64_t>(), (int)K, tok_lp.data_ptr<float>(),
+                                         top_lp.data_ptr<float>(), top_id.data_ptr<int>(), ld, wp,
+                                         wp ? (int)nsplit : 1, cur_stream()));
+}
+
 // (mt, kc, splits) of the weight-streaming decode GEMM for a shape, or (0, 0, 0) if unsupported
 static std::vector<int64_t> wstream_plan(int64_t M, int64_t N, int64_t K, int64_t max_splits) {
   int mt = 0, kc = 0, s = 0;
@@ -902,6 +949,8 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"), py::arg("top_p"), py::arg("top_k"),
         py::arg("seeds"), py::arg("step"), py::arg("out"), py::arg("ws") = py::none(), py::arg("nsplit") = 1,
         py::arg("proc") = py::none(), py::arg("mask_tab") = py::none(), py::arg("counts") = py::none());
+  m.def("token_logprobs", &token_logprobs, py::arg("logits"), py::arg("tokens"), py::arg("rows"), py::arg("k"),
+        py::arg("tok_lp"), py::arg("top_lp"), py::arg("top_id"), py::arg("ws") = py::none(), py::arg("nsplit") = 1);
   m.def("wstream_plan", &wstream_plan);
   m.def("wstream_gemm", &wstream_gemm, py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"),
         py::arg("max_splits"), py::arg("nt"), py::arg("glu"));

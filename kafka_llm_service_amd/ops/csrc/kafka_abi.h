@@ -140,6 +140,17 @@ hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int64_t stride,
                                int64_t* out_tokens, int* ws, int nsplit, const int* proc, const uint32_t* mask_tab,
                                int64_t mask_ld, int* counts, int64_t cnt_ld, hipStream_t st);
 
+// ---- logprobs.hip
+// Log softmax of the RAW logits (no temperature / penalties / mask) at each scored row's sampled token, and the row's
+// K (0..20) largest entries in the order (value descending, index ascending). rows (optional): int32 [R] rows of
+// `logits` (nullptr: rows 0..R-1; the kernel trusts them); tokens: int64 [>= max row + 1], the sampled id of each
+// LOGITS row. Record r lands at tok_lp[r * ld], top_lp[r * ld + j], top_id[r * ld + j] (three views of one packed
+// buffer). ws (optional): int32 workspace of >= 8192 + R * nsplit * 42 entries whose first 8192 are zero (tickets,
+// re-armed by the kernel); without it, or for V < 16384, every row is one workgroup. R <= 8192, nsplit <= 64.
+hipError_t kafka_launch_token_logprobs(const void* logits, bool is_bf16, int64_t stride, int V, const int* rows, int R,
+                                       const int64_t* tokens, int K, float* tok_lp, float* top_lp, int* top_id,
+                                       int64_t ld, int* ws, int nsplit, hipStream_t st);
+
 // ---- wstream_gemm.hip
 // Host plan: row tiles MT, K chunk KC and split count S for a shape; returns 0 if supported (mirrored by
 // ops.stream_plan). max_splits caps S (1 forces a direct bf16 output).

@@ -380,6 +380,34 @@ def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=No
     return res
 
 
+def token_logprobs(logits, tokens, rows=None, k: int = 0):
+    """fp32 reference of csrc/logprobs.hip: for each scored row r (``rows``, default every row) of the RAW logits,
+    (log softmax at tokens[row], the k largest log-probabilities, their ids) as (tok_lp [R] f32, top_lp [R, k] f32,
+    top_id [R, k] i32). The k largest are the first k of a STABLE descending sort — (value descending, index
+    ascending), the kernel's tie rule; ``torch.topk`` leaves the order of ties unspecified. Slots past the row's
+    length hold -inf / -1; a NaN entry counts as -inf."""
+    x = logits.float()
+    x = torch.where(x != x, torch.full_like(x, float("-inf")), x)
+    V = x.shape[1]
+    if rows is None:
+        idx = torch.arange(x.shape[0], device=x.device)
+    else:
+        idx = torch.as_tensor(rows, device=x.device).long().reshape(-1)
+    xs = x[idx]
+    R = xs.shape[0]
+    lse = torch.logsumexp(xs, -1)
+    tok = torch.as_tensor(tokens, device=x.device).long()[idx]
+    tok_lp = xs.gather(1, tok[:, None])[:, 0] - lse
+    top_lp = torch.full((R, k), float("-inf"), dtype=torch.float32, device=x.device)
+    top_id = torch.full((R, k), -1, dtype=torch.int32, device=x.device)
+    n = min(k, V)
+    if n and R:
+        vals, ids = torch.sort(xs, dim=-1, descending=True, stable=True)
+        top_lp[:, :n] = vals[:, :n] - lse[:, None]
+        top_id[:, :n] = ids[:, :n].to(torch.int32)
+    return tok_lp, top_lp, top_id
+
+
 def rope_cos_sin(max_pos: int, head_dim: int, theta: float, scaling: dict | None = None,
                  device="cpu") -> torch.Tensor:
     """[max_pos, D] fp32 table: cos of the D/2 frequencies then sin (rotate-half / NeoX convention).

@@ -107,6 +107,9 @@ def _sampling_kwargs(req: ChatCompletionRequest) -> dict[str, Any]:
         v = getattr(req, k)
         if v is not None:
             kw[k] = v
+    if req.logprobs:  # (a request that does not ask passes nothing new down)
+        kw["logprobs"] = True
+        kw["top_logprobs"] = req.top_logprobs or 0
     return kw
 
 
@@ -244,7 +247,19 @@ def create_app(config: ServerConfig | None = None, state: ServerState | None = N
                     continue
                 delta = ch[0].get("delta") or {}
                 text = delta.get("content")
-                if text:
+                lp = ch[0].get("logprobs") if req.logprobs else None
+                if lp is not None:
+                    # a request with ``logprobs``: the general formatter, the entries beside ``delta`` (a frame
+                    # whose tokens added no text yet still carries their entries, with empty content)
+                    if text and first:
+                        t_first = time.perf_counter()
+                        M.TTFT.observe(t_first - t0)
+                        first = False
+                    yield _sse({"id": cid, "object": "chat.completion.chunk", "created": created, "model": model,
+                                "choices": [{"index": 0, "delta": {"role": None, "content": text or "",
+                                                                   "tool_calls": None},
+                                             "logprobs": lp, "finish_reason": None}]})
+                elif text:
                     if first:
                         t_first = time.perf_counter()
                         M.TTFT.observe(t_first - t0)
@@ -276,18 +291,29 @@ def create_app(config: ServerConfig | None = None, state: ServerState | None = N
 
     async def completion_json(messages, req: ChatCompletionRequest, thread_id: str | None) -> ChatCompletionResponse:
         content, usage, finish = "", {}, "stop"
+        entries: list = []  # logprob entries of the run, in emission order (requests with ``logprobs``)
         async for ev in st.run_agent(messages, req.model, req.temperature, req.max_tokens, thread_id,
                                      **_sampling_kwargs(req)):
+            if req.logprobs and ev.get("choices"):
+                lp = ev["choices"][0].get("logprobs")
+                if lp:
+                    entries += lp.get("content") or []
             if ev.get("type") == "agent_done":
                 content = ev.get("final_content") or ev.get("summary") or content
                 usage = ev.get("usage") or usage
                 if ev.get("reason") == "max_iterations":
                     finish = "length"
-        return ChatCompletionResponse(
+        resp = ChatCompletionResponse(
             id=f"chatcmpl-{uuid.uuid4().hex[:24]}", created=int(time.time()), model=req.model,
             choices=[Choice(message=MessageContent(content=content), finish_reason=finish)],
             usage=Usage(prompt_tokens=usage.get("prompt_tokens", 0), completion_tokens=usage.get("completion_tokens", 0),
                         total_tokens=usage.get("total_tokens", 0)))
+        if not req.logprobs:
+            return resp  # (the body of a request that does not ask has no ``logprobs`` key, as before)
+        body = resp.model_dump()
+        # null when the provider computed none (stub / remote providers, tool-call-only runs)
+        body["choices"][0]["logprobs"] = {"content": entries, "refusal": None} if entries else None
+        return JSONResponse(body)
 
     @app.post("/v1/threads/{thread_id}/chat/completions")
     async def thread_chat(thread_id: str, req: ChatCompletionRequest, request: Request):
