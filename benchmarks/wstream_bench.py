@@ -5,7 +5,8 @@ hipBLASLt (torch F.linear) on the per-layer projection shapes of Llama-3-8B (TP=
 The streaming kernel's time includes what its consumer pays to combine split-K slabs only in the "+reduce" column
 (the engine never runs that reduce: rope_kv / SwiGLU / add+RMSNorm sum the slabs while loading). Each case is a fresh
 weight buffer larger than the Infinity Cache rotation (cold HBM reads, like one layer of a real step).
-One JSON line per (shape, M)."""
+``--weight-dtype fp8`` streams e4m3 tiles (ops.tile_weight_fp8; hipBLASLt then runs on the dequantised bf16 weight,
+and TB/s counts the fp8 bytes actually streamed). One JSON line per (shape, M)."""
 from __future__ import annotations
 
 import argparse
@@ -46,27 +47,37 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--M", default="1,16,64,128")
     ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"])
     args = ap.parse_args()
+    fp8 = args.weight_dtype == "fp8"
     dev = torch.device("cuda:0")
     for name in args.shapes.split(","):
         N, K = SHAPES[name]
         nbytes = N * K * 2
         copies = max(2, (600 << 20) // nbytes + 1)  # > 512 MB of weights in rotation: beyond the 256 MB MALL
         ws = [(torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16) for _ in range(copies)]
-        wts = [ops.tile_weight(w) for w in ws]
+        if fp8:  # (tiles, scales); ws become the dequantised weights hipBLASLt and the error reference read
+            wts = [ops.tile_weight_fp8(w) for w in ws]
+            ws = [ops.untile_weight_fp8(wt, st) for wt, st in wts]
+            stream = lambda x, t, **kw: ops.linear_stream(x, t[0], scale=t[1], **kw)
+            sbytes = N * K + 4 * N
+        else:
+            wts = [ops.tile_weight(w) for w in ws]
+            stream = lambda x, t, **kw: ops.linear_stream(x, t, **kw)
+            sbytes = nbytes
         for M in [int(m) for m in args.M.split(",")]:
             x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
             plan = ops.stream_plan(M, N, K)
             t_blas = timeit([lambda w=w: F.linear(x, w) for w in ws])
-            row = {"shape": name, "M": M, "N": N, "K": K, "hipblaslt_us": round(t_blas, 1),
+            row = {"shape": name, "weight_dtype": args.weight_dtype, "M": M, "N": N, "K": K, "hipblaslt_us": round(t_blas, 1),
                    "hipblaslt_TB/s": round(nbytes / t_blas / 1e6, 2)}
             if plan is not None:
-                t_ws = timeit([lambda wt=wt: ops.linear_stream(x, wt) for wt in wts])
-                t_ws1 = timeit([lambda wt=wt: ops.linear_stream(x, wt, max_splits=1) for wt in wts])
-                t_red = timeit([lambda wt=wt: ops.slab_reduce(ops.linear_stream(x, wt)) for wt in wts])
+                t_ws = timeit([lambda wt=wt: stream(x, wt) for wt in wts])
+                t_ws1 = timeit([lambda wt=wt: stream(x, wt, max_splits=1) for wt in wts])
+                t_red = timeit([lambda wt=wt: ops.slab_reduce(stream(x, wt)) for wt in wts])
                 ref = x.float() @ ws[0].float().t()
-                err = (ops.slab_reduce(ops.linear_stream(x, wts[0])).float() - ref).abs().max().item()
-                row.update({"splits": plan[2], "wstream_us": round(t_ws, 1), "wstream_TB/s": round(nbytes / t_ws / 1e6, 2),
+                err = (ops.slab_reduce(stream(x, wts[0])).float() - ref).abs().max().item()
+                row.update({"splits": plan[2], "wstream_us": round(t_ws, 1), "wstream_TB/s": round(sbytes / t_ws / 1e6, 2),
                             "wstream_s1_us": round(t_ws1, 1), "wstream+reduce_us": round(t_red, 1),
                             "speedup": round(t_blas / t_ws, 2), "max_err": round(err, 4)})
             print(json.dumps(row), flush=True)

@@ -65,6 +65,11 @@ class EngineConfig:
     # decode GEMMs: "stream" = weight-streaming MFMA kernel on wave-tiled weight copies (csrc/wstream_gemm.hip),
     # "blas" = hipBLASLt only; "auto" = stream on GPU (env KAFKA_DECODE_GEMM overrides)
     decode_gemm: str = "auto"           # auto | stream | stream_only (tiled weights only) | blas
+    # dense projections + lm_head: "bf16", or "fp8" = e4m3 wave tiles with one power-of-two scale per output row
+    # (half the bytes of every decode GEMM and of the tiled copy; the row-major weights become the dequantised
+    # values, so every path and the oracle run the same quantised model; models/llama.py enable_stream_weights).
+    # Needs the streaming decode GEMM (auto resolves to stream); env KAFKA_WEIGHT_DTYPE overrides
+    weight_dtype: str = "bf16"          # bf16 | fp8
     async_scheduling: bool = True       # plan step n+1 on the host while step n runs on the GPU
     # Mixtral data-parallel attention (engine/dp_attention.py): this rank serves its own sequences with whole
     # attention weights; experts are sharded over parallel.state's EP group and every step runs in lockstep with
@@ -132,19 +137,29 @@ class LLMEngine:
                                                                                  mc.max_position_embeddings),
                                           dp_attention=dpa)
         mode = os.environ.get("KAFKA_DECODE_GEMM", cfg.decode_gemm)
+        wdt = os.environ.get("KAFKA_WEIGHT_DTYPE") or cfg.weight_dtype
+        if wdt not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype must be bf16 or fp8, not {wdt!r}")
+        if wdt == "fp8" and mode == "blas":
+            raise ValueError("weight_dtype='fp8' needs the weight-streaming decode GEMM (decode_gemm auto | stream | "
+                             "stream_only), not 'blas'")
         if mode == "auto":
-            mode = "stream" if self.device.type == "cuda" else "blas"
+            # fp8 weights live in the streaming kernel's tiles on any device (the CPU runs the reference path)
+            mode = "stream" if self.device.type == "cuda" or wdt == "fp8" else "blas"
+        if self.model.stream and self.model.weight_dtype != wdt:
+            raise ValueError(f"the model's streamed weights are {self.model.weight_dtype}, the engine asks for {wdt}")
+        cfg.weight_dtype = wdt
         if mode == "stream" and not self.model.stream:
-            need = self.model.stream_weight_bytes()
+            need = self.model.stream_weight_bytes(wdt)
             free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else need * 4
             if need <= 0.5 * free:
-                self.model.enable_stream_weights()  # before the KV pool is sized from the free memory
+                self.model.enable_stream_weights(weight_dtype=wdt)  # before the KV pool is sized from the free memory
             else:  # e.g. Llama-3-70B on one GPU: a second copy of 140 GB would starve the KV pool
                 log.warning("wave-tiled weight copy (%.1f GB) does not fit next to the KV pool (%.1f GB free): "
                             "keeping tiled weights only (prefill untiles per projection)", need / 1e9, free / 1e9)
-                self.model.enable_stream_weights(tiled_only=True)
+                self.model.enable_stream_weights(tiled_only=True, weight_dtype=wdt)
         elif mode == "stream_only" and not self.model.stream:
-            self.model.enable_stream_weights(tiled_only=True)
+            self.model.enable_stream_weights(tiled_only=True, weight_dtype=wdt)
         if self.model.tiled_only and cfg.max_num_seqs > self.model.stream_max_m:
             # decode batches beyond the streaming kernel's rows would untile every projection every step
             log.info("tiled-only weights: max_num_seqs %d -> %d", cfg.max_num_seqs, self.model.stream_max_m)
@@ -209,8 +224,9 @@ class LLMEngine:
         self._coll_mark = (0, 0)  # (collective calls, steps) at the last perf_stats() read
         self._n_added = 0
         self.stop_checker_factory = None  # set by the frontend: (request params) -> incremental stop-string checker
-        log.info("engine ready: %s tp=%d kv pages=%d (%s, %.1f GB) load %.1fs", mc.name, cfg.tp, nb, cfg.kv_dtype,
-                 nb * page_bytes / 1e9, self.load_s)
+        log.info("engine ready: %s tp=%d weights %s (%.1f GB) kv pages=%d (%s, %.1f GB) load %.1fs", mc.name, cfg.tp,
+                 self.model.weight_dtype, self.model.weight_bytes() / 1e9, nb, cfg.kv_dtype, nb * page_bytes / 1e9,
+                 self.load_s)
 
     # ------------------------------------------------------------------------------------------------------------
 

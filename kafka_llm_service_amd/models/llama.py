@@ -78,7 +78,8 @@ class StepInput:
 
 class LayerWeights:
     __slots__ = ("input_norm", "post_norm", "qkv", "o", "gate_up", "down", "router", "w13", "w2", "expert_ids",
-                 "qkv_t", "o_t", "gate_up_t", "down_t", "glu", "w13_t", "w2_t")
+                 "qkv_t", "o_t", "gate_up_t", "down_t", "glu", "w13_t", "w2_t",
+                 "qkv_s", "o_s", "gate_up_s", "down_s")  # _s: fp32 row scales of fp8 tiles (weight_dtype="fp8")
     STREAMED = ("qkv", "o", "gate_up", "down")  # projections with a wave-tiled copy for the decode GEMM
 
     def __init__(self):
@@ -116,6 +117,8 @@ class TransformerLM:
         self.scale = self.D ** -0.5
         self.moe = None
         self.lm_head_t = None
+        self.lm_head_s = None  # row scales of fp8 lm_head tiles
+        self.weight_dtype = "bf16"  # of the streamed projections and the lm_head (enable_stream_weights)
         self.stream = False  # decode GEMMs on the weight-streaming kernel (enable_stream_weights)
         self.tiled_only = False  # row-major dense weights dropped (enable_stream_weights(tiled_only=True))
         self.stream_max_m = ops.STREAM_MAX_M  # rows up to which a step's projections stream
@@ -138,23 +141,29 @@ class TransformerLM:
             self.moe.serve_idle(lw, self.cfg.hidden_size, self.dtype, self.device)
 
     # ------------------------------------------------------------------------------------------------------------
-    def stream_weight_bytes(self) -> int:
-        """Bytes enable_stream_weights would add (the wave-tiled copies; 0 in tiled-only mode)."""
+    def stream_weight_bytes(self, weight_dtype: str = "bf16") -> int:
+        """Bytes enable_stream_weights would add (the wave-tiled copies; 0 in tiled-only mode). ``"fp8"``: one byte
+        per element plus a 4-byte scale per row for the dense projections and the lm_head; experts stay bf16."""
+        def tiled(w):
+            if weight_dtype == "fp8":
+                return w.numel() + 4 * w.shape[0]
+            return w.numel() * w.element_size()
+
         n = 0
         for lw in self.layers:
             for name in LayerWeights.STREAMED:
                 w = getattr(lw, name)
                 if w is not None and ops.stream_plan(1, w.shape[0], w.shape[1]) is not None:
-                    n += w.numel() * w.element_size()
+                    n += tiled(w)
             for name in ("w13", "w2"):
                 w = getattr(lw, name)
                 if w is not None and ops.stream_moe_supported(w.shape[1], w.shape[2]):
                     n += w.numel() * w.element_size()
         if self.lm_head is not None and ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
-            n += self.lm_head.numel() * self.lm_head.element_size()
+            n += tiled(self.lm_head)
         return n
 
-    def enable_stream_weights(self, tiled_only: bool = False) -> int:
+    def enable_stream_weights(self, tiled_only: bool = False, weight_dtype: str = "bf16") -> int:
         """Keep a wave-tiled copy of every dense projection and of the lm_head (ops.tile_weight) so decode-sized
         steps (T <= ops.STREAM_MAX_M) run the weight-streaming MFMA GEMM (csrc/wstream_gemm.hip) instead of
         hipBLASLt; prefill-sized steps keep the row-major weights. Costs one more copy of those weights (16 GB for
@@ -163,21 +172,44 @@ class TransformerLM:
         ``tiled_only``: when the second copy does not fit (Llama-3-70B on one GPU), the row-major dense projections
         and the lm_head are dropped after tiling (no extra memory) and prefill-sized steps untile one weight at a
         time into a transient buffer for hipBLASLt (``_dense``); MoE experts keep their row-major layout only
-        (grouped GEMM at every step size — a tiled expert copy would be the 90 GB second copy this mode avoids)."""
+        (grouped GEMM at every step size — a tiled expert copy would be the 90 GB second copy this mode avoids).
+
+        ``weight_dtype="fp8"``: the tiles are e4m3 with one power-of-two scale per output row
+        (ops.tile_weight_fp8: ``<name>_t`` uint8, ``<name>_s`` fp32) — half the bytes per decode step and half the
+        tiled copy. The model then IS the quantised model at every step size: the row-major bf16 tensor of each
+        quantised projection is replaced by its dequantised values (exact in bf16), so hipBLASLt prefill, the streamed
+        decode steps and the dense oracle compute with the same weights. Embedding, norms, router and MoE experts stay
+        bf16; the skinny GEMM and the fused decode layer do not take fp8 tiles (hipBLASLt / the unfused layer run)."""
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype must be bf16 or fp8, not {weight_dtype!r}")
+        fp8 = weight_dtype == "fp8"
         added = 0
+
+        def tile(w, glu=False):
+            """(tiles, scales or None, row-major tensor to keep, bytes of the tiled copy)"""
+            if not fp8:
+                wt = ops.tile_weight(w, glu=glu)
+                return wt, None, w, wt.numel() * wt.element_size()
+            wt, st = ops.tile_weight_fp8(w, glu=glu)
+            keep = None if tiled_only else ops.untile_weight_fp8(wt, st, glu=glu)
+            return wt, st, keep, wt.numel() + st.numel() * st.element_size()
+
         for lw in self.layers:
             for name in LayerWeights.STREAMED:
                 w = getattr(lw, name)
                 if w is not None and ops.stream_plan(1, w.shape[0], w.shape[1]) is not None:
                     glu = name == "gate_up" and w.shape[0] % 64 == 0
-                    setattr(lw, name + "_t", ops.tile_weight(w, glu=glu))
+                    wt, st, keep, nbytes = tile(w, glu)
+                    setattr(lw, name + "_t", wt)
+                    setattr(lw, name + "_s", st)
                     if name == "gate_up":
                         lw.glu = glu
+                    del w
                     if tiled_only:
                         setattr(lw, name, None)
-                        del w
                     else:
-                        added += w.numel() * w.element_size()
+                        setattr(lw, name, keep)
+                        added += nbytes
             if not tiled_only and lw.w13 is not None and \
                     ops.stream_moe_supported(lw.w13.shape[1], lw.w13.shape[2]) and \
                     ops.stream_moe_supported(lw.w2.shape[1], lw.w2.shape[2]):
@@ -185,13 +217,16 @@ class TransformerLM:
                 lw.w2_t = ops.tile_experts(lw.w2)
                 added += (lw.w13.numel() + lw.w2.numel()) * lw.w13.element_size()
         if ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
-            self.lm_head_t = ops.tile_weight(self.lm_head)
+            # (an lm_head that aliases the embedding gets a tensor of its own here: the embedding keeps its values)
+            self.lm_head_t, self.lm_head_s, keep, nbytes = tile(self.lm_head)
             if tiled_only:
                 self.lm_head = None
             else:
-                added += self.lm_head_t.numel() * self.lm_head_t.element_size()
+                self.lm_head = keep
+                added += nbytes
         self.stream = True
         self.tiled_only = tiled_only
+        self.weight_dtype = weight_dtype
         # tiled-only: any larger step would untile every projection for hipBLASLt, so the streaming kernel takes
         # steps up to its 256-row limit (two row tiles beyond 128) — slower than hipBLASLt there, far cheaper than
         # untiling
@@ -201,21 +236,35 @@ class TransformerLM:
         return added
 
     def _linear(self, x: torch.Tensor, w: torch.Tensor, wt: torch.Tensor | None, max_splits: int = 8,
-                kind: str = ""):
+                kind: str = "", st: torch.Tensor | None = None):
         """x @ w^T: the weight-streaming kernel for decode-sized x (bf16 or a split-K slab out), the skinny MFMA GEMM
-        for 129..256 rows of the projections in SKINNY, else hipBLASLt."""
+        for 129..256 rows of the projections in SKINNY (bf16 tiles only), else hipBLASLt. ``st``: fp8 tiles' scales."""
         M = x.shape[0]
         if self.stream and wt is not None:
             if 0 < M <= self.stream_max_m:
-                return ops.linear_stream(x, wt, max_splits)
-            if kind in SKINNY and ops.skinny_plan(M, wt.shape[0] * 32, x.shape[1], max_splits):
+                return ops.linear_stream(x, wt, max_splits, scale=st)
+            if kind in SKINNY and not ops.is_fp8_weight(wt) and \
+                    ops.skinny_plan(M, wt.shape[0] * 32, x.shape[1], max_splits):
                 return ops.linear_skinny(x, wt, max_splits)
-        return F.linear(x, self._dense(w, wt))
+        return F.linear(x, self._dense(w, wt, st=st))
 
     @staticmethod
-    def _dense(w: torch.Tensor | None, wt: torch.Tensor | None, glu: bool = False) -> torch.Tensor:
-        """The row-major weight for hipBLASLt: the stored one, or (tiled-only mode) a transient untiled copy."""
-        return w if w is not None else ops.untile_weight(wt, glu=glu)
+    def _dense(w: torch.Tensor | None, wt: torch.Tensor | None, glu: bool = False,
+               st: torch.Tensor | None = None) -> torch.Tensor:
+        """The row-major weight for hipBLASLt: the stored one, or (tiled-only mode) a transient untiled copy —
+        dequantised for fp8 tiles (``st`` their scales)."""
+        if w is not None:
+            return w
+        return ops.untile_weight_fp8(wt, st, glu=glu) if ops.is_fp8_weight(wt) else ops.untile_weight(wt, glu=glu)
+
+    def dense_weight(self, lw: LayerWeights | None, name: str) -> torch.Tensor:
+        """Row-major [N, K] weight of a streamed projection of ``lw`` (or of "lm_head" with lw = None) in either
+        mode: the stored tensor, or the untiled (fp8: dequantised) tiles of a tiled-only model — what export and the
+        dense oracle read."""
+        if lw is None:
+            return self._dense(self.lm_head, self.lm_head_t, st=self.lm_head_s)
+        return self._dense(getattr(lw, name), getattr(lw, name + "_t"), bool(lw.glu) and name == "gate_up",
+                           getattr(lw, name + "_s"))
 
     def forward(self, inp: StepInput, k_caches: list[torch.Tensor], v_caches: list[torch.Tensor],
                 gather: bool = True) -> torch.Tensor:
@@ -250,17 +299,18 @@ class TransformerLM:
                 pstate.tp_all_reduce_add_rmsnorm(delta, residual, lw.input_norm, eps, out=x)
             else:
                 ops.fused_add_rmsnorm(delta, residual, lw.input_norm, eps, out=x)
-            qkv = self._linear(x, lw.qkv, lw.qkv_t, kind="qkv")
+            qkv = self._linear(x, lw.qkv, lw.qkv_t, kind="qkv", st=lw.qkv_s)
             ops.rope_kv_write(qkv, inp.positions, self.cos_sin, q, k_caches[i], v_caches[i], inp.slot_mapping,
                               self.hq, self.hkv)
             paged_attention(q, k_caches[i], v_caches[i], inp.attn, attn_out)
             if tp and self._can_overlap(T, lw.o_t):
                 self._overlapped_seam(attn_out.view(T, -1), lw.o_t, residual, lw.post_norm, eps, x)
             elif tp and self._can_pipe(T, lw.o, lw.o_t):
-                o = pstate.tp_linear_all_reduce(attn_out.view(T, -1), self._dense(lw.o, lw.o_t), self._pipe_chunks(T))
+                o = pstate.tp_linear_all_reduce(attn_out.view(T, -1), self._dense(lw.o, lw.o_t, st=lw.o_s),
+                                                self._pipe_chunks(T))
                 ops.fused_add_rmsnorm(o, residual, lw.post_norm, eps, out=x)
             else:
-                o = self._linear(attn_out.view(T, -1), lw.o, lw.o_t, kind="o")
+                o = self._linear(attn_out.view(T, -1), lw.o, lw.o_t, kind="o", st=lw.o_s)
                 if tp:
                     pstate.tp_all_reduce_add_rmsnorm(o, residual, lw.post_norm, eps, out=x)
                 else:
@@ -270,23 +320,24 @@ class TransformerLM:
                 pending = tp and not self.moe.reduced
                 continue
             if self.stream and lw.glu and 0 < T <= self.stream_max_m:
-                a = ops.linear_glu(x, lw.gate_up_t)  # SwiGLU in the GEMM epilogue (or on its slabs)
+                a = ops.linear_glu(x, lw.gate_up_t, scale=lw.gate_up_s)  # SwiGLU in the GEMM epilogue (or on its slabs)
             elif (self.stream and lw.glu and "gate_up" in SKINNY and lw.gate_up_t is not None
-                  and ops.skinny_plan(T, lw.gate_up_t.shape[0] * 32, x.shape[1])):
+                  and not ops.is_fp8_weight(lw.gate_up_t) and ops.skinny_plan(T, lw.gate_up_t.shape[0] * 32, x.shape[1])):
                 a = ops.linear_skinny(x, lw.gate_up_t, glu=True)  # fused SwiGLU (one split) or gate | up slabs
                 if ops.is_slab(a):
                     a = ops.silu_mul(a)
             else:
-                a = ops.silu_mul(F.linear(x, self._dense(lw.gate_up, lw.gate_up_t, bool(lw.glu))))
+                a = ops.silu_mul(F.linear(x, self._dense(lw.gate_up, lw.gate_up_t, bool(lw.glu), lw.gate_up_s)))
             if tp and self._can_overlap(T, lw.down_t) and i + 1 < len(self.layers):
                 # the next layer's input RMSNorm is the seam's normalisation: delta is consumed here
                 self._overlapped_seam(a, lw.down_t, residual, self.layers[i + 1].input_norm, eps, x)
                 delta, pending = _SEAM_DONE, False
             elif tp and self._can_pipe(T, lw.down, lw.down_t):
-                delta = pstate.tp_linear_all_reduce(a, self._dense(lw.down, lw.down_t), self._pipe_chunks(T))
+                delta = pstate.tp_linear_all_reduce(a, self._dense(lw.down, lw.down_t, st=lw.down_s),
+                                                    self._pipe_chunks(T))
                 pending = False  # already reduced: the next seam is a plain add + RMSNorm
             else:
-                delta = self._linear(a, lw.down, lw.down_t, kind="down")
+                delta = self._linear(a, lw.down, lw.down_t, kind="down", st=lw.down_s)
                 pending = tp
         if pending:
             delta = pstate.tp_all_reduce(delta)
@@ -294,7 +345,7 @@ class TransformerLM:
         d_sel = delta.index_select(1 if ops.is_slab(delta) else 0, rows)
         r_sel = residual.index_select(0, rows)
         hf = ops.fused_add_rmsnorm(d_sel, r_sel, self.final_norm, eps)
-        logits = self._linear(hf, self.lm_head, self.lm_head_t, max_splits=1)
+        logits = self._linear(hf, self.lm_head, self.lm_head_t, max_splits=1, st=self.lm_head_s)
         if not gather:
             return logits
         if tp:
@@ -306,6 +357,8 @@ class TransformerLM:
         copy, the KV cache is bf16 with 128-dim heads and the shapes fit the fused epilogues."""
         if not (FUSED and self.stream and self.tp == 1 and not self.dp_attention and 0 < T <= self.stream_max_m):
             return False
+        if self.weight_dtype != "bf16" or ops.is_fp8_weight(self.layers[0].qkv_t):
+            return False  # the fused epilogues read bf16 tiles only
         if self._fused_shapes is None:
             lw0 = self.layers[0]
             ok = all(lw.router is None and lw.glu and lw.qkv_t is not None and lw.o_t is not None and
@@ -346,11 +399,11 @@ class TransformerLM:
                 ops.linear_res(a, lw.down_t, residual, self.layers[i + 1].input_norm, x, ss[1], pool="fin_down")
                 ss_in = ss[1]
             else:
-                delta = self._linear(a, lw.down, lw.down_t, kind="down")
+                delta = self._linear(a, lw.down, lw.down_t, kind="down", st=lw.down_s)
         rows = inp.logit_rows
         d_sel = delta.index_select(1 if ops.is_slab(delta) else 0, rows)
         hf = ops.fused_add_rmsnorm(d_sel, residual.index_select(0, rows), self.final_norm, eps)
-        logits = self._linear(hf, self.lm_head, self.lm_head_t, max_splits=1)
+        logits = self._linear(hf, self.lm_head, self.lm_head_t, max_splits=1, st=self.lm_head_s)
         return logits if not gather else logits[:, :cfg.vocab_size]
 
     def _can_pipe(self, T: int, w: torch.Tensor | None, wt: torch.Tensor | None) -> bool:
@@ -368,6 +421,8 @@ class TransformerLM:
     def _can_overlap(self, T: int, wt: torch.Tensor | None) -> bool:
         if not (TP_OVERLAP and self.stream and wt is not None and 0 < T <= self.stream_max_m and self.device.type == "cuda"):
             return False
+        if ops.is_fp8_weight(wt):
+            return False  # (the overlapped seam slices bf16 tiles)
         car = pstate.custom_ar()
         return car is not None and wt.shape[0] % 2 == 0 and T * wt.shape[0] * 32 * 2 <= car.max_bytes
 
@@ -408,8 +463,8 @@ class TransformerLM:
     # ------------------------------------------------------------------------------------------------------------
     def weight_bytes(self) -> int:
         """Device bytes of every weight tensor, wave-tiled copies included (so tiled-only models report fully)."""
-        ts = list(self.named_tensors().values()) + [self.lm_head_t]
-        ts += [getattr(lw, s) for lw in self.layers for s in LayerWeights.__slots__ if s.endswith("_t")]
+        ts = list(self.named_tensors().values()) + [self.lm_head_t, self.lm_head_s]
+        ts += [getattr(lw, s) for lw in self.layers for s in LayerWeights.__slots__ if s.endswith(("_t", "_s"))]
         return sum(t.numel() * t.element_size() for t in ts if isinstance(t, torch.Tensor))
 
     def named_tensors(self) -> dict[str, torch.Tensor]:
@@ -417,6 +472,6 @@ class TransformerLM:
         for i, lw in enumerate(self.layers):
             for s in LayerWeights.__slots__:
                 t = getattr(lw, s)
-                if isinstance(t, torch.Tensor) and not s.endswith("_t"):
+                if isinstance(t, torch.Tensor) and not s.endswith(("_t", "_s")):
                     out[f"layers.{i}.{s}"] = t
         return {k: v for k, v in out.items() if v is not None}

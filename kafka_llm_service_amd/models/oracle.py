@@ -47,9 +47,12 @@ def dense_logits(model: TransformerLM, tokens: list[int], fp32: bool = False) ->
     D, hq, hkv = model.D, model.hq, model.hkv
     G = hq // hkv
     mask = torch.ones(T, T, dtype=torch.bool, device=dev).tril()
+    # the row-major weight of a streamed projection: the stored tensor (with fp8 weights: the dequantised values the
+    # engine computes with) or, for a tiled-only model, its untiled / dequantised tiles
+    W = model.dense_weight
     for lw in model.layers:
         x = _rms(h, lw.input_norm, cfg.rms_norm_eps)
-        qkv = _lin(x, lw.qkv)
+        qkv = _lin(x, W(lw, "qkv"))
         q = qkv[:, :hq * D].view(T, hq, D)
         k = qkv[:, hq * D:(hq + hkv) * D].view(T, hkv, D)
         v = qkv[:, (hq + hkv) * D:].view(T, hkv, D)
@@ -59,7 +62,7 @@ def dense_logits(model: TransformerLM, tokens: list[int], fp32: bool = False) ->
         s = torch.einsum("thd,shd->hts", q.float(), kf) * model.scale
         s = s.masked_fill(~mask[None], float("-inf"))
         o = torch.einsum("hts,shd->thd", torch.softmax(s, -1), vf).to(h.dtype)
-        h = (h.float() + _lin(o.reshape(T, -1), lw.o).float()).to(h.dtype)
+        h = (h.float() + _lin(o.reshape(T, -1), W(lw, "o")).float()).to(h.dtype)
         x = _rms(h, lw.post_norm, cfg.rms_norm_eps)
         if lw.router is not None:
             w, e = route(_lin(x, lw.router), cfg.num_experts_per_tok)
@@ -76,13 +79,13 @@ def dense_logits(model: TransformerLM, tokens: list[int], fp32: bool = False) ->
                 out[rows] += y * (w * sel)[rows].sum(-1, keepdim=True)
             delta = out.to(h.dtype)
         else:
-            gu = _lin(x, lw.gate_up)
+            gu = _lin(x, W(lw, "gate_up"))
             Fh = gu.shape[-1] // 2
             a = (F.silu(gu[:, :Fh].float()) * gu[:, Fh:].float()).to(x.dtype)
-            delta = _lin(a, lw.down)
+            delta = _lin(a, W(lw, "down"))
         h = (h.float() + delta.float()).to(h.dtype)
     x = _rms(h, model.final_norm, cfg.rms_norm_eps)
-    return _lin(x, model.lm_head).float()[:, :cfg.vocab_size]
+    return _lin(x, W(None, "lm_head")).float()[:, :cfg.vocab_size]
 
 
 def greedy_generate(model: TransformerLM, prompt: list[int], n: int) -> list[int]:

@@ -229,14 +229,11 @@ def save_safetensors(model: TransformerLM, path: str | Path) -> None:
     assert model.tp == 1
     D, F = cfg.head_dim, cfg.intermediate_size
     qn, kn = cfg.num_heads * D, cfg.num_kv_heads * D
-    from kafka_llm_service_amd import ops
 
-    def dense(lw, name):  # tiled-only models keep just the wave-tiled copy: untile it for export
-        w = getattr(lw, name)
-        return w if w is not None else ops.untile_weight(getattr(lw, name + "_t"), glu=bool(lw.glu) and
-                                                         name == "gate_up")
+    def dense(lw, name):  # tiled-only models keep just the wave-tiled copy: untile (fp8: dequantise) it for export
+        return model.dense_weight(lw, name)
 
-    lm_head = model.lm_head if model.lm_head is not None else ops.untile_weight(model.lm_head_t)
+    lm_head = model.dense_weight(None, "lm_head")
     out = {"model.embed_tokens.weight": model.embed, "lm_head.weight": lm_head,
            "model.norm.weight": model.final_norm}
     for i, lw in enumerate(model.layers):

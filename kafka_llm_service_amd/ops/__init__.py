@@ -300,6 +300,21 @@ def untile_weight(wt: torch.Tensor, glu: bool = False) -> torch.Tensor:
     return wt.reshape(nb, kb, 2, 32, 8).permute(0, 3, 1, 2, 4).reshape(nb * 32, kb * 16)
 
 
+# fp8 weights (weight_dtype="fp8"): e4m3 wave tiles uint8 [N/32, K/32, 64, 16] plus fp32 power-of-two row scales [N]
+# (layout and quantisation rule: reference.tile_weight_fp8); linear_stream / linear_glu take them with ``scale``.
+tile_weight_fp8 = ref.tile_weight_fp8
+untile_weight_fp8 = ref.untile_weight_fp8
+
+
+def is_fp8_weight(wt: torch.Tensor | None) -> bool:
+    return wt is not None and wt.dtype == torch.uint8
+
+
+def tiled_dims(wt: torch.Tensor) -> tuple[int, int]:
+    """(N, K) of a wave-tiled weight: bf16 tiles [N/32, K/16, 64, 8] or fp8 tiles [N/32, K/32, 64, 16]."""
+    return wt.shape[0] * 32, wt.shape[1] * (32 if wt.dtype == torch.uint8 else 16)
+
+
 # Steps of up to this many rows run the dense projections on the weight-streaming kernel (csrc/wstream_gemm.hip).
 # The kernel takes up to 256 rows: one 192-row tile (MT = 6) up to 192, beyond that two row tiles of 128 sharing each
 # weight slice through the MALL, where it loses to hipBLASLt (gate_up 101 vs 66 us at 168..248 rows; bench 7,359 vs
@@ -365,26 +380,38 @@ def linear_skinny(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: b
 
 
 def linear_stream(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, nt: bool = True,
-                  glu: bool = False) -> torch.Tensor:
+                  glu: bool = False, scale: torch.Tensor | None = None) -> torch.Tensor:
     """y = x @ W^T for decode-sized M (<= 128) from the wave-tiled weight ``wt``: the weight-streaming MFMA kernel.
     Returns bf16 [M, N] when the plan has one split, else the fp32 split-K slabs [S, M, N] (a slab; the consumer
     kernels sum it while loading). ``glu`` (wt tiled with glu=True): a one-split plan returns the ACTIVATED
-    silu(gate) * up [M, N/2] (fused epilogue); a split plan returns gate | up slabs as usual (see ``linear_glu``)."""
+    silu(gate) * up [M, N/2] (fused epilogue); a split plan returns gate | up slabs as usual (see ``linear_glu``).
+    fp8 tiles (uint8 ``wt`` from ``tile_weight_fp8``) need their row scales ``scale``; same plans and outputs."""
     M, K = x.shape
+    w8 = wt.dtype == torch.uint8
+    if w8:
+        if scale is None:
+            raise ValueError("linear_stream: fp8 weight tiles need their row scales (scale=)")
+        if not nt:
+            raise ValueError("linear_stream: fp8 weight tiles stream non-temporally only (nt=False unsupported)")
+        if wt.shape[1] * 32 != K:
+            raise ValueError(f"linear_stream: x has K={K}, the fp8 tiles K={wt.shape[1] * 32}")
     N = wt.shape[0] * 32
     plan = stream_plan(M, N, K, max_splits)
     if plan is None:
         raise ValueError(f"linear_stream: unsupported shape M={M} N={N} K={K}")
     S = plan[2]
     if _gpu(x):
+        y = p = None
         if S == 1:
             y = torch.empty(M, N // 2 if glu else N, dtype=x.dtype, device=x.device)
-            ext().wstream_gemm(x, wt, y, None, int(max_splits), bool(nt), bool(glu))
-            return y
-        p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        ext().wstream_gemm(x, wt, None, p, int(max_splits), bool(nt), bool(glu))
-        return p
-    w = untile_weight(wt, glu).float()
+        else:
+            p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
+        if w8:
+            ext().wstream_gemm_w8(x, wt, scale, y, p, int(max_splits), bool(glu))
+        else:
+            ext().wstream_gemm(x, wt, y, p, int(max_splits), bool(nt), bool(glu))
+        return y if S == 1 else p
+    w = (untile_weight_fp8(wt, scale, glu) if w8 else untile_weight(wt, glu)).float()
     xf = x.float()
     if S == 1:
         y = xf @ w.t()
@@ -395,12 +422,13 @@ def linear_stream(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, nt: bo
     return torch.stack([xf[:, s * ks:(s + 1) * ks] @ w[:, s * ks:(s + 1) * ks].t() for s in range(S)])
 
 
-def linear_glu(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8) -> torch.Tensor:
+def linear_glu(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8,
+               scale: torch.Tensor | None = None) -> torch.Tensor:
     """silu(x @ Wg^T) * (x @ Wu^T) from GLU-tiled gate_up weights: fused into the GEMM epilogue when the plan has one
-    split, else the GEMM's slabs go through silu_mul."""
+    split, else the GEMM's slabs go through silu_mul. ``scale``: the row scales of fp8 tiles."""
     N = wt.shape[0] * 32
     plan = stream_plan(x.shape[0], N, x.shape[1], max_splits)
-    y = linear_stream(x, wt, max_splits, glu=True)
+    y = linear_stream(x, wt, max_splits, glu=True, scale=scale)
     return y if plan is not None and plan[2] == 1 else silu_mul(y)
 
 

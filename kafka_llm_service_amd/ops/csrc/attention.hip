@@ -58,18 +58,10 @@ __device__ __forceinline__ float xor32_sum(float x) {
 }
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float exp2i(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
 
-// 8 e4m3 bytes (two dwords) -> bf16x8 times `sc` (a power of two)
-__device__ __forceinline__ bf16x8 dq8(uint32_t lo, uint32_t hi, float sc) {
-  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, false);
-  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, true);
-  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, false);
-  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, true);
-  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-}
+// (u32x4 and dq8, the e4m3 -> bf16x8 dequantisation: common.h, shared with the fp8-weight decode GEMM)
 
 template <int D>
 struct WaveAcc {

@@ -164,6 +164,18 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// 8 e4m3 bytes (two dwords) -> bf16x8 times `sc` (a power of two): v_cvt_scalef32_pk_bf16_fp8, one VALU op per two
+// elements (fp8 KV cache: attention.hip; fp8 weights: wstream_gemm.hip W8)
+__device__ __forceinline__ bf16x8 dq8(uint32_t lo, uint32_t hi, float sc) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, true);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, false);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, true);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
 // Counter-based RNG (splitmix64 finaliser): deterministic given (seed, stream, index).
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;

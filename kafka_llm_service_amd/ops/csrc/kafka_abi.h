@@ -158,6 +158,11 @@ int kafka_wstream_plan(int M, int N, int K, int max_splits, int* mt, int* kc, in
 hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int mt, int kc,
                                      int splits, int nt, int kw, int pin, int glu, bf16* Y, int64_t ldy, float* P,
                                      hipStream_t st);
+// fp8 weights: Wt8 [N/32][K/32][64 lanes][16] e4m3 bytes (ops.tile_weight_fp8: a lane's 16 B are the B fragments of
+// two k-steps), St [N] fp32 power-of-two row scales in tile order; plans, configurations and outputs as above
+hipError_t kafka_launch_wstream_gemm_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St, int M, int N,
+                                        int K, int mt, int kc, int splits, int kw, int pin, int glu, bf16* Y,
+                                        int64_t ldy, float* P, hipStream_t st);
 // Fused decode-layer GEMMs (FIN_RES / FIN_ROPE / FIN_GLU): one row tile (M <= 128), N % 128 == 0, S in
 // {1, 2, 4, 8}; P = [S][M][N] fp32 scratch (unused for S == 1); FIN_GLU needs S == 1.
 hipError_t kafka_launch_wstream_fin(int fin, const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int mt,

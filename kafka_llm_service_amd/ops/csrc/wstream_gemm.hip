@@ -24,6 +24,7 @@
 #include "common.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace kafka {
 
@@ -219,7 +220,15 @@ __device__ __forceinline__ void fin_rope(const float* tp, const float* P, int by
 // stays because dropping it changes register allocation — MT = 3 FIN_GLU gains 4 VGPR spills — which wants its own
 // measurement.)
 enum { WIDE_P = 1, WIDE_Y = 2 };
-template <int MT, int KC, bool NT, int KW, bool PIN, int FIN = FIN_NONE>
+// W8 (fp8 weights, ops.tile_weight_fp8): Wt is the e4m3 image Wt8[N/32][K/32][64 lanes][16 B] — bytes 0..7 of lane
+// (r, h) of tile (nb, kb2) = W[32 nb + r][32 kb2 + 8 h : +8] (k-step 2 kb2), bytes 8..15 the same 8 columns 16 further
+// (k-step 2 kb2 + 1) — so one 16-B load per lane carries the B fragments of TWO k-steps and a wave-instruction is
+// still one contiguous 1 KB run: half the loads, half the prefetch registers, half the bytes. St[32 nb + r] is the
+// power-of-two scale of the lane's row; it is the scale operand of v_cvt_scalef32_pk_bf16_fp8 (dq8), so the B
+// fragments are the exact bf16 values e4m3 * 2^e, the MFMA stays bf16 and the accumulators hold true values: every
+// epilogue is shared with the bf16 kernel. St travels in fa.ss_in (W8 is FIN_NONE only, where no epilogue reads it), so
+// the kernel's argument block — and with it every bf16 instantiation — is byte for byte what it was without W8.
+template <int MT, int KC, bool NT, int KW, bool PIN, int FIN = FIN_NONE, bool W8 = false>
 __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __restrict__ X, int64_t ldx,
                                                                  const bf16x8* __restrict__ Wt, int M, int N, int K,
                                                                  int ks, bf16* __restrict__ Y, int64_t ldy,
@@ -231,7 +240,10 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   constexpr int XL = ROWS * CPR / NTH;    // X chunks staged per thread
   constexpr int KSTEP = KC / 16;          // MFMA k-steps per K chunk
   constexpr int KSW = KSTEP / KW;         // k-steps of one wave (KW waves split each chunk along K)
+  constexpr int KSV = W8 ? KSW / 2 : KSW;  // 16-B weight vectors of one wave per chunk (W8: two k-steps each)
+  typedef typename std::conditional<W8, u32x4, bf16x8>::type wvec;
   static_assert(CPR >= 16 && XL >= 1 && KSW >= 1, "chunk too small");
+  static_assert(!W8 || (KSW % 2 == 0 && FIN == FIN_NONE && NT), "fp8 tiles hold k-step pairs; plain epilogues only");
   static_assert(2 * ROWS * KC * 2 >= 4 * (KW - 1) * MT * 16 * 64 * 4, "LDS too small for the K-half reduction");
   __shared__ __attribute__((aligned(16))) bf16 xs[2][ROWS * KC];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -261,8 +273,12 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   const bool active = nb < (N >> 5);
   const int k0 = blockIdx.y * ks;
   const int nchunks = ks / KC;
-  const bf16x8* wp =
-      Wt + ((int64_t)(active ? nb : (N >> 5) - 1) * (K >> 4) + (k0 >> 4) + kh * KSW) * 64 + lane;
+  const int nbl = active ? nb : (N >> 5) - 1;
+  // (both layouts: K / 16 bf16 or K / 32 fp8 vectors of 64 lanes x 16 B per tile row, KSV per wave and chunk)
+  const wvec* wp = reinterpret_cast<const wvec*>(Wt) +
+                   ((int64_t)nbl * (W8 ? K >> 5 : K >> 4) + (W8 ? k0 >> 5 : k0 >> 4) + kh * KSV) * 64 + lane;
+  float wsc = 1.f;  // W8: 2^e of this lane's weight row
+  if constexpr (W8) wsc = fa.ss_in[32 * nbl + r];
 
   // phase stamps (FinArgs::stamps, benchmarks only): 0 start, 1 main loop done, 2 slab stores drained, 3 ticket
   // taken (finisher), 4 finisher done
@@ -303,10 +319,10 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
       *reinterpret_cast<bf16x8*>(&xs[buf][row * KC + 8 * (c ^ (row & 15))]) = xr[i];
     }
   };
-  auto load_w = [&](bf16x8(&wv)[KSW], int ch) {
+  auto load_w = [&](wvec(&wv)[KSV], int ch) {
 #pragma unroll
-    for (int t = 0; t < KSW; ++t) {
-      const bf16x8* p = wp + (int64_t)(ch * KSTEP + t) * 64;
+    for (int t = 0; t < KSV; ++t) {
+      const wvec* p = wp + (int64_t)(ch * (KSV * KW) + t) * 64;
       wv[t] = NT ? __builtin_nontemporal_load(p) : *p;
     }
     // PIN keeps the prefetch where it is issued: left alone, the machine scheduler sinks these loads (and the X
@@ -319,19 +335,27 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[mt][i] = 0.f;
-  auto compute = [&](int buf, const bf16x8(&wv)[KSW]) {
+  auto compute = [&](int buf, const wvec(&wv)[KSV]) {
 #pragma unroll
     for (int t = 0; t < KSW; ++t) {
+      bf16x8 wf;
+      if constexpr (W8) {
+        // dequantised right before its MFMAs: the prefetch registers keep the raw fp8
+        const u32x4 v = wv[t >> 1];
+        wf = (t & 1) ? dq8(v[2], v[3], wsc) : dq8(v[0], v[1], wsc);
+      } else {
+        wf = wv[t];
+      }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         const int m = mt * 32 + r, c = 2 * (kh * KSW + t) + h;
         const bf16x8 xf = *reinterpret_cast<const bf16x8*>(&xs[buf][m * KC + 8 * (c ^ (m & 15))]);
-        acc[mt] = mfma32(xf, wv[t], acc[mt]);
+        acc[mt] = mfma32(xf, wf, acc[mt]);
       }
     }
   };
 
-  bf16x8 wa[KSW], wb[KSW];
+  wvec wa[KSV], wb[KSV];
   // X first: its LDS image is written while the first weight chunk is still in flight (loads return in order)
   load_x(0);
   load_w(wa, 0);
@@ -893,6 +917,50 @@ extern "C" hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, cons
   else return hipErrorInvalidValue;
 #undef KAFKA_WS_IF
 #undef KAFKA_WS
+  return hipGetLastError();
+}
+
+// fp8 weights (W8 above): Wt8 [N/32][K/32][64][16] e4m3 bytes, St [N] fp32 row scales in tile order. Same plans,
+// grid, outputs and (mt, kc, kw, pin) configurations as kafka_launch_wstream_gemm; always non-temporal loads.
+extern "C" hipError_t kafka_launch_wstream_gemm_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St,
+                                                  int M, int N, int K, int mt, int kc, int splits, int kw, int pin,
+                                                  int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st) {
+  if (M < 1) return hipSuccess;
+  if (glu && (N % 64 != 0 || kw > 2)) return hipErrorInvalidValue;
+  if (K % 32 != 0 || N % 32 != 0 || Wt8 == nullptr || St == nullptr) return hipErrorInvalidValue;
+  if (K % (kc * splits) != 0 || (splits > 1 && P == nullptr) || (splits == 1 && P == nullptr && Y == nullptr))
+    return hipErrorInvalidValue;
+  const int rt = (M + 32 * mt - 1) / (32 * mt);
+  const int nblk = (N + 127) / 128;
+  const dim3 grid((rt > 1 ? (nblk + 7) / 8 * 8 : nblk) * rt, splits);
+  const int ks = K / splits;
+  const auto* wt = reinterpret_cast<const bf16x8*>(Wt8);
+  float* p = splits > 1 ? P : nullptr;
+  const bool y_unaligned = Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0);
+  const int wide = y_unaligned ? WIDE_P : (WIDE_P | WIDE_Y);
+  FinArgs fa{};
+  fa.ss_in = St;  // (the W8 kernel's row scales: see the kernel's header comment)
+#define KAFKA_W8(MT_, KC_, KW_, PIN_)                                                                              \
+  wstream_gemm_kernel<MT_, KC_, true, KW_, PIN_, FIN_NONE, true><<<grid, 256 * KW_, 0, st>>>(                      \
+      X, ldx, wt, M, N, K, ks, Y, ldy, p, glu, rt, wide, fa)
+#define KAFKA_W8_IF(MT_, KC_, KW_)                                      \
+  if (mt == MT_ && kc == KC_ && kw == KW_) {                           \
+    if (pin)                                                           \
+      KAFKA_W8(MT_, KC_, KW_, true);                                   \
+    else                                                               \
+      KAFKA_W8(MT_, KC_, KW_, false);                                  \
+  }
+  KAFKA_W8_IF(1, 256, 1)
+  else KAFKA_W8_IF(1, 256, 2)
+  else KAFKA_W8_IF(2, 256, 1)
+  else KAFKA_W8_IF(2, 256, 2)
+  else KAFKA_W8_IF(3, 256, 1)
+  else KAFKA_W8_IF(4, 128, 1)
+  else KAFKA_W8_IF(4, 128, 2)
+  else KAFKA_W8_IF(6, 128, 1)
+  else return hipErrorInvalidValue;
+#undef KAFKA_W8_IF
+#undef KAFKA_W8
   return hipGetLastError();
 }
 

@@ -66,6 +66,38 @@ def fp8_quant(x: torch.Tensor):
     return y.to(torch.float8_e4m3fn).view(torch.uint8), e
 
 
+def tile_weight_fp8(w: torch.Tensor, glu: bool = False):
+    """Row-major weight [N, K] -> (wt8 uint8 [N/32, K/32, 64, 16], st fp32 [N]): every row quantised over its whole K
+    by ``fp8_quant`` (e4m3 bytes, one power-of-two scale 2^e per row) and laid out for the fp8 weight-streaming GEMM
+    (csrc/wstream_gemm.hip W8): lane l = (r = l % 32, h = l // 32) of tile (nb, kb2) holds W[32 nb + r,
+    32 kb2 + 8 h : +8] in bytes 0..7 (MFMA k-step 2 kb2) and W[32 nb + r, 32 kb2 + 16 + 8 h : +8] in bytes 8..15
+    (k-step 2 kb2 + 1). ``st`` is in tile order: st[32 nb + r] scales the row of lane r of tile nb. ``glu``
+    interleaves the 32-row tiles gate_0, up_0, gate_1, ... as ``tile_weight`` does."""
+    N, K = w.shape
+    if N % 32 or K % 32 or (glu and N % 64):
+        raise ValueError(f"tile_weight_fp8: N={N} K={K} must be multiples of 32 (N of 64 with glu)")
+    q, e = fp8_quant(w)
+    t = q.reshape(N // 32, 32, K // 32, 2, 2, 8).permute(0, 2, 4, 1, 3, 5)
+    s = torch.exp2(e.float()).reshape(N // 32, 32)
+    if glu:
+        t = t.reshape(2, N // 64, K // 32, 2, 32, 2, 8).transpose(0, 1)
+        s = s.reshape(2, N // 64, 32).transpose(0, 1)
+    return t.contiguous().view(N // 32, K // 32, 64, 16), s.contiguous().view(N)
+
+
+def untile_weight_fp8(wt8: torch.Tensor, st: torch.Tensor, glu: bool = False) -> torch.Tensor:
+    """The dequantised row-major weight e4m3 * 2^e of fp8 tiles: bf16 [N, K], exact (3 mantissa bits, and the
+    exponents fp8_quant picks for bf16 inputs stay in bf16's range)."""
+    nb, kb = wt8.shape[0], wt8.shape[1]
+    st = st.view(nb, 32)
+    if glu:
+        wt8 = wt8.view(nb // 2, 2, kb, 64, 16).transpose(0, 1).reshape(nb, kb, 64, 16)
+        st = st.view(nb // 2, 2, 32).transpose(0, 1).reshape(nb, 32)
+    q = wt8.reshape(nb, kb, 2, 32, 2, 8).permute(0, 3, 1, 4, 2, 5).reshape(nb * 32, kb * 32)
+    w = q.contiguous().view(torch.float8_e4m3fn).float() * st.reshape(nb * 32, 1)
+    return w.to(torch.bfloat16)
+
+
 def fp8_dequant_pages(k_pages: torch.Tensor, v_pages: torch.Tensor):
     """fp8 pages (K [n, Hkv, 16D + 32], V [n, Hkv, 16D] uint8) -> fp32 K [n, Hkv, 16, D] and V [n, Hkv, D, 16]
     (V in natural key order)."""

@@ -84,11 +84,14 @@ class ServerConfig:
 
 
 def _engine_kwargs(e) -> dict[str, Any]:
-    """Engine options from the environment: KAFKA_KV_DTYPE (bf16 | fp8 KV cache), KAFKA_GRAPHS=1 (hipGraph decode
+    """Engine options from the environment: KAFKA_KV_DTYPE (bf16 | fp8 KV cache), KAFKA_WEIGHT_DTYPE (bf16 | fp8 dense
+    projections and lm_head), KAFKA_GRAPHS=1 (hipGraph decode
     steps), KAFKA_MAX_NUM_SEQS, KAFKA_MAX_BATCHED_TOKENS."""
     kw: dict[str, Any] = {}
     if e.get("KAFKA_KV_DTYPE"):
         kw["kv_dtype"] = e["KAFKA_KV_DTYPE"]
+    if e.get("KAFKA_WEIGHT_DTYPE"):
+        kw["weight_dtype"] = e["KAFKA_WEIGHT_DTYPE"]
     if e.get("KAFKA_GRAPHS") in ("0", "1"):  # unset: the engine's default (on for TP > 1)
         kw["use_graphs"] = e["KAFKA_GRAPHS"] == "1"
     if e.get("KAFKA_MAX_NUM_SEQS"):
