@@ -65,8 +65,8 @@ class EngineConfig:
     # decode GEMMs: "stream" = weight-streaming MFMA kernel on wave-tiled weight copies (csrc/wstream_gemm.hip),
     # "blas" = hipBLASLt only; "auto" = stream on GPU (env KAFKA_DECODE_GEMM overrides)
     decode_gemm: str = "auto"           # auto | stream | stream_only (tiled weights only) | blas
-    # dense projections + lm_head: "bf16", or "fp8" = e4m3 wave tiles with one power-of-two scale per output row
-    # (half the bytes of every decode GEMM and of the tiled copy; the row-major weights become the dequantised
+    # dense projections, lm_head and MoE experts: "bf16", or "fp8" = e4m3 wave tiles with one power-of-two scale per
+    # output row (half the bytes of every decode GEMM and of the tiled copy; the row-major weights become the dequantised
     # values, so every path and the oracle run the same quantised model; models/llama.py enable_stream_weights).
     # Needs the streaming decode GEMM (auto resolves to stream); env KAFKA_WEIGHT_DTYPE overrides
     weight_dtype: str = "bf16"          # bf16 | fp8

@@ -79,7 +79,8 @@ class StepInput:
 class LayerWeights:
     __slots__ = ("input_norm", "post_norm", "qkv", "o", "gate_up", "down", "router", "w13", "w2", "expert_ids",
                  "qkv_t", "o_t", "gate_up_t", "down_t", "glu", "w13_t", "w2_t",
-                 "qkv_s", "o_s", "gate_up_s", "down_s")  # _s: fp32 row scales of fp8 tiles (weight_dtype="fp8")
+                 "qkv_s", "o_s", "gate_up_s", "down_s",  # _s: fp32 row scales of fp8 tiles (weight_dtype="fp8")
+                 "w13_s", "w2_s")
     STREAMED = ("qkv", "o", "gate_up", "down")  # projections with a wave-tiled copy for the decode GEMM
 
     def __init__(self):
@@ -143,10 +144,11 @@ class TransformerLM:
     # ------------------------------------------------------------------------------------------------------------
     def stream_weight_bytes(self, weight_dtype: str = "bf16") -> int:
         """Bytes enable_stream_weights would add (the wave-tiled copies; 0 in tiled-only mode). ``"fp8"``: one byte
-        per element plus a 4-byte scale per row for the dense projections and the lm_head; experts stay bf16."""
+        per element plus a 4-byte scale per row for the dense projections, the lm_head and the MoE experts (a scale
+        per row of every expert)."""
         def tiled(w):
             if weight_dtype == "fp8":
-                return w.numel() + 4 * w.shape[0]
+                return w.numel() + 4 * (w.numel() // w.shape[-1])
             return w.numel() * w.element_size()
 
         n = 0
@@ -158,7 +160,7 @@ class TransformerLM:
             for name in ("w13", "w2"):
                 w = getattr(lw, name)
                 if w is not None and ops.stream_moe_supported(w.shape[1], w.shape[2]):
-                    n += w.numel() * w.element_size()
+                    n += tiled(w)
         if self.lm_head is not None and ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
             n += tiled(self.lm_head)
         return n
@@ -172,14 +174,19 @@ class TransformerLM:
         ``tiled_only``: when the second copy does not fit (Llama-3-70B on one GPU), the row-major dense projections
         and the lm_head are dropped after tiling (no extra memory) and prefill-sized steps untile one weight at a
         time into a transient buffer for hipBLASLt (``_dense``); MoE experts keep their row-major layout only
-        (grouped GEMM at every step size — a tiled expert copy would be the 90 GB second copy this mode avoids).
+        (grouped GEMM at every step size — a tiled expert copy would be the 90 GB second copy this mode avoids), and
+        that single copy stays unquantised bf16 under ``weight_dtype="fp8"`` too (``w13_t`` is None).
 
         ``weight_dtype="fp8"``: the tiles are e4m3 with one power-of-two scale per output row
         (ops.tile_weight_fp8: ``<name>_t`` uint8, ``<name>_s`` fp32) — half the bytes per decode step and half the
         tiled copy. The model then IS the quantised model at every step size: the row-major bf16 tensor of each
         quantised projection is replaced by its dequantised values (exact in bf16), so hipBLASLt prefill, the streamed
-        decode steps and the dense oracle compute with the same weights. Embedding, norms, router and MoE experts stay
-        bf16; the skinny GEMM and the fused decode layer do not take fp8 tiles (hipBLASLt / the unfused layer run)."""
+        decode steps and the dense oracle compute with the same weights. The MoE experts are quantised the same way
+        where their tiled copy is made (ops.tile_experts_fp8: ``w13_t`` / ``w2_t`` uint8, ``w13_s`` / ``w2_s`` fp32
+        [E_local, N]; every expert-parallel rank quantises its own whole experts, rows over their whole K, so a rank's
+        tiles equal the matching slice of the unsharded model's) and row-major ``w13`` / ``w2`` become the dequantised
+        experts that ``ops.grouped_gemm`` runs on prefill-sized steps. Embedding, norms and router stay bf16; the
+        skinny GEMM and the fused decode layer do not take fp8 tiles (hipBLASLt / the unfused layer run)."""
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype must be bf16 or fp8, not {weight_dtype!r}")
         fp8 = weight_dtype == "fp8"
@@ -213,9 +220,17 @@ class TransformerLM:
             if not tiled_only and lw.w13 is not None and \
                     ops.stream_moe_supported(lw.w13.shape[1], lw.w13.shape[2]) and \
                     ops.stream_moe_supported(lw.w2.shape[1], lw.w2.shape[2]):
-                lw.w13_t = ops.tile_experts(lw.w13, glu=True)  # expert MLPs: grouped streaming kernel
-                lw.w2_t = ops.tile_experts(lw.w2)
-                added += (lw.w13.numel() + lw.w2.numel()) * lw.w13.element_size()
+                if fp8:  # expert MLPs: grouped streaming kernel on e4m3 tiles, row-major = the dequantised experts
+                    for name, glu in (("w13", True), ("w2", False)):
+                        wt, st = ops.tile_experts_fp8(getattr(lw, name), glu=glu)
+                        setattr(lw, name + "_t", wt)
+                        setattr(lw, name + "_s", st)
+                        setattr(lw, name, ops.untile_experts_fp8(wt, st, glu=glu))
+                        added += wt.numel() + st.numel() * st.element_size()
+                else:
+                    lw.w13_t = ops.tile_experts(lw.w13, glu=True)  # expert MLPs: grouped streaming kernel
+                    lw.w2_t = ops.tile_experts(lw.w2)
+                    added += (lw.w13.numel() + lw.w2.numel()) * lw.w13.element_size()
         if ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
             # (an lm_head that aliases the embedding gets a tensor of its own here: the embedding keeps its values)
             self.lm_head_t, self.lm_head_s, keep, nbytes = tile(self.lm_head)

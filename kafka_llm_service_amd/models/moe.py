@@ -10,6 +10,11 @@ Per layer: router GEMM (hipBLASLt) -> ``ops.moe_route`` (HIP, one workgroup: sof
 expert sort, no host sync) -> ``ops.grouped_gemm`` gate_up (HIP MFMA, A rows gathered through the permutation) ->
 ``ops.silu_mul`` -> ``ops.grouped_gemm`` down with the routing-weighted scatter-combine fused into its epilogue
 (fp32 atomics onto a zeroed [T, d] buffer). On CPU the same calls run the fp32 references of ``ops/reference.py``.
+
+Decode-sized steps (T <= MOE_STREAM_MAX_T) of a model with streamed weights instead run ``ops.grouped_stream_glu`` /
+``ops.grouped_stream_combine`` on the wave-tiled expert copies ``w13_t`` / ``w2_t``. With ``weight_dtype="fp8"`` those
+are e4m3 tiles with per-row scales ``w13_s`` / ``w2_s`` (half the streamed bytes) and the row-major ``w13`` / ``w2``
+hold the dequantised values, so larger steps (``ops.grouped_gemm``) compute with the same quantised experts.
 """
 from __future__ import annotations
 
@@ -62,9 +67,10 @@ class MoEBlock:
         if self.model.stream and lw.w13_t is not None and T <= MOE_STREAM_MAX_T:
             # decode-sized steps: expert weights streamed from their wave-tiled copies, SwiGLU fused into the gate_up
             # epilogue, weighted combine fused into the down epilogue (csrc/wstream_gemm.hip, grouped variant)
-            a = ops.grouped_stream_glu(x, lw.w13_t, r, e_lo=self.e0)
+            # (fp8 weights: e4m3 expert tiles with their row scales w13_s / w2_s, None for bf16 tiles)
+            a = ops.grouped_stream_glu(x, lw.w13_t, r, e_lo=self.e0, scale=lw.w13_s)
             out = torch.zeros(T, d, dtype=torch.float32, device=x.device)
-            ops.grouped_stream_combine(a, lw.w2_t, r, T, out, e_lo=self.e0)
+            ops.grouped_stream_combine(a, lw.w2_t, r, T, out, e_lo=self.e0, scale=lw.w2_s)
             return self._finish(out, x.dtype)
         # gate_up for every (token, expert) entry routed to a local expert, rows gathered from x by the kernel
         h = ops.grouped_gemm(x, lw.w13, r, gather=True, e_lo=self.e0)
@@ -133,8 +139,8 @@ class MoEBlock:
         rows = recv.view(-1, d)
         y = torch.zeros(rows.shape[0], d, dtype=torch.float32, device=x.device)
         if self.model.stream and lw.w13_t is not None and rows.shape[0] <= MOE_STREAM_MAX_T:
-            a = ops.grouped_stream_glu(rows, lw.w13_t, rr, e_lo=0)
-            ops.grouped_stream_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0)
+            a = ops.grouped_stream_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
+            ops.grouped_stream_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
         else:
             h = ops.grouped_gemm(rows, lw.w13, rr, gather=True, e_lo=0)
             ops.grouped_gemm(ops.silu_mul(h), lw.w2, rr, gather=False, e_lo=0, combine_out=y)
@@ -177,8 +183,8 @@ class MoEBlock:
         rows = recv.view(-1, d)
         y = torch.zeros(rows.shape[0], d, dtype=torch.float32, device=device)
         if self.model.stream and lw.w13_t is not None and rows.shape[0] <= MOE_STREAM_MAX_T:
-            a = ops.grouped_stream_glu(rows, lw.w13_t, rr, e_lo=0)
-            ops.grouped_stream_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0)
+            a = ops.grouped_stream_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
+            ops.grouped_stream_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
         else:
             h = ops.grouped_gemm(rows, lw.w13, rr, gather=True, e_lo=0)
             ops.grouped_gemm(ops.silu_mul(h), lw.w2, rr, gather=False, e_lo=0, combine_out=y)

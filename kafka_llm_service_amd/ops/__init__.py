@@ -595,7 +595,14 @@ def untile_experts(wt: torch.Tensor, glu: bool = False) -> torch.Tensor:
     return torch.stack([untile_weight(wt[e], glu) for e in range(wt.shape[0])])
 
 
+# fp8 expert weights: uint8 [E, N/32, K/32, 64, 16] tiles plus fp32 row scales [E, N] (reference.tile_experts_fp8);
+# grouped_stream_glu / grouped_stream_combine take them with ``scale``.
+tile_experts_fp8 = ref.tile_experts_fp8
+untile_experts_fp8 = ref.untile_experts_fp8
+
+
 def stream_moe_supported(N: int, K: int) -> bool:
+    # (bf16 and fp8 tiles alike: the kernel's 256- and 128-deep K chunks are 8 and 4 fp8 vectors, both even)
     return N % 64 == 0 and K % 256 == 0
 
 
@@ -604,30 +611,53 @@ def stream_moe_supported(N: int, K: int) -> bool:
 GROUPED_PIN = True
 
 
-def grouped_stream_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: int = 0) -> torch.Tensor:
+def _expert_scale(fn: str, wt: torch.Tensor, scale: torch.Tensor | None) -> bool:
+    """Whether ``wt`` are fp8 expert tiles; they need their row scales."""
+    w8 = is_fp8_weight(wt)
+    if w8 and scale is None:
+        raise ValueError(f"{fn}: fp8 expert tiles need their row scales (scale=)")
+    return w8
+
+
+def grouped_stream_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: int = 0,
+                       scale: torch.Tensor | None = None) -> torch.Tensor:
     """silu(gate) * up for every routed (token, local expert) entry, rows in expert-sorted order [n_ent, F]: the
-    weight-streaming grouped kernel on GLU-tiled expert weights (``tile_experts(w13, glu=True)``)."""
+    weight-streaming grouped kernel on GLU-tiled expert weights (``tile_experts(w13, glu=True)``, or the uint8 tiles
+    of ``tile_experts_fp8`` with their row scales ``scale``)."""
+    w8 = _expert_scale("grouped_stream_glu", wt, scale)
     T = x.shape[0]
     n_ent = r.perm_tok.numel()
-    F = wt.shape[1] * 16
+    F = wt.shape[1] * 16  # (N / 32 tiles of 32 rows, N = 2 F: either tile format)
     y = torch.empty(n_ent, F, dtype=x.dtype, device=x.device)
     if _gpu(x):
-        ext().wstream_grouped(x, wt, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), True, y, None,
-                              GROUPED_PIN)
+        if w8:
+            ext().wstream_grouped_w8(x, wt, scale, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), True, y,
+                                     None, GROUPED_PIN)
+        else:
+            ext().wstream_grouped(x, wt, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), True, y, None,
+                                  GROUPED_PIN)
         return y
-    h = ref_grouped(x, untile_experts(wt, glu=True), r, e_lo, gather=True)
+    w = untile_experts_fp8(wt, scale, glu=True) if w8 else untile_experts(wt, glu=True)
+    h = ref_grouped(x, w, r, e_lo, gather=True)
     y.copy_(ref.silu_mul(h))
     return y
 
 
 def grouped_stream_combine(a: torch.Tensor, wt: torch.Tensor, r: "MoERouting", T: int, out: torch.Tensor,
-                           e_lo: int = 0) -> torch.Tensor:
-    """out[token] += w * (a[entry] @ W_e^T) over the local experts' entries (out f32 [T, N], zeroed by the caller)."""
+                           e_lo: int = 0, scale: torch.Tensor | None = None) -> torch.Tensor:
+    """out[token] += w * (a[entry] @ W_e^T) over the local experts' entries (out f32 [T, N], zeroed by the caller).
+    ``scale``: the row scales of fp8 expert tiles."""
+    w8 = _expert_scale("grouped_stream_combine", wt, scale)
     if _gpu(a):
-        ext().wstream_grouped(a, wt, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), False, None, out,
-                              GROUPED_PIN)
+        if w8:
+            ext().wstream_grouped_w8(a, wt, scale, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), False, None,
+                                     out, GROUPED_PIN)
+        else:
+            ext().wstream_grouped(a, wt, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), False, None, out,
+                                  GROUPED_PIN)
         return out
-    ref.grouped_gemm(a, untile_experts(wt), r.perm_tok, r.perm_w, r.expert_off, e_lo, False, None, out)
+    w = untile_experts_fp8(wt, scale) if w8 else untile_experts(wt)
+    ref.grouped_gemm(a, w, r.perm_tok, r.perm_w, r.expert_off, e_lo, False, None, out)
     return out
 
 

@@ -679,15 +679,23 @@ static void wstream_gemm_cfg(at::Tensor x, at::Tensor wt, c10::optional<at::Tens
 // Expert MLP halves on wave-tiled expert weights wt [E_local, N/32, K/16, 64, 8] (ops.tile_experts). glu: gate_up
 // with fused SwiGLU into y [n_ent, N/2]; else down with the weighted combine into out f32 [T, N]. max_rows = T
 // bounds every expert segment (a token picks an expert at most once).
-static void wstream_grouped(at::Tensor x, at::Tensor wt, at::Tensor perm_tok, at::Tensor perm_w, at::Tensor expert_off,
-                            int64_t e_lo, int64_t max_rows, bool gather, c10::optional<at::Tensor> y,
-                            c10::optional<at::Tensor> out, bool pin) {
-  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_DT(wt, at::kBFloat16); CHECK_LASTDIM(x);
+// st: the fp8 variant (wstream_grouped_w8 below): wt uint8 [E_local, N/32, K/32, 64, 16] and st f32 [E_local, N].
+static void wstream_grouped_impl(at::Tensor x, at::Tensor wt, const at::Tensor* st, at::Tensor perm_tok,
+                                 at::Tensor perm_w, at::Tensor expert_off, int64_t e_lo, int64_t max_rows, bool gather,
+                                 c10::optional<at::Tensor> y, c10::optional<at::Tensor> out, bool pin) {
+  const bool w8 = st != nullptr;
+  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_DT(wt, w8 ? at::kByte : at::kBFloat16); CHECK_LASTDIM(x);
   CHECK_DT(perm_tok, at::kInt); CHECK_DT(perm_w, at::kFloat); CHECK_DT(expert_off, at::kInt);
   TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "wstream_grouped: x must be [rows, K] with 16-B rows");
-  TORCH_CHECK(wt.dim() == 5 && wt.is_contiguous() && wt.size(3) == 64 && wt.size(4) == 8,
-              "wstream_grouped: wt must be contiguous [E_local, N/32, K/16, 64, 8]");
-  const int E_local = wt.size(0), N = wt.size(1) * 32, K = wt.size(2) * 16;
+  TORCH_CHECK(wt.dim() == 5 && wt.is_contiguous() && wt.size(3) == 64 && wt.size(4) == (w8 ? 16 : 8),
+              "wstream_grouped: wt must be contiguous [E_local, N/32, K/16, 64, 8] (fp8: [E_local, N/32, K/32, 64, 16])");
+  const int E_local = wt.size(0), N = wt.size(1) * 32, K = wt.size(2) * (w8 ? 32 : 16);
+  if (w8) {
+    CHECK_DT(*st, at::kFloat);
+    TORCH_CHECK(st->dim() == 2 && st->is_contiguous() && st->size(0) == E_local && st->size(1) == N &&
+                    st->device() == wt.device(),
+                "wstream_grouped_w8: st must be contiguous [E_local, N] on the weights' device");
+  }
   TORCH_CHECK(x.size(1) == K && K % 256 == 0 && N % 64 == 0, "wstream_grouped: K / N");
   const int64_t n_ent = perm_tok.numel();
   TORCH_CHECK(perm_w.numel() == n_ent && perm_tok.is_contiguous() && perm_w.is_contiguous(), "wstream_grouped: perm");
@@ -712,10 +720,30 @@ static void wstream_grouped(at::Tensor x, at::Tensor wt, at::Tensor perm_tok, at
     op = out->data_ptr<float>();
     ldo = out->stride(0);
   }
-  CHECK_HIP(kafka_launch_wstream_grouped(bptr(x), x.stride(0), bptr(wt), E_local, N, K, perm_tok.data_ptr<int>(),
-                                         perm_w.data_ptr<float>(), expert_off.data_ptr<int>(), (int)e_lo,
-                                         (int)max_rows, gather ? 1 : 0, yp, ldy, op, ldo, pin ? 1 : 0,
-                                         cur_stream()));
+  if (w8)
+    CHECK_HIP(kafka_launch_wstream_grouped_w8(bptr(x), x.stride(0), wt.data_ptr<uint8_t>(), st->data_ptr<float>(),
+                                              E_local, N, K, perm_tok.data_ptr<int>(), perm_w.data_ptr<float>(),
+                                              expert_off.data_ptr<int>(), (int)e_lo, (int)max_rows, gather ? 1 : 0,
+                                              yp, ldy, op, ldo, pin ? 1 : 0, cur_stream()));
+  else
+    CHECK_HIP(kafka_launch_wstream_grouped(bptr(x), x.stride(0), bptr(wt), E_local, N, K, perm_tok.data_ptr<int>(),
+                                           perm_w.data_ptr<float>(), expert_off.data_ptr<int>(), (int)e_lo,
+                                           (int)max_rows, gather ? 1 : 0, yp, ldy, op, ldo, pin ? 1 : 0,
+                                           cur_stream()));
+}
+
+static void wstream_grouped(at::Tensor x, at::Tensor wt, at::Tensor perm_tok, at::Tensor perm_w, at::Tensor expert_off,
+                            int64_t e_lo, int64_t max_rows, bool gather, c10::optional<at::Tensor> y,
+                            c10::optional<at::Tensor> out, bool pin) {
+  wstream_grouped_impl(x, wt, nullptr, perm_tok, perm_w, expert_off, e_lo, max_rows, gather, y, out, pin);
+}
+
+// The same on fp8 expert tiles wt8 [E_local, N/32, K/32, 64, 16] with row scales st [E_local, N]
+// (ops.tile_experts_fp8).
+static void wstream_grouped_w8(at::Tensor x, at::Tensor wt8, at::Tensor st, at::Tensor perm_tok, at::Tensor perm_w,
+                               at::Tensor expert_off, int64_t e_lo, int64_t max_rows, bool gather,
+                               c10::optional<at::Tensor> y, c10::optional<at::Tensor> out, bool pin) {
+  wstream_grouped_impl(x, wt8, &st, perm_tok, perm_w, expert_off, e_lo, max_rows, gather, y, out, pin);
 }
 
 // y [M, N] bf16 = sum over the slabs p [S, M, N]
@@ -1005,6 +1033,9 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("wstream_grouped", &wstream_grouped, py::arg("x"), py::arg("wt"), py::arg("perm_tok"), py::arg("perm_w"),
         py::arg("expert_off"), py::arg("e_lo"), py::arg("max_rows"), py::arg("gather"), py::arg("y"), py::arg("out"),
         py::arg("pin") = true);
+  m.def("wstream_grouped_w8", &wstream_grouped_w8, py::arg("x"), py::arg("wt8"), py::arg("st"), py::arg("perm_tok"),
+        py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("max_rows"), py::arg("gather"),
+        py::arg("y"), py::arg("out"), py::arg("pin") = true);
   m.def("moe_route", &moe_route);
   m.def("cu_mask_stream", &cu_mask_stream);
   m.def("stream_cu_mask", &stream_cu_mask);

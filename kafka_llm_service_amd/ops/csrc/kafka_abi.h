@@ -176,6 +176,12 @@ hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, const bf16* 
                                         const int* perm_tok, const float* perm_w, const int* expert_off, int e_lo,
                                         int max_rows, int gather, bf16* Y, int64_t ldy, float* out, int64_t ldo,
                                         int pin, hipStream_t st);
+// fp8 expert weights: Wt8 [E_local][N/32][K/32][64 lanes][16] e4m3 bytes and St [E_local][N] fp32 power-of-two row
+// scales in tile order (ops.tile_experts_fp8), both indexed by the local expert; grid, row tiles and outputs as above
+hipError_t kafka_launch_wstream_grouped_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St,
+                                           int e_local, int N, int K, const int* perm_tok, const float* perm_w,
+                                           const int* expert_off, int e_lo, int max_rows, int gather, bf16* Y,
+                                           int64_t ldy, float* out, int64_t ldo, int pin, hipStream_t st);
 
 // ---- skinny_gemm.hip
 // Split plan for a shape (mirrored by ops.skinny_plan): the fewest power-of-two splits that give >= 192 workgroups

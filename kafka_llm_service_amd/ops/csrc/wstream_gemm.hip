@@ -675,19 +675,33 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
 // (MT = 4: at most 256 registers so two workgroups share a CU — left free the compiler took 316, one wave per SIMD:
 // the 128-row expert tiles streamed 8 % slower, Mixtral 128 threads 5,155 vs 5,234 tok/s, profiles/r06/mixtral/;
 // MT = 2 spills 32+ registers under the same bound and keeps its 324)
-template <int MT, int KC, bool GATHER, bool COMBINE, bool PIN>
+//
+// W8 (fp8 expert weights, ops.tile_experts_fp8): Wt is the e4m3 image Wt8[E_local][N/32][K/32][64][16 B] of the dense
+// W8 kernel per expert and St[E_local][N] the power-of-two row scales in tile order, both indexed by the LOCAL expert
+// (expert_off by e_lo + el). A wave loads KSTEP / 2 vectors per chunk, keeps raw fp8 in wa / wb and dequantises each
+// vector right before its two k-steps' MFMAs (dq8, the row scale being the conversion's scale operand), so the
+// accumulators hold true values and the X stage, the MT = 4 rule and both epilogues are the bf16 kernel's. St is a
+// trailing argument whose type depends on W8 — an empty struct for bf16, which never reads it: the 24 bf16
+// instantiations compile to the register counts they had without W8 (profiles/wfp8_moe/resource_usage.txt).
+struct NoScales {};
+template <int MT, int KC, bool GATHER, bool COMBINE, bool PIN, bool W8 = false>
 __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(const bf16* __restrict__ X, int64_t ldx,
                                                                const bf16x8* __restrict__ Wt, int N, int K,
                                                                const int* __restrict__ perm_tok,
                                                                const float* __restrict__ perm_w,
                                                                const int* __restrict__ expert_off, int e_lo,
                                                                bf16* __restrict__ Y, int64_t ldy,
-                                                               float* __restrict__ out, int64_t ldo) {
+                                                               float* __restrict__ out, int64_t ldo,
+                                                               typename std::conditional<W8, const float*,
+                                                                                         NoScales>::type St) {
   constexpr int ROWS = 32 * MT;
   constexpr int CPR = KC / 8;
   constexpr int XL = ROWS * CPR / 256;
   constexpr int KSTEP = KC / 16;
+  constexpr int KSV = W8 ? KSTEP / 2 : KSTEP;  // 16-B weight vectors per chunk (W8: two k-steps each)
+  typedef typename std::conditional<W8, u32x4, bf16x8>::type wvec;
   static_assert(CPR >= 16 && XL >= 1, "chunk too small");
+  static_assert(!W8 || KSTEP % 2 == 0, "fp8 tiles hold k-step pairs");
   __shared__ __attribute__((aligned(16))) bf16 xs[2][ROWS * KC];
   const int el = blockIdx.y, e = e_lo + el;
   const int seg0 = expert_off[e];
@@ -699,7 +713,13 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
   const int r = lane & 31, h = lane >> 5;
   const int nb = blockIdx.x * 4 + w;
   const bool active = nb < (N >> 5);
-  const bf16x8* wp = Wt + ((int64_t)el * (N >> 5) + (active ? nb : (N >> 5) - 1)) * (K >> 4) * 64 + lane;
+  // (an inactive tail wave streams the last tile, and reads its scales; both layouts: K / 16 bf16 or K / 32 fp8
+  // vectors of 64 lanes x 16 B per tile row)
+  const int nbl = active ? nb : (N >> 5) - 1;
+  const wvec* wp =
+      reinterpret_cast<const wvec*>(Wt) + ((int64_t)el * (N >> 5) + nbl) * (W8 ? K >> 5 : K >> 4) * 64 + lane;
+  float wsc = 1.f;  // W8: 2^e of this lane's weight row
+  if constexpr (W8) wsc = St[(int64_t)el * N + 32 * nbl + r];
   const int nchunks = K / KC;
 
   // A-row sources of this thread's staged chunks (fixed over K)
@@ -725,9 +745,9 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
       *reinterpret_cast<bf16x8*>(&xs[buf][row * KC + 8 * (c ^ (row & 15))]) = xr[i];
     }
   };
-  auto load_w = [&](bf16x8(&wv)[KSTEP], int ch) {
+  auto load_w = [&](wvec(&wv)[KSV], int ch) {
 #pragma unroll
-    for (int t = 0; t < KSTEP; ++t) wv[t] = __builtin_nontemporal_load(wp + (int64_t)(ch * KSTEP + t) * 64);
+    for (int t = 0; t < KSV; ++t) wv[t] = __builtin_nontemporal_load(wp + (int64_t)(ch * KSV + t) * 64);
     if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);  // (prefetch kept ahead of the MFMAs, as wstream_gemm)
   };
   const int mt_used = (rows + 31) >> 5;  // row tiles with live rows (uniform)
@@ -736,9 +756,17 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[mt][i] = 0.f;
-  auto compute = [&](int buf, const bf16x8(&wv)[KSTEP]) {
+  auto compute = [&](int buf, const wvec(&wv)[KSV]) {
 #pragma unroll
     for (int t = 0; t < KSTEP; ++t) {
+      bf16x8 wf;
+      if constexpr (W8) {
+        // dequantised right before its MFMAs: the prefetch registers keep the raw fp8
+        const u32x4 v = wv[t >> 1];
+        wf = (t & 1) ? dq8(v[2], v[3], wsc) : dq8(v[0], v[1], wsc);
+      } else {
+        wf = wv[t];
+      }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         // MT = 4 computes every row tile (rows past the segment hold a valid row, never stored): with the MFMAs of
@@ -748,12 +776,12 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
         if (MT == 4 || mt < mt_used) {
           const int m = mt * 32 + r, c = 2 * t + h;
           const bf16x8 xf = *reinterpret_cast<const bf16x8*>(&xs[buf][m * KC + 8 * (c ^ (m & 15))]);
-          acc[mt] = mfma32(xf, wv[t], acc[mt]);
+          acc[mt] = mfma32(xf, wf, acc[mt]);
         }
       }
     }
   };
-  bf16x8 wa[KSTEP], wb[KSTEP];
+  wvec wa[KSV], wb[KSV];
   load_x(0);
   load_w(wa, 0);
   store_x(0);
@@ -1041,6 +1069,8 @@ namespace kafka {
 // Grouped streaming GEMM for the expert MLP (see wstream_grouped_kernel). max_rows bounds any expert's segment
 // (the token count T: a token picks an expert at most once); glu: gate_up with fused SwiGLU into Y [n_ent, N/2];
 // else combine into out_f32 [T, N].
+static int grouped_mt(int max_rows) { return max_rows <= 32 ? 1 : (max_rows <= 192 ? 2 : 4); }
+
 extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, const bf16* Wt, int e_local, int N,
                                                   int K, const int* perm_tok, const float* perm_w,
                                                   const int* expert_off, int e_lo, int max_rows, int gather,
@@ -1054,7 +1084,7 @@ extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, c
   // (64-row tiles stay below 193 rows: an expert then rarely fills a second tile, and they stream faster there —
   // benchmarks/moe_bench.py T = 128 / 192: 493 / 522 vs 517 / 551 us per layer; T = 256 / 384 / 512: 761 / 1002 /
   // 1303 vs 601 / 691 / 1004, profiles/r06/mixtral/)
-  const int MT = max_rows <= 32 ? 1 : (max_rows <= 192 ? 2 : 4);
+  const int MT = grouped_mt(max_rows);
   const dim3 grid((N + 127) / 128, e_local, (max_rows + 32 * MT - 1) / (32 * MT));
   const auto* wt = reinterpret_cast<const bf16x8*>(Wt);
 #define KAFKA_WG(MT_, G_, C_)                                                                                   \
@@ -1062,10 +1092,10 @@ extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, c
     constexpr int KC_ = MT_ == 4 ? 128 : 256;                                                                  \
     if (pin)                                                                                                   \
       wstream_grouped_kernel<MT_, KC_, G_, C_, true><<<grid, 256, 0, st>>>(X, ldx, wt, N, K, perm_tok, perm_w,      \
-                                                                           expert_off, e_lo, Y, ldy, out, ldo);  \
+                                                                           expert_off, e_lo, Y, ldy, out, ldo, NoScales{});  \
     else                                                                                                       \
       wstream_grouped_kernel<MT_, KC_, G_, C_, false><<<grid, 256, 0, st>>>(X, ldx, wt, N, K, perm_tok, perm_w,     \
-                                                                            expert_off, e_lo, Y, ldy, out, ldo); \
+                                                                            expert_off, e_lo, Y, ldy, out, ldo, NoScales{}); \
   } while (0)
   const bool comb = out != nullptr;
   if (MT == 1) {
@@ -1079,6 +1109,44 @@ extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, c
     else { if (comb) KAFKA_WG(4, false, true); else KAFKA_WG(4, false, false); }
   }
 #undef KAFKA_WG
+  return hipGetLastError();
+}
+
+// fp8 expert weights: Wt8 [E_local][N/32][K/32][64][16] e4m3 bytes, St [E_local][N] fp32 row scales in tile order
+// (ops.tile_experts_fp8). Same grid, MT choice and outputs as kafka_launch_wstream_grouped.
+extern "C" hipError_t kafka_launch_wstream_grouped_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St,
+                                                     int e_local, int N, int K, const int* perm_tok,
+                                                     const float* perm_w, const int* expert_off, int e_lo,
+                                                     int max_rows, int gather, bf16* Y, int64_t ldy, float* out,
+                                                     int64_t ldo, int pin, hipStream_t st) {
+  if (max_rows < 1 || e_local < 1) return hipSuccess;
+  if (N % 64 != 0 || K % 256 != 0 || (out == nullptr) == (Y == nullptr) || Wt8 == nullptr || St == nullptr)
+    return hipErrorInvalidValue;
+  const int MT = grouped_mt(max_rows);
+  const dim3 grid((N + 127) / 128, e_local, (max_rows + 32 * MT - 1) / (32 * MT));
+  const auto* wt = reinterpret_cast<const bf16x8*>(Wt8);
+#define KAFKA_WG8(MT_, G_, C_)                                                                                  \
+  do {                                                                                                         \
+    constexpr int KC_ = MT_ == 4 ? 128 : 256;                                                                  \
+    if (pin)                                                                                                   \
+      wstream_grouped_kernel<MT_, KC_, G_, C_, true, true><<<grid, 256, 0, st>>>(                                 \
+          X, ldx, wt, N, K, perm_tok, perm_w, expert_off, e_lo, Y, ldy, out, ldo, St);                         \
+    else                                                                                                       \
+      wstream_grouped_kernel<MT_, KC_, G_, C_, false, true><<<grid, 256, 0, st>>>(                                \
+          X, ldx, wt, N, K, perm_tok, perm_w, expert_off, e_lo, Y, ldy, out, ldo, St);                         \
+  } while (0)
+  const bool comb = out != nullptr;
+  if (MT == 1) {
+    if (gather) { if (comb) KAFKA_WG8(1, true, true); else KAFKA_WG8(1, true, false); }
+    else { if (comb) KAFKA_WG8(1, false, true); else KAFKA_WG8(1, false, false); }
+  } else if (MT == 2) {
+    if (gather) { if (comb) KAFKA_WG8(2, true, true); else KAFKA_WG8(2, true, false); }
+    else { if (comb) KAFKA_WG8(2, false, true); else KAFKA_WG8(2, false, false); }
+  } else {
+    if (gather) { if (comb) KAFKA_WG8(4, true, true); else KAFKA_WG8(4, true, false); }
+    else { if (comb) KAFKA_WG8(4, false, true); else KAFKA_WG8(4, false, false); }
+  }
+#undef KAFKA_WG8
   return hipGetLastError();
 }
 }  // namespace kafka

@@ -98,6 +98,29 @@ def untile_weight_fp8(wt8: torch.Tensor, st: torch.Tensor, glu: bool = False) ->
     return w.to(torch.bfloat16)
 
 
+def tile_experts_fp8(w: torch.Tensor, glu: bool = False):
+    """Expert weights [E, N, K] -> (wt8 uint8 [E, N/32, K/32, 64, 16], st fp32 [E, N]): ``tile_weight_fp8`` per expert
+    (every row of every expert quantised over its whole K, scales in tile order, ``glu`` the gate / up tile interleave
+    of ``tile_experts``), for the grouped fp8 streaming kernel (csrc/wstream_gemm.hip, W8 grouped variant)."""
+    E, N, K = w.shape
+    wt8 = torch.empty(E, N // 32, K // 32, 64, 16, dtype=torch.uint8, device=w.device)
+    st = torch.empty(E, N, dtype=torch.float32, device=w.device)
+    for e in range(E):
+        t, s = tile_weight_fp8(w[e], glu)
+        wt8[e].copy_(t)
+        st[e].copy_(s)
+    return wt8, st
+
+
+def untile_experts_fp8(wt8: torch.Tensor, st: torch.Tensor, glu: bool = False) -> torch.Tensor:
+    """The dequantised row-major experts of fp8 expert tiles: bf16 [E, N, K], exact (``untile_weight_fp8``)."""
+    E = wt8.shape[0]
+    out = torch.empty(E, wt8.shape[1] * 32, wt8.shape[2] * 32, dtype=torch.bfloat16, device=wt8.device)
+    for e in range(E):
+        out[e].copy_(untile_weight_fp8(wt8[e], st[e], glu))
+    return out
+
+
 def fp8_dequant_pages(k_pages: torch.Tensor, v_pages: torch.Tensor):
     """fp8 pages (K [n, Hkv, 16D + 32], V [n, Hkv, 16D] uint8) -> fp32 K [n, Hkv, 16, D] and V [n, Hkv, D, 16]
     (V in natural key order)."""
