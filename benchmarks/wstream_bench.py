@@ -6,7 +6,8 @@ The streaming kernel's time includes what its consumer pays to combine split-K s
 (the engine never runs that reduce: rope_kv / SwiGLU / add+RMSNorm sum the slabs while loading). Each case is a fresh
 weight buffer larger than the Infinity Cache rotation (cold HBM reads, like one layer of a real step).
 ``--weight-dtype fp8`` streams e4m3 tiles (ops.tile_weight_fp8; hipBLASLt then runs on the dequantised bf16 weight,
-and TB/s counts the fp8 bytes actually streamed). One JSON line per (shape, M)."""
+and TB/s counts the fp8 bytes actually streamed); ``--weight-dtype mxfp4`` the same with MXFP4 tiles and their e8m0
+block-scale image (ops.tile_weight_mxfp4). One JSON line per (shape, M)."""
 from __future__ import annotations
 
 import argparse
@@ -47,9 +48,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--M", default="1,16,64,128")
     ap.add_argument("--shapes", default=",".join(SHAPES))
-    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"])
     args = ap.parse_args()
     fp8 = args.weight_dtype == "fp8"
+    mxfp4 = args.weight_dtype == "mxfp4"
     dev = torch.device("cuda:0")
     for name in args.shapes.split(","):
         N, K = SHAPES[name]
@@ -61,6 +63,11 @@ def main():
             ws = [ops.untile_weight_fp8(wt, st) for wt, st in wts]
             stream = lambda x, t, **kw: ops.linear_stream(x, t[0], scale=t[1], **kw)
             sbytes = N * K + 4 * N
+        elif mxfp4:  # (tiles, block-scale image); ws the dequantised weights, as for fp8
+            wts = [ops.tile_weight_mxfp4(w) for w in ws]
+            ws = [ops.untile_weight_mxfp4(wt, se) for wt, se in wts]
+            stream = lambda x, t, **kw: ops.linear_stream(x, t[0], scale=t[1], **kw)
+            sbytes = N * K // 2 + N * K // 32
         else:
             wts = [ops.tile_weight(w) for w in ws]
             stream = lambda x, t, **kw: ops.linear_stream(x, t, **kw)

@@ -68,8 +68,10 @@ class EngineConfig:
     # dense projections, lm_head and MoE experts: "bf16", or "fp8" = e4m3 wave tiles with one power-of-two scale per
     # output row (half the bytes of every decode GEMM and of the tiled copy; the row-major weights become the dequantised
     # values, so every path and the oracle run the same quantised model; models/llama.py enable_stream_weights).
-    # Needs the streaming decode GEMM (auto resolves to stream); env KAFKA_WEIGHT_DTYPE overrides
-    weight_dtype: str = "bf16"          # bf16 | fp8
+    # "mxfp4" = OCP MXFP4 wave tiles of the dense projections and the lm_head (e2m1 in 32-column blocks along K, one
+    # e8m0 exponent per block: 4.25 bits per weight; same semantics; MoE experts keep bf16 tiles).
+    # fp8 and mxfp4 need the streaming decode GEMM (auto resolves to stream); env KAFKA_WEIGHT_DTYPE overrides
+    weight_dtype: str = "bf16"          # bf16 | fp8 | mxfp4
     async_scheduling: bool = True       # plan step n+1 on the host while step n runs on the GPU
     # Mixtral data-parallel attention (engine/dp_attention.py): this rank serves its own sequences with whole
     # attention weights; experts are sharded over parallel.state's EP group and every step runs in lockstep with
@@ -138,14 +140,14 @@ class LLMEngine:
                                           dp_attention=dpa)
         mode = os.environ.get("KAFKA_DECODE_GEMM", cfg.decode_gemm)
         wdt = os.environ.get("KAFKA_WEIGHT_DTYPE") or cfg.weight_dtype
-        if wdt not in ("bf16", "fp8"):
-            raise ValueError(f"weight_dtype must be bf16 or fp8, not {wdt!r}")
-        if wdt == "fp8" and mode == "blas":
-            raise ValueError("weight_dtype='fp8' needs the weight-streaming decode GEMM (decode_gemm auto | stream | "
+        if wdt not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype must be bf16, fp8 or mxfp4, not {wdt!r}")
+        if wdt != "bf16" and mode == "blas":
+            raise ValueError(f"weight_dtype={wdt!r} needs the weight-streaming decode GEMM (decode_gemm auto | stream | "
                              "stream_only), not 'blas'")
         if mode == "auto":
-            # fp8 weights live in the streaming kernel's tiles on any device (the CPU runs the reference path)
-            mode = "stream" if self.device.type == "cuda" or wdt == "fp8" else "blas"
+            # quantised weights live in the streaming kernel's tiles on any device (the CPU runs the reference path)
+            mode = "stream" if self.device.type == "cuda" or wdt != "bf16" else "blas"
         if self.model.stream and self.model.weight_dtype != wdt:
             raise ValueError(f"the model's streamed weights are {self.model.weight_dtype}, the engine asks for {wdt}")
         cfg.weight_dtype = wdt

@@ -79,7 +79,7 @@ class StepInput:
 class LayerWeights:
     __slots__ = ("input_norm", "post_norm", "qkv", "o", "gate_up", "down", "router", "w13", "w2", "expert_ids",
                  "qkv_t", "o_t", "gate_up_t", "down_t", "glu", "w13_t", "w2_t",
-                 "qkv_s", "o_s", "gate_up_s", "down_s",  # _s: fp32 row scales of fp8 tiles (weight_dtype="fp8")
+                 "qkv_s", "o_s", "gate_up_s", "down_s",  # _s: fp32 row scales of fp8 tiles / e8m0 image of mxfp4 tiles
                  "w13_s", "w2_s")
     STREAMED = ("qkv", "o", "gate_up", "down")  # projections with a wave-tiled copy for the decode GEMM
 
@@ -118,7 +118,7 @@ class TransformerLM:
         self.scale = self.D ** -0.5
         self.moe = None
         self.lm_head_t = None
-        self.lm_head_s = None  # row scales of fp8 lm_head tiles
+        self.lm_head_s = None  # row scales of fp8 lm_head tiles / block-scale image of mxfp4 ones
         self.weight_dtype = "bf16"  # of the streamed projections and the lm_head (enable_stream_weights)
         self.stream = False  # decode GEMMs on the weight-streaming kernel (enable_stream_weights)
         self.tiled_only = False  # row-major dense weights dropped (enable_stream_weights(tiled_only=True))
@@ -145,10 +145,13 @@ class TransformerLM:
     def stream_weight_bytes(self, weight_dtype: str = "bf16") -> int:
         """Bytes enable_stream_weights would add (the wave-tiled copies; 0 in tiled-only mode). ``"fp8"``: one byte
         per element plus a 4-byte scale per row for the dense projections, the lm_head and the MoE experts (a scale
-        per row of every expert)."""
-        def tiled(w):
+        per row of every expert). ``"mxfp4"``: half a byte per element plus one exponent byte per 32 (4.25 bits) for the
+        dense projections and the lm_head; the MoE experts keep bf16 tiles."""
+        def tiled(w, dense=True):
             if weight_dtype == "fp8":
                 return w.numel() + 4 * (w.numel() // w.shape[-1])
+            if weight_dtype == "mxfp4" and dense:
+                return w.numel() // 2 + w.numel() // 32
             return w.numel() * w.element_size()
 
         n = 0
@@ -160,7 +163,7 @@ class TransformerLM:
             for name in ("w13", "w2"):
                 w = getattr(lw, name)
                 if w is not None and ops.stream_moe_supported(w.shape[1], w.shape[2]):
-                    n += tiled(w)
+                    n += tiled(w, dense=False)
         if self.lm_head is not None and ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
             n += tiled(self.lm_head)
         return n
@@ -186,14 +189,28 @@ class TransformerLM:
         [E_local, N]; every expert-parallel rank quantises its own whole experts, rows over their whole K, so a rank's
         tiles equal the matching slice of the unsharded model's) and row-major ``w13`` / ``w2`` become the dequantised
         experts that ``ops.grouped_gemm`` runs on prefill-sized steps. Embedding, norms and router stay bf16; the
-        skinny GEMM and the fused decode layer do not take fp8 tiles (hipBLASLt / the unfused layer run)."""
-        if weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"weight_dtype must be bf16 or fp8, not {weight_dtype!r}")
+        skinny GEMM and the fused decode layer do not take fp8 tiles (hipBLASLt / the unfused layer run).
+
+        ``weight_dtype="mxfp4"``: the tiles of the dense projections and the lm_head are OCP MXFP4 — e2m1 elements in
+        32-column blocks along K with one e8m0 exponent per block (ops.tile_weight_mxfp4: ``<name>_t``
+        float4_e2m1fn_x2, ``<name>_s`` the float8_e8m0fnu block-scale image), 4.25 bits per weight. Semantics and
+        exclusions are fp8's: the row-major tensors become the dequantised values (e2m1 * 2^e, exact in bf16), so every
+        step size, export and the oracle see one quantised model; no skinny GEMM, fused decode layer or overlapped TP
+        seam. Blocks run along K and every rank quantises its own shard, so a row-parallel shard cut on a multiple of
+        64 columns has exactly the matching slice of the unsharded model's tiles. The MoE experts keep bf16 tiles in
+        this mode (attention projections and the lm_head are quantised)."""
+        if weight_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype must be bf16, fp8 or mxfp4, not {weight_dtype!r}")
         fp8 = weight_dtype == "fp8"
+        mxfp4 = weight_dtype == "mxfp4"
         added = 0
 
         def tile(w, glu=False):
             """(tiles, scales or None, row-major tensor to keep, bytes of the tiled copy)"""
+            if mxfp4:
+                wt, se = ops.tile_weight_mxfp4(w, glu=glu)
+                keep = None if tiled_only else ops.untile_weight_mxfp4(wt, se, glu=glu)
+                return wt, se, keep, wt.numel() + se.numel()
             if not fp8:
                 wt = ops.tile_weight(w, glu=glu)
                 return wt, None, w, wt.numel() * wt.element_size()
@@ -253,12 +270,12 @@ class TransformerLM:
     def _linear(self, x: torch.Tensor, w: torch.Tensor, wt: torch.Tensor | None, max_splits: int = 8,
                 kind: str = "", st: torch.Tensor | None = None):
         """x @ w^T: the weight-streaming kernel for decode-sized x (bf16 or a split-K slab out), the skinny MFMA GEMM
-        for 129..256 rows of the projections in SKINNY (bf16 tiles only), else hipBLASLt. ``st``: fp8 tiles' scales."""
+        for 129..256 rows of the projections in SKINNY (bf16 tiles only), else hipBLASLt. ``st``: fp8 / mxfp4 tiles' scales."""
         M = x.shape[0]
         if self.stream and wt is not None:
             if 0 < M <= self.stream_max_m:
                 return ops.linear_stream(x, wt, max_splits, scale=st)
-            if kind in SKINNY and not ops.is_fp8_weight(wt) and \
+            if kind in SKINNY and wt.dtype == torch.bfloat16 and \
                     ops.skinny_plan(M, wt.shape[0] * 32, x.shape[1], max_splits):
                 return ops.linear_skinny(x, wt, max_splits)
         return F.linear(x, self._dense(w, wt, st=st))
@@ -267,14 +284,16 @@ class TransformerLM:
     def _dense(w: torch.Tensor | None, wt: torch.Tensor | None, glu: bool = False,
                st: torch.Tensor | None = None) -> torch.Tensor:
         """The row-major weight for hipBLASLt: the stored one, or (tiled-only mode) a transient untiled copy —
-        dequantised for fp8 tiles (``st`` their scales)."""
+        dequantised for fp8 and mxfp4 tiles (``st`` their scales)."""
         if w is not None:
             return w
+        if ops.is_mxfp4_weight(wt):
+            return ops.untile_weight_mxfp4(wt, st, glu=glu)
         return ops.untile_weight_fp8(wt, st, glu=glu) if ops.is_fp8_weight(wt) else ops.untile_weight(wt, glu=glu)
 
     def dense_weight(self, lw: LayerWeights | None, name: str) -> torch.Tensor:
         """Row-major [N, K] weight of a streamed projection of ``lw`` (or of "lm_head" with lw = None) in either
-        mode: the stored tensor, or the untiled (fp8: dequantised) tiles of a tiled-only model — what export and the
+        mode: the stored tensor, or the untiled (fp8 / mxfp4: dequantised) tiles of a tiled-only model — what export and the
         dense oracle read."""
         if lw is None:
             return self._dense(self.lm_head, self.lm_head_t, st=self.lm_head_s)
@@ -337,7 +356,7 @@ class TransformerLM:
             if self.stream and lw.glu and 0 < T <= self.stream_max_m:
                 a = ops.linear_glu(x, lw.gate_up_t, scale=lw.gate_up_s)  # SwiGLU in the GEMM epilogue (or on its slabs)
             elif (self.stream and lw.glu and "gate_up" in SKINNY and lw.gate_up_t is not None
-                  and not ops.is_fp8_weight(lw.gate_up_t) and ops.skinny_plan(T, lw.gate_up_t.shape[0] * 32, x.shape[1])):
+                  and lw.gate_up_t.dtype == torch.bfloat16 and ops.skinny_plan(T, lw.gate_up_t.shape[0] * 32, x.shape[1])):
                 a = ops.linear_skinny(x, lw.gate_up_t, glu=True)  # fused SwiGLU (one split) or gate | up slabs
                 if ops.is_slab(a):
                     a = ops.silu_mul(a)
@@ -372,7 +391,8 @@ class TransformerLM:
         copy, the KV cache is bf16 with 128-dim heads and the shapes fit the fused epilogues."""
         if not (FUSED and self.stream and self.tp == 1 and not self.dp_attention and 0 < T <= self.stream_max_m):
             return False
-        if self.weight_dtype != "bf16" or ops.is_fp8_weight(self.layers[0].qkv_t):
+        qkv_t = self.layers[0].qkv_t
+        if self.weight_dtype != "bf16" or (qkv_t is not None and qkv_t.dtype != torch.bfloat16):
             return False  # the fused epilogues read bf16 tiles only
         if self._fused_shapes is None:
             lw0 = self.layers[0]
@@ -436,7 +456,7 @@ class TransformerLM:
     def _can_overlap(self, T: int, wt: torch.Tensor | None) -> bool:
         if not (TP_OVERLAP and self.stream and wt is not None and 0 < T <= self.stream_max_m and self.device.type == "cuda"):
             return False
-        if ops.is_fp8_weight(wt):
+        if wt.dtype != torch.bfloat16:
             return False  # (the overlapped seam slices bf16 tiles)
         car = pstate.custom_ar()
         return car is not None and wt.shape[0] % 2 == 0 and T * wt.shape[0] * 32 * 2 <= car.max_bytes

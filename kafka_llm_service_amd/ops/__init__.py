@@ -310,9 +310,31 @@ def is_fp8_weight(wt: torch.Tensor | None) -> bool:
     return wt is not None and wt.dtype == torch.uint8
 
 
+# MXFP4 weights (weight_dtype="mxfp4"): e2m1 wave tiles float4_e2m1fn_x2 [N/32, K/64, 64, 16] plus the e8m0 block-scale
+# image float8_e8m0fnu [N/32, K/64, 32, 2] (layout and quantisation rule: reference.tile_weight_mxfp4 / mxfp4_quant);
+# linear_stream / linear_glu take them with ``scale``. The tile dtype tells the three formats apart.
+mxfp4_quant = ref.mxfp4_quant
+tile_weight_mxfp4 = ref.tile_weight_mxfp4
+untile_weight_mxfp4 = ref.untile_weight_mxfp4
+
+
+_F4 = torch.float4_e2m1fn_x2
+
+
+def is_mxfp4_weight(wt: torch.Tensor | None) -> bool:
+    return wt is not None and wt.dtype == _F4
+
+
 def tiled_dims(wt: torch.Tensor) -> tuple[int, int]:
-    """(N, K) of a wave-tiled weight: bf16 tiles [N/32, K/16, 64, 8] or fp8 tiles [N/32, K/32, 64, 16]."""
-    return wt.shape[0] * 32, wt.shape[1] * (32 if wt.dtype == torch.uint8 else 16)
+    """(N, K) of a wave-tiled weight: bf16 tiles [N/32, K/16, 64, 8], fp8 tiles [N/32, K/32, 64, 16] or MXFP4 tiles
+    [N/32, K/64, 64, 16]."""
+    return wt.shape[0] * 32, wt.shape[1] * (64 if is_mxfp4_weight(wt) else (32 if wt.dtype == torch.uint8 else 16))
+
+
+def _refuse_quantised(fn: str, wt: torch.Tensor) -> None:
+    """The kernels behind ``fn`` read bf16 tiles only: quantised ones are refused instead of misread (the callers test
+    the dtype inline: they sit on the decode step's host path)."""
+    raise ValueError(f"{fn}: takes bf16 weight tiles only, not {wt.dtype} tiles (use linear_stream / linear_glu)")
 
 
 # Steps of up to this many rows run the dense projections on the weight-streaming kernel (csrc/wstream_gemm.hip).
@@ -357,6 +379,8 @@ def skinny_plan(M: int, N: int, K: int, max_splits: int = 8) -> int:
 def linear_skinny(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bool = False) -> torch.Tensor:
     """y = x @ W^T for 129..256 rows from the wave-tiled weight (mixed decode + prefill steps): bf16 [M, N] (or the
     activated [M, N/2] with ``glu``) for one split, else fp32 split-K slabs [S, M, N] in gate | up order for glu."""
+    if wt.dtype != torch.bfloat16:
+        _refuse_quantised("linear_skinny", wt)
     M, K = x.shape
     N = wt.shape[0] * 32
     S = skinny_plan(M, N, K, max_splits)
@@ -385,9 +409,21 @@ def linear_stream(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, nt: bo
     Returns bf16 [M, N] when the plan has one split, else the fp32 split-K slabs [S, M, N] (a slab; the consumer
     kernels sum it while loading). ``glu`` (wt tiled with glu=True): a one-split plan returns the ACTIVATED
     silu(gate) * up [M, N/2] (fused epilogue); a split plan returns gate | up slabs as usual (see ``linear_glu``).
-    fp8 tiles (uint8 ``wt`` from ``tile_weight_fp8``) need their row scales ``scale``; same plans and outputs."""
+    fp8 tiles (uint8 ``wt`` from ``tile_weight_fp8``) need their row scales ``scale``, MXFP4 tiles (``tile_weight_mxfp4``)
+    their e8m0 block-scale image; same plans and outputs."""
     M, K = x.shape
     w8 = wt.dtype == torch.uint8
+    w4 = wt.dtype == _F4
+    if w4:
+        if scale is None:
+            raise ValueError("linear_stream: mxfp4 weight tiles need their block-scale image (scale=)")
+        if scale.dtype != torch.float8_e8m0fnu or tuple(scale.shape) != (wt.shape[0], wt.shape[1], 32, 2):
+            raise ValueError(f"linear_stream: the scale of mxfp4 tiles {tuple(wt.shape)} must be their float8_e8m0fnu "
+                             f"image [N/32, K/64, 32, 2], not {scale.dtype} {tuple(scale.shape)}")
+        if not nt:
+            raise ValueError("linear_stream: mxfp4 weight tiles stream non-temporally only (nt=False unsupported)")
+        if wt.shape[1] * 64 != K:
+            raise ValueError(f"linear_stream: x has K={K}, the mxfp4 tiles K={wt.shape[1] * 64}")
     if w8:
         if scale is None:
             raise ValueError("linear_stream: fp8 weight tiles need their row scales (scale=)")
@@ -406,12 +442,17 @@ def linear_stream(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, nt: bo
             y = torch.empty(M, N // 2 if glu else N, dtype=x.dtype, device=x.device)
         else:
             p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        if w8:
+        if w4:  # (the extension takes the raw bytes of both images)
+            ext().wstream_gemm_w4(x, wt.view(torch.uint8), scale.view(torch.uint8), y, p, int(max_splits), bool(glu))
+        elif w8:
             ext().wstream_gemm_w8(x, wt, scale, y, p, int(max_splits), bool(glu))
         else:
             ext().wstream_gemm(x, wt, y, p, int(max_splits), bool(nt), bool(glu))
         return y if S == 1 else p
-    w = (untile_weight_fp8(wt, scale, glu) if w8 else untile_weight(wt, glu)).float()
+    if w4:
+        w = untile_weight_mxfp4(wt, scale, glu).float()
+    else:
+        w = (untile_weight_fp8(wt, scale, glu) if w8 else untile_weight(wt, glu)).float()
     xf = x.float()
     if S == 1:
         y = xf @ w.t()
@@ -425,7 +466,8 @@ def linear_stream(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, nt: bo
 def linear_glu(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8,
                scale: torch.Tensor | None = None) -> torch.Tensor:
     """silu(x @ Wg^T) * (x @ Wu^T) from GLU-tiled gate_up weights: fused into the GEMM epilogue when the plan has one
-    split, else the GEMM's slabs go through silu_mul. ``scale``: the row scales of fp8 tiles."""
+    split, else the GEMM's slabs go through silu_mul. ``scale``: the row scales of fp8 tiles / the block-scale image of
+    MXFP4 tiles."""
     N = wt.shape[0] * 32
     plan = stream_plan(x.shape[0], N, x.shape[1], max_splits)
     y = linear_stream(x, wt, max_splits, glu=True, scale=scale)
@@ -514,6 +556,8 @@ def linear_res(x: torch.Tensor, wt: torch.Tensor, resid: torch.Tensor, nw: torch
                ss_out: torch.Tensor, max_splits: int = 8, pool: str = "fin") -> None:
     """resid <- bf16(resid + x @ W^T) in place; xn <- bf16(resid * nw); ss_out[cb, m] = sum of resid[m, 128 cb:+128]^2
     (the o / down projection with the residual add and the next RMSNorm's producer half, csrc FIN_RES)."""
+    if wt.dtype != torch.bfloat16:
+        _refuse_quantised("linear_res", wt)
     N = wt.shape[0] * 32
     if _gpu(x):
         S, p = _fin_scratch(x, N, max_splits)
@@ -534,6 +578,8 @@ def linear_qkv_rope(x: torch.Tensor, wt: torch.Tensor, ss_in: torch.Tensor | Non
                     pool: str = "fin_qkv") -> None:
     """RoPE + paged KV write of r * (x @ Wqkv^T) (r: the deferred RMSNorm of x from ``ss_in``, or 1), in the QKV
     GEMM's split-K finisher (csrc FIN_ROPE); bf16 caches, head dim 128."""
+    if wt.dtype != torch.bfloat16:
+        _refuse_quantised("linear_qkv_rope", wt)
     N = wt.shape[0] * 32
     M, K = x.shape
     if _gpu(x):
@@ -551,6 +597,8 @@ def linear_qkv_rope(x: torch.Tensor, wt: torch.Tensor, ss_in: torch.Tensor | Non
 
 def linear_glu_rs(x: torch.Tensor, wt: torch.Tensor, ss_in: torch.Tensor | None, eps: float) -> torch.Tensor:
     """silu(r g) * (r u) with [g | u] = x @ Wgu^T from GLU-tiled weights, one split (csrc FIN_GLU); r as above."""
+    if wt.dtype != torch.bfloat16:
+        _refuse_quantised("linear_glu_rs", wt)
     N = wt.shape[0] * 32
     M, K = x.shape
     if _gpu(x):

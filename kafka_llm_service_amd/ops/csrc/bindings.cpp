@@ -510,6 +510,46 @@ static void wstream_gemm_w8(at::Tensor x, at::Tensor wt8, at::Tensor st, c10::op
                                          mt, kc, s, kw, pin, glu ? 1 : 0, yp, ldy, pp, cur_stream()));
 }
 
+// The same GEMM on MXFP4 weights, both images as raw bytes: wt4 [N/32, K/64, 64, 16] e2m1 nibble pairs and se
+// [N/32, K/64, 32, 2] e8m0 block exponents (ops.tile_weight_mxfp4, viewed as uint8). Same plan, outputs and kw / pin
+// rules as wstream_gemm.
+static void wstream_gemm_w4(at::Tensor x, at::Tensor wt4, at::Tensor se, c10::optional<at::Tensor> y,
+                            c10::optional<at::Tensor> p, int64_t max_splits, bool glu) {
+  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_CUDA(wt4); CHECK_DT(wt4, at::kByte); CHECK_CUDA(se);
+  CHECK_DT(se, at::kByte); CHECK_LASTDIM(x);
+  TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "wstream_gemm_w4: x must be [M, K] with 16-B rows");
+  TORCH_CHECK(wt4.dim() == 4 && wt4.is_contiguous() && wt4.size(2) == 64 && wt4.size(3) == 16,
+              "wstream_gemm_w4: wt4 must be contiguous [N/32, K/64, 64, 16]");
+  const int M = x.size(0), K = x.size(1), N = wt4.size(0) * 32;
+  TORCH_CHECK(K % 64 == 0 && wt4.size(1) * 64 == K, "wstream_gemm_w4: K mismatch (K % 64 == 0)");
+  TORCH_CHECK(se.dim() == 4 && se.is_contiguous() && se.size(0) == wt4.size(0) && se.size(1) == wt4.size(1) &&
+                  se.size(2) == 32 && se.size(3) == 2,
+              "wstream_gemm_w4: se must be contiguous [N/32, K/64, 32, 2]");
+  TORCH_CHECK(!glu || N % 64 == 0, "wstream_gemm_w4: GLU weights need N % 64 == 0");
+  int mt = 0, kc = 0, s = 0;
+  TORCH_CHECK(kafka_wstream_plan(M, N, K, (int)max_splits, &mt, &kc, &s) == 0, "wstream_gemm_w4: unsupported shape");
+  bf16* yp = nullptr;
+  int64_t ldy = 0;
+  float* pp = nullptr;
+  if (s == 1) {
+    TORCH_CHECK(y.has_value(), "wstream_gemm_w4: y required for a single split");
+    CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == M && y->size(1) == (glu ? N / 2 : N), "wstream_gemm_w4: y shape");
+    yp = bptr(y.value());
+    ldy = y->stride(0);
+  } else {
+    TORCH_CHECK(p.has_value(), "wstream_gemm_w4: slab output required");
+    CHECK_CUDA(p.value()); CHECK_DT(p.value(), at::kFloat);
+    TORCH_CHECK(p->is_contiguous() && p->dim() == 3 && p->size(0) == s && p->size(1) == M && p->size(2) == N,
+                "wstream_gemm_w4: slab shape must be [splits, M, N]");
+    pp = p->data_ptr<float>();
+  }
+  const int kw = mt == 2 && kc == 256 && K / s / kc >= 6 ? 2 : 1;  // (the wstream_gemm rules above)
+  const int pin = mt != 3 && K / s / kc >= 3 ? 1 : 0;
+  CHECK_HIP(kafka_launch_wstream_gemm_w4(bptr(x), x.stride(0), wt4.data_ptr<uint8_t>(), se.data_ptr<uint8_t>(), M, N,
+                                         K, mt, kc, s, kw, pin, glu ? 1 : 0, yp, ldy, pp, cur_stream()));
+}
+
 // Fused decode-layer GEMMs (wstream_gemm.hip FIN_*): fin 1 = o / down with the split-K finisher doing the residual
 // add, the next RMSNorm's weight and its row partial sums (resid, nw, xn, ss_out); 2 = qkv with RoPE + paged KV
 // write in the finisher (positions, cos_sin, q_out, caches, slots, Hq, Hkv); 3 = gate_up with the SwiGLU epilogue
@@ -1020,6 +1060,8 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("wstream_gemm", &wstream_gemm, py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"),
         py::arg("max_splits"), py::arg("nt"), py::arg("glu"));
   m.def("wstream_gemm_w8", &wstream_gemm_w8, py::arg("x"), py::arg("wt8"), py::arg("st"), py::arg("y"), py::arg("p"),
+        py::arg("max_splits"), py::arg("glu"));
+  m.def("wstream_gemm_w4", &wstream_gemm_w4, py::arg("x"), py::arg("wt4"), py::arg("se"), py::arg("y"), py::arg("p"),
         py::arg("max_splits"), py::arg("glu"));
   m.def("wstream_fin", &wstream_fin, py::arg("fin"), py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"),
         py::arg("tickets"), py::arg("ss_in"), py::arg("eps"), py::arg("resid"), py::arg("nw"), py::arg("xn"),

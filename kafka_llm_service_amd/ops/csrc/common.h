@@ -176,6 +176,16 @@ __device__ __forceinline__ bf16x8 dq8(uint32_t lo, uint32_t hi, float sc) {
   return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// 8 e2m1 nibbles (one dword, element i in nibble i: the low nibble of a byte first) -> bf16x8 times `sc` (a power of
+// two): v_cvt_scalef32_pk_bf16_fp4, one VALU op per byte = two elements (MXFP4 weights: wstream_gemm.hip W4)
+__device__ __forceinline__ bf16x8 dq4(uint32_t v, float sc) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 0);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 1);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 2);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 3);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
 // Counter-based RNG (splitmix64 finaliser): deterministic given (seed, stream, index).
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;

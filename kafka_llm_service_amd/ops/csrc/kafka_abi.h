@@ -163,6 +163,12 @@ hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, const bf16* Wt,
 hipError_t kafka_launch_wstream_gemm_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St, int M, int N,
                                         int K, int mt, int kc, int splits, int kw, int pin, int glu, bf16* Y,
                                         int64_t ldy, float* P, hipStream_t st);
+// MXFP4 weights: Wt4 [N/32][K/64][64 lanes][16] e2m1 bytes (ops.tile_weight_mxfp4: a lane's 16 B are the B fragments of
+// four k-steps, low nibble first), Se [N/32][K/64][32 rows][2] e8m0 block exponents (bias 127, in [7, 247]); plans,
+// configurations and outputs as above
+hipError_t kafka_launch_wstream_gemm_w4(const bf16* X, int64_t ldx, const uint8_t* Wt4, const uint8_t* Se, int M, int N,
+                                        int K, int mt, int kc, int splits, int kw, int pin, int glu, bf16* Y,
+                                        int64_t ldy, float* P, hipStream_t st);
 // Fused decode-layer GEMMs (FIN_RES / FIN_ROPE / FIN_GLU): one row tile (M <= 128), N % 128 == 0, S in
 // {1, 2, 4, 8}; P = [S][M][N] fp32 scratch (unused for S == 1); FIN_GLU needs S == 1.
 hipError_t kafka_launch_wstream_fin(int fin, const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int mt,

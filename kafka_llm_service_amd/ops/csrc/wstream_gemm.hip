@@ -228,7 +228,20 @@ enum { WIDE_P = 1, WIDE_Y = 2 };
 // fragments are the exact bf16 values e4m3 * 2^e, the MFMA stays bf16 and the accumulators hold true values: every
 // epilogue is shared with the bf16 kernel. St travels in fa.ss_in (W8 is FIN_NONE only, where no epilogue reads it), so
 // the kernel's argument block — and with it every bf16 instantiation — is byte for byte what it was without W8.
-template <int MT, int KC, bool NT, int KW, bool PIN, int FIN = FIN_NONE, bool W8 = false>
+//
+// W4 (MXFP4 weights, ops.tile_weight_mxfp4): Wt is the e2m1 image Wt4[N/32][K/64][64 lanes][16 B] — bytes 4j..4j+3
+// (dword j = 0..3) of lane (r, h) of tile (nb, kb4) = the eight nibbles W[32 nb + r][64 kb4 + 16 j + 8 h : +8], low
+// nibble first (k-step 4 kb4 + j) — so one 16-B load per lane carries the B fragments of FOUR k-steps and a
+// wave-instruction is still one contiguous 1 KB run: a quarter of the loads, prefetch registers and bytes. The block
+// scales are the e8m0 image Se[N/32][K/64][32 rows][2 B]: the two bytes of (nb, kb4, r) are the exponents of columns
+// 64 kb4 : +32 (dwords 0, 1) and 64 kb4 + 32 : +32 (dwords 2, 3) of that row. The image does not depend on the plan
+// (MT, KC, KW only decide how many (nb, kb4) groups a wave walks per chunk); a lane fetches one 2-B load per weight
+// vector, and a wave's load is one contiguous 64-B run (both h halves read the same bytes). The scale loads are issued
+// with the weights, ahead of them and under the same PIN fence, stay raw until their vector is dequantised, and become
+// fp32 with a shift (uint32(e) << 23: e is clamped to [7, 247] by the quantiser). dq4 (v_cvt_scalef32_pk_bf16_fp4)
+// makes the exact bf16 values e2m1 * 2^e, so MFMA, accumulators and epilogues are the bf16 kernel's. Se travels in
+// fa.ss_in like St; FIN_NONE and NT only.
+template <int MT, int KC, bool NT, int KW, bool PIN, int FIN = FIN_NONE, bool W8 = false, bool W4 = false>
 __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __restrict__ X, int64_t ldx,
                                                                  const bf16x8* __restrict__ Wt, int M, int N, int K,
                                                                  int ks, bf16* __restrict__ Y, int64_t ldy,
@@ -240,10 +253,14 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   constexpr int XL = ROWS * CPR / NTH;    // X chunks staged per thread
   constexpr int KSTEP = KC / 16;          // MFMA k-steps per K chunk
   constexpr int KSW = KSTEP / KW;         // k-steps of one wave (KW waves split each chunk along K)
-  constexpr int KSV = W8 ? KSW / 2 : KSW;  // 16-B weight vectors of one wave per chunk (W8: two k-steps each)
-  typedef typename std::conditional<W8, u32x4, bf16x8>::type wvec;
+  // 16-B weight vectors of one wave per chunk (W8: two k-steps each, W4: four)
+  constexpr int KSV = W4 ? KSW / 4 : (W8 ? KSW / 2 : KSW);
+  constexpr int VSH = W4 ? 6 : (W8 ? 5 : 4);  // log2 of the K columns one vector covers
+  constexpr int NSC = W4 ? KSV : 1;           // W4: raw block-scale pairs prefetched per chunk (one per vector)
+  typedef typename std::conditional<W8 || W4, u32x4, bf16x8>::type wvec;
   static_assert(CPR >= 16 && XL >= 1 && KSW >= 1, "chunk too small");
   static_assert(!W8 || (KSW % 2 == 0 && FIN == FIN_NONE && NT), "fp8 tiles hold k-step pairs; plain epilogues only");
+  static_assert(!W4 || (KSW % 4 == 0 && FIN == FIN_NONE && NT && !W8), "mxfp4 tiles hold four k-steps; plain epilogues only");
   static_assert(2 * ROWS * KC * 2 >= 4 * (KW - 1) * MT * 16 * 64 * 4, "LDS too small for the K-half reduction");
   __shared__ __attribute__((aligned(16))) bf16 xs[2][ROWS * KC];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -274,11 +291,16 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   const int k0 = blockIdx.y * ks;
   const int nchunks = ks / KC;
   const int nbl = active ? nb : (N >> 5) - 1;
-  // (both layouts: K / 16 bf16 or K / 32 fp8 vectors of 64 lanes x 16 B per tile row, KSV per wave and chunk)
-  const wvec* wp = reinterpret_cast<const wvec*>(Wt) +
-                   ((int64_t)nbl * (W8 ? K >> 5 : K >> 4) + (W8 ? k0 >> 5 : k0 >> 4) + kh * KSV) * 64 + lane;
+  // (every layout: K / 16 bf16, K / 32 fp8 or K / 64 mxfp4 vectors of 64 lanes x 16 B per tile row, KSV per wave and
+  // chunk)
+  const int64_t v0 = (int64_t)nbl * (K >> VSH) + (k0 >> VSH) + kh * KSV;  // this wave's first vector
+  const wvec* wp = reinterpret_cast<const wvec*>(Wt) + v0 * 64 + lane;
   float wsc = 1.f;  // W8: 2^e of this lane's weight row
   if constexpr (W8) wsc = fa.ss_in[32 * nbl + r];
+  // W4: the lane's row in the block-scale image, 32 rows x 2 B per vector (same tile and vector index as wp: in range
+  // wherever the weight load is)
+  const uint16_t* sp = nullptr;
+  if constexpr (W4) sp = reinterpret_cast<const uint16_t*>(fa.ss_in) + v0 * 32 + r;
 
   // phase stamps (FinArgs::stamps, benchmarks only): 0 start, 1 main loop done, 2 slab stores drained, 3 ticket
   // taken (finisher), 4 finisher done
@@ -319,7 +341,13 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
       *reinterpret_cast<bf16x8*>(&xs[buf][row * KC + 8 * (c ^ (row & 15))]) = xr[i];
     }
   };
-  auto load_w = [&](wvec(&wv)[KSV], int ch) {
+  auto load_w = [&](wvec(&wv)[KSV], uint16_t(&sv)[NSC], int ch) {
+    if constexpr (W4) {
+      // the block scales first: loads return in order, so the first dequantisation waits for them and vector 0 only
+#pragma unroll
+      for (int t = 0; t < KSV; ++t)
+        sv[t] = __builtin_nontemporal_load(sp + (int64_t)(ch * (KSV * KW) + t) * 32);
+    }
 #pragma unroll
     for (int t = 0; t < KSV; ++t) {
       const wvec* p = wp + (int64_t)(ch * (KSV * KW) + t) * 64;
@@ -335,11 +363,18 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[mt][i] = 0.f;
-  auto compute = [&](int buf, const wvec(&wv)[KSV]) {
+  auto compute = [&](int buf, const wvec(&wv)[KSV], const uint16_t(&sv)[NSC]) {
 #pragma unroll
     for (int t = 0; t < KSW; ++t) {
       bf16x8 wf;
-      if constexpr (W8) {
+      if constexpr (W4) {
+        // dequantised right before its MFMAs: the prefetch registers keep the raw nibbles and exponent bytes; dword
+        // t & 3 of vector t >> 2 is this k-step, its block exponent byte (t & 3) >> 1 of the vector's pair
+        const u32x4 v = wv[t >> 2];
+        const uint32_t e2 = sv[t >> 2];
+        const uint32_t eb = (t & 2) ? e2 >> 8 : e2 & 0xffu;
+        wf = dq4(v[t & 3], __builtin_bit_cast(float, eb << 23));
+      } else if constexpr (W8) {
         // dequantised right before its MFMAs: the prefetch registers keep the raw fp8
         const u32x4 v = wv[t >> 1];
         wf = (t & 1) ? dq8(v[2], v[3], wsc) : dq8(v[0], v[1], wsc);
@@ -356,9 +391,10 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   };
 
   wvec wa[KSV], wb[KSV];
+  uint16_t sa[NSC], sb[NSC];  // (W4 only: dead otherwise)
   // X first: its LDS image is written while the first weight chunk is still in flight (loads return in order)
   load_x(0);
-  load_w(wa, 0);
+  load_w(wa, sa, 0);
   store_x(0);
   __syncthreads();
   int ch = 0;
@@ -366,26 +402,26 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   // in buffer 0 / wa
   for (; ch + 2 < nchunks; ch += 2) {
     load_x(ch + 1);
-    load_w(wb, ch + 1);
-    compute(0, wa);
+    load_w(wb, sb, ch + 1);
+    compute(0, wa, sa);
     store_x(1);
     __syncthreads();
     load_x(ch + 2);
-    load_w(wa, ch + 2);
-    compute(1, wb);
+    load_w(wa, sa, ch + 2);
+    compute(1, wb, sb);
     store_x(0);
     __syncthreads();
   }
   // tail: one or two chunks left (chunk ch is in buffer 0 / wa)
   if (ch + 1 < nchunks) {
     load_x(ch + 1);
-    load_w(wb, ch + 1);
-    compute(0, wa);
+    load_w(wb, sb, ch + 1);
+    compute(0, wa, sa);
     store_x(1);
     __syncthreads();
-    compute(1, wb);
+    compute(1, wb, sb);
   } else {
-    compute(0, wa);
+    compute(0, wa, sa);
   }
 
   if constexpr (KW > 1) {
@@ -989,6 +1025,50 @@ extern "C" hipError_t kafka_launch_wstream_gemm_w8(const bf16* X, int64_t ldx, c
   else return hipErrorInvalidValue;
 #undef KAFKA_W8_IF
 #undef KAFKA_W8
+  return hipGetLastError();
+}
+
+// MXFP4 weights (W4 above): Wt4 [N/32][K/64][64][16] e2m1 bytes, Se [N/32][K/64][32][2] e8m0 block exponents. Same
+// plans, grid, outputs and (mt, kc, kw, pin) configurations as kafka_launch_wstream_gemm; always non-temporal loads.
+extern "C" hipError_t kafka_launch_wstream_gemm_w4(const bf16* X, int64_t ldx, const uint8_t* Wt4, const uint8_t* Se,
+                                                  int M, int N, int K, int mt, int kc, int splits, int kw, int pin,
+                                                  int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st) {
+  if (M < 1) return hipSuccess;
+  if (glu && (N % 64 != 0 || kw > 2)) return hipErrorInvalidValue;
+  if (K % 64 != 0 || N % 32 != 0 || Wt4 == nullptr || Se == nullptr) return hipErrorInvalidValue;
+  if (K % (kc * splits) != 0 || (splits > 1 && P == nullptr) || (splits == 1 && P == nullptr && Y == nullptr))
+    return hipErrorInvalidValue;
+  const int rt = (M + 32 * mt - 1) / (32 * mt);
+  const int nblk = (N + 127) / 128;
+  const dim3 grid((rt > 1 ? (nblk + 7) / 8 * 8 : nblk) * rt, splits);
+  const int ks = K / splits;
+  const auto* wt = reinterpret_cast<const bf16x8*>(Wt4);
+  float* p = splits > 1 ? P : nullptr;
+  const bool y_unaligned = Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0);
+  const int wide = y_unaligned ? WIDE_P : (WIDE_P | WIDE_Y);
+  FinArgs fa{};
+  fa.ss_in = reinterpret_cast<const float*>(Se);  // (the W4 kernel's block-scale image: see the kernel's header comment)
+#define KAFKA_W4(MT_, KC_, KW_, PIN_)                                                                              \
+  wstream_gemm_kernel<MT_, KC_, true, KW_, PIN_, FIN_NONE, false, true><<<grid, 256 * KW_, 0, st>>>(               \
+      X, ldx, wt, M, N, K, ks, Y, ldy, p, glu, rt, wide, fa)
+#define KAFKA_W4_IF(MT_, KC_, KW_)                                      \
+  if (mt == MT_ && kc == KC_ && kw == KW_) {                           \
+    if (pin)                                                           \
+      KAFKA_W4(MT_, KC_, KW_, true);                                   \
+    else                                                               \
+      KAFKA_W4(MT_, KC_, KW_, false);                                  \
+  }
+  KAFKA_W4_IF(1, 256, 1)
+  else KAFKA_W4_IF(1, 256, 2)
+  else KAFKA_W4_IF(2, 256, 1)
+  else KAFKA_W4_IF(2, 256, 2)
+  else KAFKA_W4_IF(3, 256, 1)
+  else KAFKA_W4_IF(4, 128, 1)
+  else KAFKA_W4_IF(4, 128, 2)
+  else KAFKA_W4_IF(6, 128, 1)
+  else return hipErrorInvalidValue;
+#undef KAFKA_W4_IF
+#undef KAFKA_W4
   return hipGetLastError();
 }
 

@@ -121,6 +121,88 @@ def untile_experts_fp8(wt8: torch.Tensor, st: torch.Tensor, glu: bool = False) -
     return out
 
 
+# MXFP4 (OCP Microscaling): 32-element blocks along K, e2m1 elements (sign + 3 bits on the grid below), one e8m0
+# exponent (bias 127) per block.
+MXFP4_BLOCK = 32
+MXFP4_EXP_MIN, MXFP4_EXP_MAX = 7, 247  # biased: the scale uint32(e) << 23 is a normal fp32, e2m1 * 2^e a normal bf16
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# magnitude code of the doubled grid value 0, 1, 2, 3, 4, 6, 8, 12
+_E2M1_CODE_OF_2V = torch.tensor([0, 1, 2, 3, 4, 0, 5, 0, 6, 0, 0, 0, 7], dtype=torch.uint8)
+_E2M1_VALUE = torch.tensor(_E2M1_GRID + tuple(-v for v in _E2M1_GRID), dtype=torch.float32)
+
+
+def mxfp4_quant(w: torch.Tensor):
+    """bf16 [N, K] (K % 64 == 0) -> (codes uint8 [N, K/2], e uint8 [N, K/32]): per 32-column block the OCP shared
+    exponent e = floor(log2(amax)) - 2 (biased by 127, clamped to [7, 247]; 127 for an all-zero block) and the
+    elements w / 2^e rounded to nearest-even on the e2m1 grid 0, .5, 1, 1.5, 2, 3, 4, 6, saturated to +-6. Two codes
+    per byte, the even column in the LOW nibble (the order v_cvt_scalef32_pk_bf16_fp4 delivers a byte's elements)."""
+    N, K = w.shape
+    if K % 64:
+        raise ValueError(f"mxfp4_quant: K={K} must be a multiple of 64")
+    x = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = x.abs().amax(-1)
+    _, ex = torch.frexp(amax)  # amax = m * 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = torch.where(amax > 0, ex - 3 + 127, torch.full_like(ex, 127)).clamp(MXFP4_EXP_MIN, MXFP4_EXP_MAX)
+    y = torch.ldexp(x, (127 - e)[..., None])
+    a = y.abs().clamp(max=6.0)
+    # nearest-even per binade: steps of .5 below 2, of 1 below 4, of 2 up to 6 (torch.round is half-to-even, and the
+    # even multiple of the step is the code with an even mantissa bit)
+    v = torch.where(a < 2.0, torch.round(a * 2.0) * 0.5, torch.where(a < 4.0, torch.round(a), torch.round(a * 0.5) * 2.0))
+    mag = _E2M1_CODE_OF_2V.to(w.device)[(v * 2.0).long()]
+    code = (mag | (((y < 0) & (mag > 0)).to(torch.uint8) << 3)).reshape(N, K // 2, 2)
+    return code[..., 0] | (code[..., 1] << 4), e.to(torch.uint8)
+
+
+def mxfp4_dequant(codes: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """(codes uint8 [N, K/2], e uint8 [N, K/32]) of ``mxfp4_quant`` -> the values e2m1 * 2^(e - 127), fp32 [N, K]
+    (each one exact in bf16)."""
+    N = codes.shape[0]
+    c = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(N, -1).long()
+    v = _E2M1_VALUE.to(codes.device)[c].reshape(N, -1, MXFP4_BLOCK)
+    return torch.ldexp(v, (e.int() - 127)[..., None]).reshape(N, -1)
+
+
+def _glu_tiles(t: torch.Tensor, inverse: bool = False) -> torch.Tensor:
+    """Tile rows [N/32, ...] between natural order and the gate_0, up_0, gate_1, ... interleave of ``tile_weight``."""
+    nb = t.shape[0]
+    a, b = (nb // 2, 2) if inverse else (2, nb // 2)
+    return t.reshape(a, b, *t.shape[1:]).transpose(0, 1).reshape(t.shape)
+
+
+def tile_weight_mxfp4(w: torch.Tensor, glu: bool = False):
+    """Row-major weight [N, K] -> (wt4 float4_e2m1fn_x2 [N/32, K/64, 64, 16], se float8_e8m0fnu [N/32, K/64, 32, 2]):
+    ``mxfp4_quant`` laid out for the MXFP4 weight-streaming GEMM (csrc/wstream_gemm.hip W4). Lane l = (r = l % 32,
+    h = l // 32) of tile (nb, kb4) holds in bytes 4j..4j+3 (j = 0..3) the eight columns 64 kb4 + 16 j + 8 h : +8 of row
+    32 nb + r — the B fragment of MFMA k-step 4 kb4 + j — so one 16-B load carries four k-steps. se[nb, kb4, r] are the
+    two block exponents of row 32 nb + r for columns 64 kb4 : +32 and 64 kb4 + 32 : +32 (dwords 0, 1 and 2, 3 of that
+    lane's vector): one 64-B run per (tile, kb4), independent of the kernel's plan, and a K slice on a 64-column
+    boundary is a slice of both images. ``glu`` interleaves the 32-row tiles gate_0, up_0, gate_1, ... as
+    ``tile_weight`` does (rows of both images in that tile order)."""
+    N, K = w.shape
+    if N % 32 or K % 64 or (glu and N % 64):
+        raise ValueError(f"tile_weight_mxfp4: N={N} must be a multiple of 32 (64 with glu), K={K} of 64")
+    codes, e = mxfp4_quant(w)
+    # bytes of a row's 64-column tile: [j][h][4], byte (j, h, b) = columns 16 j + 8 h + 2 b, + 1
+    t = codes.reshape(N // 32, 32, K // 64, 4, 2, 4).permute(0, 2, 4, 1, 3, 5)
+    s = e.reshape(N // 32, 32, K // 64, 2).permute(0, 2, 1, 3)
+    if glu:
+        t, s = _glu_tiles(t), _glu_tiles(s)
+    return (t.contiguous().view(N // 32, K // 64, 64, 16).view(torch.float4_e2m1fn_x2),
+            s.contiguous().view(torch.float8_e8m0fnu))
+
+
+def untile_weight_mxfp4(wt4: torch.Tensor, se: torch.Tensor, glu: bool = False) -> torch.Tensor:
+    """The dequantised row-major weight e2m1 * 2^e of MXFP4 tiles: bf16 [N, K], exact (1 mantissa bit, normal
+    exponents) and element for element ``mxfp4_dequant(*mxfp4_quant(w))``."""
+    nb, kb = wt4.shape[0], wt4.shape[1]
+    t, s = wt4.view(torch.uint8), se.view(torch.uint8)
+    if glu:
+        t, s = _glu_tiles(t, inverse=True), _glu_tiles(s, inverse=True)
+    codes = t.reshape(nb, kb, 2, 32, 4, 4).permute(0, 3, 1, 4, 2, 5).reshape(nb * 32, kb * 32)
+    e = s.permute(0, 2, 1, 3).reshape(nb * 32, kb * 2)
+    return mxfp4_dequant(codes, e).to(torch.bfloat16)
+
+
 def fp8_dequant_pages(k_pages: torch.Tensor, v_pages: torch.Tensor):
     """fp8 pages (K [n, Hkv, 16D + 32], V [n, Hkv, 16D] uint8) -> fp32 K [n, Hkv, 16, D] and V [n, Hkv, D, 16]
     (V in natural key order)."""

@@ -84,8 +84,8 @@ class ServerConfig:
 
 
 def _engine_kwargs(e) -> dict[str, Any]:
-    """Engine options from the environment: KAFKA_KV_DTYPE (bf16 | fp8 KV cache), KAFKA_WEIGHT_DTYPE (bf16 | fp8 dense
-    projections and lm_head), KAFKA_GRAPHS=1 (hipGraph decode
+    """Engine options from the environment: KAFKA_KV_DTYPE (bf16 | fp8 KV cache), KAFKA_WEIGHT_DTYPE (bf16 | fp8 | mxfp4
+    dense projections and lm_head), KAFKA_GRAPHS=1 (hipGraph decode
     steps), KAFKA_MAX_NUM_SEQS, KAFKA_MAX_BATCHED_TOKENS."""
     kw: dict[str, Any] = {}
     if e.get("KAFKA_KV_DTYPE"):
