@@ -7,6 +7,10 @@
 //                             (#tokens with x > x_c) < k and (mass of tokens with x > x_c) < p; otherwise raise the
 //                             pivot to x_c and redraw. Accepted draws are exactly distributed as the renormalised
 //                             top-k/top-p distribution; rounds are bounded (fallback: argmax).
+//                             Every comparison is strict, which fixes the tie rule: tokens tied with the candidate
+//                             count neither toward k nor toward the mass, and tokens tied with the pivot are not
+//                             redrawn (top_k = 1 over a maximum that occurs twice returns either of the two).
+//                             ops/reference.py sample_replay replays these decisions with the same random stream.
 // All reads are 16-byte vectors; every pass is one streaming read of the row (bf16 or fp32 logits).
 // Greedy and plain-temperature rows (no top-k / top-p) are split over `nsplit` workgroups (grid (B, nsplit)): each
 // takes a slice of the vocabulary, publishes its (value, index) winner, and the last of a row's workgroups to take

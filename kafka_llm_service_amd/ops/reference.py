@@ -12,7 +12,9 @@ or, for the fp8 cache (kv_dtype="fp8", ops/csrc/rope_kv.hip), uint8 pages
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
+import numpy as np
 import torch
 
 PAGE = 16
@@ -471,7 +473,9 @@ def process_logits(logits, proc, mask_tab, counts):
 
 def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
            mask_tab=None, counts=None):
-    """CPU sampler with the same semantics (not the same random stream) as the HIP kernel."""
+    """CPU sampler with the same semantics (not the same random stream) as the HIP kernel: the sort-based definition
+    of top-k / top-p and the CPU engine path. ``sample_replay`` below reproduces the kernel's own stream and
+    decisions draw by draw."""
     B, V = logits.shape
     forced = None
     if proc is not None:
@@ -515,6 +519,202 @@ def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=No
         out[:B].copy_(res)
         return out
     return res
+
+
+# ---- sample_replay: the sampler kernel's algorithm with the kernel's own random stream -------------------------------
+# The noise of csrc/sampling.hip is a pure integer function of (seed, step, round, index) (mix64 / uniform01 of
+# csrc/common.h, lowbias32 / gumbel_fast of csrc/sampling.hip) and its uniform u = (h + 1) * 2^-24 is exact in fp32, so
+# the stream is reproduced bit for bit with wrapping numpy integers. x / T is formed in fp32 exactly as the kernel forms
+# it (its exact ties are the replay's exact ties); everything after that (Gumbel noise, scores, max, z, mass) is float64.
+# Where the float64 decision is closer than a band to going the other way the row is flagged ``ambiguous``: the kernel's
+# fp32 arithmetic may legitimately decide it either way. The bands come from fp32 arithmetic, not from a kernel run:
+#   score band on x / T + g: scores stay below ~64 in magnitude, so one fp32 ulp is at most 3.8e-6; 1e-4 is ~25 ulps for
+#     the two native logarithms and the add;
+#   mass band on mass / z: fp32 sums of 1024 partial sums and the native exp on arguments up to ~50 in magnitude are of
+#     the order of 1e-5 relative.
+SAMPLE_SCORE_BAND = 1e-4
+SAMPLE_MASS_BAND = 1e-4
+SAMPLE_MAX_ROUNDS = 32                                           # the launcher's max_rounds
+_U_CLAMP = float(np.float32(1.0) - np.float32(2.0 ** -24))      # the kernel's 0.99999994f: only u == 1 is clamped
+_NO_IDX = 0x7FFFFFFF                                             # ArgMax's "nothing yet" index
+_STREAM_MUL = np.uint64(0x632BE59BD9B4E019)
+
+
+class SampleReplay(NamedTuple):
+    tokens: torch.Tensor     # int64 [B]
+    ambiguous: torch.Tensor  # bool [B]: some decision of the row lies within a band (the kernel may differ there)
+    rounds: torch.Tensor     # int64 [B]: draws of the rejection loop (0 for greedy / plain / forced rows)
+    fell_back: torch.Tensor  # bool [B]: the loop ended without an accepted draw (token = argmax)
+    plain: torch.Tensor      # bool [B]: drawn from the plain-temperature stream (gumbel_fast), not the filtered one
+
+
+def _mix64(z: np.ndarray) -> np.ndarray:
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _lowbias32(x: np.ndarray) -> np.ndarray:
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7FEB352D)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846CA68B)
+    return x ^ (x >> np.uint32(16))
+
+
+def _gumbel(h24: np.ndarray) -> np.ndarray:
+    """Gumbel noise of the 24-bit integers h: u = (h + 1) * 2^-24 in (0, 1], exact in fp32 and in float64."""
+    u = np.minimum((h24.astype(np.float64) + 1.0) * 2.0 ** -24, _U_CLAMP)
+    return -np.log(-np.log(u))
+
+
+def _first_max(s: np.ndarray):
+    """Per row (max, index) the way the kernel's ``better`` reduces from (-inf, 0x7fffffff): NaN never wins and the
+    lowest index wins among equals; a row with nothing to compare keeps (-inf, 0x7fffffff)."""
+    R = s.shape[0]
+    if s.shape[1] == 0:
+        return np.full(R, -np.inf), np.full(R, _NO_IDX, dtype=np.int64)
+    ok = ~np.isnan(s)
+    m = np.where(ok, s, -np.inf).max(1)
+    hit = ok & (s == m[:, None])
+    return m, np.where(hit.any(1), hit.argmax(1), _NO_IDX).astype(np.int64)
+
+
+def _replay_plain(xv, greedy, seeds, steps, nsplit):
+    """Greedy / plain-temperature rows: argmax of x (greedy) or x / T + gumbel_fast over ``nsplit`` slices of the row
+    and the reduction of the slices' winners, as the split workgroups do. -> (token, ambiguous)."""
+    R, V = xv.shape
+    key = _mix64(seeds ^ _mix64((steps << np.uint64(8)) * _STREAM_MUL))
+    idx = np.arange(V, dtype=np.uint32)[None, :]
+    h = _lowbias32(_lowbias32(idx + key.astype(np.uint32)[:, None]) ^ (key >> np.uint64(32)).astype(np.uint32)[:, None])
+    s = xv.astype(np.float64)
+    s = np.where(greedy[:, None], s, s + _gumbel(h >> np.uint32(8)))
+    nvec = V >> 3
+    per = -(-nvec // nsplit)
+    vals = np.full((R, nsplit), -np.inf)
+    ids = np.full((R, nsplit), _NO_IDX, dtype=np.int64)
+    for sp in range(nsplit):
+        v0 = sp * per
+        v1 = min(nvec, v0 + per)
+        cols = np.r_[v0 * 8:max(v0, v1) * 8, (nvec * 8 if sp == nsplit - 1 else V):V]  # the last split owns the tail
+        vals[:, sp], i = _first_max(s[:, cols])
+        if cols.size:
+            ids[:, sp] = np.where(i != _NO_IDX, cols[np.minimum(i, cols.size - 1)], _NO_IDX)
+    m = vals.max(1)
+    tok = np.where(vals == m[:, None], ids, _NO_IDX).min(1)
+    tok = np.where((tok >= 0) & (tok < V), tok, 0)  # emit_token: an index outside the vocabulary becomes 0
+    # greedy compares the fp32 values themselves (exact, lowest index among equals): never ambiguous
+    r = np.arange(R)
+    rest = s.copy()
+    rest[r, tok] = -np.inf
+    amb = ~greedy & (s[r, tok] - _first_max(rest)[0] < SAMPLE_SCORE_BAND)
+    return tok, amb
+
+
+def _replay_filtered(x, xv, tp, tk, seeds, steps):
+    """top-k / top-p rows: the rejection loop round by round. x: the processed fp32 logits (the fallback's argmax),
+    xv = x / T in fp32. -> (token, ambiguous, rounds, fell_back)."""
+    R, V = xv.shape
+    xd = xv.astype(np.float64)
+    e = np.exp(xd - _first_max(xd)[0][:, None])
+    z = e.sum(1)
+    pivot = np.full(R, -np.inf, dtype=np.float32)
+    tok = np.full(R, -1, dtype=np.int64)
+    rounds = np.zeros(R, dtype=np.int64)
+    amb = np.zeros(R, dtype=bool)
+    base = steps << np.uint64(8)
+    live = np.arange(R)
+    for rnd in range(SAMPLE_MAX_ROUNDS):
+        cand = xv[live] > pivot[live, None]  # strict: tokens tied with the pivot are out
+        n = cand.sum(1)
+        live, cand, n = live[n > 0], cand[n > 0], n[n > 0]  # nothing above the pivot ends the loop (fallback)
+        if live.size == 0:
+            break
+        rounds[live] += 1
+        r, c = np.nonzero(cand)  # row-major: one contiguous segment per live row
+        rows = live[r]
+        stream = (base[rows] ^ np.uint64(rnd)) * _STREAM_MUL + c.astype(np.uint64)
+        s = xd[rows, c] + _gumbel(_mix64(seeds[rows] ^ _mix64(stream)) >> np.uint64(40))
+        start = np.cumsum(n) - n
+        best = np.maximum.reduceat(s, start)
+        ci = np.minimum.reduceat(np.where(s == best[r], c, V), start)  # lowest index among equal scores
+        second = np.maximum.reduceat(np.where(c == ci[r], -np.inf, s), start)
+        xc = xv[live, ci]
+        above = xv[live] > xc[:, None]  # strict: tokens tied with the candidate count toward neither k nor the mass
+        cnt = above.sum(1)
+        mass = np.where(above, e[live], 0.0).sum(1) / z[live]
+        ok = (mass < tp[live]) & ((tk[live] <= 0) | (cnt < tk[live]))
+        amb[live] |= (best - second < SAMPLE_SCORE_BAND) | (np.abs(mass - tp[live]) < SAMPLE_MASS_BAND)
+        tok[live[ok]] = ci[ok]
+        pivot[live[~ok]] = xc[~ok]
+        live = live[~ok]
+    fell = tok < 0
+    if fell.any():  # argmax of the processed logits (not divided by T), lowest index among equals
+        i = _first_max(x[fell].astype(np.float64))[1]
+        tok[fell] = np.where((i >= 0) & (i < V), i, 0)
+    return tok, amb, rounds, fell
+
+
+def sample_replay(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
+                  mask_tab=None, counts=None, nsplit: int = 1) -> SampleReplay:
+    """CPU replay of csrc/sampling.hip with the kernel's own random stream: the arguments of ``ops.sample`` plus
+    ``nsplit`` (the workgroups a greedy / plain-temperature row is split over; it must not change the result). Every
+    row whose ``ambiguous`` flag is clear has exactly one right token and the kernel must return it. Logits are finite
+    or -inf. ``step`` holds one value as for the kernel, or (replay only) one per row. ``counts`` is bumped with every
+    token like the kernel bumps it."""
+    B, V = logits.shape
+    assert 1 <= nsplit <= 64
+    forced = None
+    if proc is not None:
+        x, forced = process_logits(logits, proc, mask_tab, counts)
+    else:
+        x = logits.float()
+    x = x.cpu().contiguous().numpy()
+
+    def arg(t, dtype, default):
+        if t is None:
+            return np.full(B, default, dtype=dtype)
+        return np.ascontiguousarray(t.detach().cpu().numpy()[:B].astype(dtype, copy=False))
+
+    temp = arg(temperature, np.float32, 0.0)
+    tp = arg(top_p, np.float32, 1.0).astype(np.float64)
+    tk = arg(top_k, np.int64, 0)
+    sd = arg(seeds, np.int64, 0x1234).view(np.uint64)  # int64 reinterpreted: negative seeds are legal
+    st = np.zeros(1, dtype=np.int64) if step is None else step.detach().cpu().numpy().astype(np.int64).reshape(-1)
+    st = np.ascontiguousarray(np.broadcast_to(st if st.size == B else st[:1], (B,))).view(np.uint64)
+    tokens = np.zeros(B, dtype=np.int64)
+    amb = np.zeros(B, dtype=bool)
+    rounds = np.zeros(B, dtype=np.int64)
+    fell = np.zeros(B, dtype=bool)
+    with np.errstate(all="ignore"):
+        greedy = ~(temp > 0)
+        inv_t = np.where(greedy, np.float32(1.0), np.float32(1.0) / temp).astype(np.float32)
+        is_forced = forced.numpy() >= 0 if forced is not None else np.zeros(B, dtype=bool)
+        filtered = ~greedy & ((tp < 1.0) | ((tk > 0) & (tk < V))) & ~is_forced
+        plain = ~filtered & ~is_forced
+        tokens[is_forced] = forced.numpy()[is_forced] if forced is not None else 0
+        tokens[is_forced & ((tokens < 0) | (tokens >= V))] = 0
+        chunk = max(1, (1 << 22) // max(V, 1))  # rows per pass: bounds the float64 temporaries
+        for sel, filt in ((np.nonzero(plain)[0], False), (np.nonzero(filtered)[0], True)):
+            for i in range(0, sel.size, chunk):
+                rows = sel[i:i + chunk]
+                xv = x[rows] * inv_t[rows, None]  # fp32 product, as the kernel forms it
+                if filt:
+                    tokens[rows], amb[rows], rounds[rows], fell[rows] = _replay_filtered(x[rows], xv, tp[rows], tk[rows],
+                                                                                        sd[rows], st[rows])
+                else:
+                    tokens[rows], amb[rows] = _replay_plain(xv, greedy[rows], sd[rows], st[rows], nsplit)
+    res = torch.from_numpy(tokens)
+    if proc is not None and counts is not None:
+        for b in range(B):
+            slot = int(proc[b, 2])
+            if slot >= 0:
+                counts[slot, int(res[b])] += 1
+    if out is not None:
+        out[:B].copy_(res)
+    return SampleReplay(res, torch.from_numpy(amb), torch.from_numpy(rounds), torch.from_numpy(fell),
+                        torch.from_numpy(plain & ~greedy))
 
 
 def token_logprobs(logits, tokens, rows=None, k: int = 0):
