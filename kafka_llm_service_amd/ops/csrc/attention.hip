@@ -1070,9 +1070,13 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_prefill_kernel(const Att
     // by row. fp32 partials: 4 rounds of 32 d; bf16 output: 2 rounds of 64 d.
     if (!__any(valid)) return;  // wave-uniform
     const bool part = it.split >= 0;
-    const float inv = acc.l > 0.f ? 1.f / acc.l : 0.f;
+    // (an item past MAX_STAGED_PAGES left acc.l = NaN above: it goes out as NaN rows and a NaN lse, as attn_tile.hip's,
+    // not as the 0 / -inf of an empty key range, which a merge would weigh as nothing)
+    const bool bad = acc.l != acc.l;
+    const float inv = acc.l > 0.f ? 1.f / acc.l : (bad ? acc.l : 0.f);
     if (part && valid && h == 0)
-      lse_part[((int64_t)token * Hq + head) * S_total + it.split] = acc.l > 0.f ? acc.m + log2f(acc.l) : -INFINITY;
+      lse_part[((int64_t)token * Hq + head) * S_total + it.split] =
+          acc.l > 0.f ? acc.m + log2f(acc.l) : (bad ? acc.l : -INFINITY);
     char* slab = lds + w * 4096;
     const int nvalid = it.q_count * G - w * 32;  // rows of this wave below it (uniform)
     const int cc = lane & 7;
