@@ -147,26 +147,26 @@ class TransformerLM:
         per element plus a 4-byte scale per row for the dense projections, the lm_head and the MoE experts (a scale
         per row of every expert). ``"mxfp4"``: half a byte per element plus one exponent byte per 32 (4.25 bits) for the
         dense projections and the lm_head; the MoE experts keep bf16 tiles."""
-        def tiled(w, dense=True):
-            if weight_dtype == "fp8":
-                return w.numel() + 4 * (w.numel() // w.shape[-1])
-            if weight_dtype == "mxfp4" and dense:
-                return w.numel() // 2 + w.numel() // 32
-            return w.numel() * w.element_size()
+        expert_dtype = self._expert_dtype(weight_dtype)  # (refuses an unknown weight_dtype)
 
         n = 0
         for lw in self.layers:
             for name in LayerWeights.STREAMED:
                 w = getattr(lw, name)
                 if w is not None and ops.stream_plan(1, w.shape[0], w.shape[1]) is not None:
-                    n += tiled(w)
+                    n += ops.tiled_weight_bytes(w.shape, weight_dtype)
             for name in ("w13", "w2"):
                 w = getattr(lw, name)
                 if w is not None and ops.stream_moe_supported(w.shape[1], w.shape[2]):
-                    n += tiled(w, dense=False)
+                    n += ops.tiled_weight_bytes(w.shape, expert_dtype)
         if self.lm_head is not None and ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
-            n += tiled(self.lm_head)
+            n += ops.tiled_weight_bytes(self.lm_head.shape, weight_dtype)
         return n
+
+    @staticmethod
+    def _expert_dtype(weight_dtype: str) -> str:
+        """The tile format of the MoE experts under ``weight_dtype``: bf16 where the grouped kernel does not take it."""
+        return weight_dtype if ops.weight_format(weight_dtype).experts else "bf16"
 
     def enable_stream_weights(self, tiled_only: bool = False, weight_dtype: str = "bf16") -> int:
         """Keep a wave-tiled copy of every dense projection and of the lm_head (ops.tile_weight) so decode-sized
@@ -199,24 +199,14 @@ class TransformerLM:
         seam. Blocks run along K and every rank quantises its own shard, so a row-parallel shard cut on a multiple of
         64 columns has exactly the matching slice of the unsharded model's tiles. The MoE experts keep bf16 tiles in
         this mode (attention projections and the lm_head are quantised)."""
-        if weight_dtype not in ("bf16", "fp8", "mxfp4"):
-            raise ValueError(f"weight_dtype must be bf16, fp8 or mxfp4, not {weight_dtype!r}")
-        fp8 = weight_dtype == "fp8"
-        mxfp4 = weight_dtype == "mxfp4"
+        expert_dtype = self._expert_dtype(weight_dtype)  # (refuses an unknown weight_dtype)
         added = 0
 
         def tile(w, glu=False):
             """(tiles, scales or None, row-major tensor to keep, bytes of the tiled copy)"""
-            if mxfp4:
-                wt, se = ops.tile_weight_mxfp4(w, glu=glu)
-                keep = None if tiled_only else ops.untile_weight_mxfp4(wt, se, glu=glu)
-                return wt, se, keep, wt.numel() + se.numel()
-            if not fp8:
-                wt = ops.tile_weight(w, glu=glu)
-                return wt, None, w, wt.numel() * wt.element_size()
-            wt, st = ops.tile_weight_fp8(w, glu=glu)
-            keep = None if tiled_only else ops.untile_weight_fp8(wt, st, glu=glu)
-            return wt, st, keep, wt.numel() + st.numel() * st.element_size()
+            wt, st = ops.tile_weight_as(w, weight_dtype, glu)
+            keep = w if st is None else (None if tiled_only else ops.untile_weight_as(wt, st, glu))
+            return wt, st, keep, ops.tiled_weight_bytes(w.shape, weight_dtype)
 
         for lw in self.layers:
             for name in LayerWeights.STREAMED:
@@ -237,17 +227,15 @@ class TransformerLM:
             if not tiled_only and lw.w13 is not None and \
                     ops.stream_moe_supported(lw.w13.shape[1], lw.w13.shape[2]) and \
                     ops.stream_moe_supported(lw.w2.shape[1], lw.w2.shape[2]):
-                if fp8:  # expert MLPs: grouped streaming kernel on e4m3 tiles, row-major = the dequantised experts
-                    for name, glu in (("w13", True), ("w2", False)):
-                        wt, st = ops.tile_experts_fp8(getattr(lw, name), glu=glu)
-                        setattr(lw, name + "_t", wt)
-                        setattr(lw, name + "_s", st)
-                        setattr(lw, name, ops.untile_experts_fp8(wt, st, glu=glu))
-                        added += wt.numel() + st.numel() * st.element_size()
-                else:
-                    lw.w13_t = ops.tile_experts(lw.w13, glu=True)  # expert MLPs: grouped streaming kernel
-                    lw.w2_t = ops.tile_experts(lw.w2)
-                    added += (lw.w13.numel() + lw.w2.numel()) * lw.w13.element_size()
+                # expert MLPs: grouped streaming kernel; quantised tiles: row-major = the dequantised experts
+                for name, glu in (("w13", True), ("w2", False)):
+                    w = getattr(lw, name)
+                    wt, st = ops.tile_experts_as(w, expert_dtype, glu)
+                    setattr(lw, name + "_t", wt)
+                    setattr(lw, name + "_s", st)
+                    if st is not None:
+                        setattr(lw, name, ops.untile_experts_as(wt, st, glu))
+                    added += ops.tiled_weight_bytes(w.shape, expert_dtype)
         if ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
             # (an lm_head that aliases the embedding gets a tensor of its own here: the embedding keeps its values)
             self.lm_head_t, self.lm_head_s, keep, nbytes = tile(self.lm_head)
@@ -285,11 +273,7 @@ class TransformerLM:
                st: torch.Tensor | None = None) -> torch.Tensor:
         """The row-major weight for hipBLASLt: the stored one, or (tiled-only mode) a transient untiled copy —
         dequantised for fp8 and mxfp4 tiles (``st`` their scales)."""
-        if w is not None:
-            return w
-        if ops.is_mxfp4_weight(wt):
-            return ops.untile_weight_mxfp4(wt, st, glu=glu)
-        return ops.untile_weight_fp8(wt, st, glu=glu) if ops.is_fp8_weight(wt) else ops.untile_weight(wt, glu=glu)
+        return w if w is not None else ops.untile_weight_as(wt, st, glu)
 
     def dense_weight(self, lw: LayerWeights | None, name: str) -> torch.Tensor:
         """Row-major [N, K] weight of a streamed projection of ``lw`` (or of "lm_head" with lw = None) in either

@@ -12,7 +12,9 @@ Kernel inventory:
 """
 from __future__ import annotations
 
+import math
 import os
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -325,10 +327,74 @@ def is_mxfp4_weight(wt: torch.Tensor | None) -> bool:
     return wt is not None and wt.dtype == _F4
 
 
+# ---- weight tile formats of the streaming GEMMs -------------------------------------------------------------------
+# The one place that knows them: everything below (and models/llama.py) looks a format up by the TILE dtype
+# (WEIGHT_FORMATS) or by its weight_dtype name (WEIGHT_DTYPES) and reads what it needs from the entry.
+class WeightFormat(NamedTuple):
+    name: str                           # the weight_dtype of enable_stream_weights / EngineConfig
+    abi: int                            # csrc/kafka_abi.h WF_*
+    vk: int                             # K columns of one 16-B tile vector: tiles are [N/32, K/vk, 64, 32 B / vk elements]
+    tile: Callable                      # (w [N, K], glu) -> (tiles, scale or None)
+    untile: Callable                    # (tiles, scale, glu) -> row-major bf16 [N, K] (quantised: the dequantised values)
+    scale_dtype: torch.dtype | None     # None: the tiles have no scale
+    scale_shape: Callable | None        # the tiles' shape -> their scale's (leading expert dims pass through)
+    scale_name: str                     # for messages
+    raw: bool                           # the extension takes tiles and scale viewed as uint8
+    experts: bool                       # the grouped (MoE) kernel takes this format
+
+
+# (tile / untile go through this module's names at call time, so a test can wrap e.g. ``ops.untile_weight_fp8``)
+WEIGHT_FORMATS = {
+    torch.bfloat16: WeightFormat("bf16", 0, 16, lambda w, glu=False: (tile_weight(w, glu), None),
+                                 lambda wt, scale, glu=False: untile_weight(wt, glu), None, None, "", False, True),
+    torch.uint8: WeightFormat("fp8", 1, 32, lambda w, glu=False: tile_weight_fp8(w, glu),
+                              lambda wt, scale, glu=False: untile_weight_fp8(wt, scale, glu), torch.float32,
+                              lambda s: (*s[:-4], s[-4] * 32), "row scales", False, True),
+    _F4: WeightFormat("mxfp4", 2, 64, lambda w, glu=False: tile_weight_mxfp4(w, glu),
+                      lambda wt, scale, glu=False: untile_weight_mxfp4(wt, scale, glu), torch.float8_e8m0fnu,
+                      lambda s: (*s[:-2], 32, 2), "block-scale image", True, False),
+}
+WEIGHT_DTYPES = {f.name: f for f in WEIGHT_FORMATS.values()}
+
+
+def weight_format(weight_dtype: str) -> WeightFormat:
+    f = WEIGHT_DTYPES.get(weight_dtype)
+    if f is None:
+        raise ValueError(f"weight_dtype must be {', '.join(WEIGHT_DTYPES)}, not {weight_dtype!r}")
+    return f
+
+
+def _check_scale(fn: str, f: WeightFormat, wt: torch.Tensor, scale: torch.Tensor | None) -> None:
+    """Quantised tiles need the scale tensor their format defines (dtype and shape)."""
+    if scale is None:
+        raise ValueError(f"{fn}: {f.name} weight tiles need their {f.scale_name} (scale=)")
+    if scale.dtype != f.scale_dtype or scale.shape != f.scale_shape(wt.shape):  # (torch.Size compares as a tuple)
+        raise ValueError(f"{fn}: the scale of {f.name} tiles {tuple(wt.shape)} must be their {f.scale_dtype} "
+                         f"{f.scale_name} {f.scale_shape(wt.shape)}, not {scale.dtype} {tuple(scale.shape)}")
+
+
 def tiled_dims(wt: torch.Tensor) -> tuple[int, int]:
-    """(N, K) of a wave-tiled weight: bf16 tiles [N/32, K/16, 64, 8], fp8 tiles [N/32, K/32, 64, 16] or MXFP4 tiles
-    [N/32, K/64, 64, 16]."""
-    return wt.shape[0] * 32, wt.shape[1] * (64 if is_mxfp4_weight(wt) else (32 if wt.dtype == torch.uint8 else 16))
+    """(N, K) of a wave-tiled weight [N/32, K/vk, 64, .] of any format."""
+    return wt.shape[0] * 32, wt.shape[1] * WEIGHT_FORMATS[wt.dtype].vk
+
+
+def tile_weight_as(w: torch.Tensor, weight_dtype: str, glu: bool = False):
+    """Row-major [N, K] -> (tiles, scale or None) of the format ``weight_dtype`` ("bf16", "fp8", "mxfp4")."""
+    return weight_format(weight_dtype).tile(w, glu)
+
+
+def untile_weight_as(wt: torch.Tensor, scale: torch.Tensor | None, glu: bool = False) -> torch.Tensor:
+    """The row-major bf16 [N, K] weight of tiles of any format (quantised ones dequantised, exactly)."""
+    return WEIGHT_FORMATS[wt.dtype].untile(wt, scale, glu)
+
+
+def tiled_weight_bytes(shape, weight_dtype: str) -> int:
+    """Bytes of the tiles and scales of a [..., N, K] weight in the format ``weight_dtype``."""
+    f = weight_format(weight_dtype)
+    n = math.prod(shape) * 32 // f.vk
+    if f.scale_dtype is not None:
+        n += math.prod(f.scale_shape((*shape[:-2], shape[-2] // 32, shape[-1] // f.vk, 64, 16))) * f.scale_dtype.itemsize
+    return n
 
 
 def _refuse_quantised(fn: str, wt: torch.Tensor) -> None:
@@ -412,25 +478,15 @@ def linear_stream(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, nt: bo
     fp8 tiles (uint8 ``wt`` from ``tile_weight_fp8``) need their row scales ``scale``, MXFP4 tiles (``tile_weight_mxfp4``)
     their e8m0 block-scale image; same plans and outputs."""
     M, K = x.shape
-    w8 = wt.dtype == torch.uint8
-    w4 = wt.dtype == _F4
-    if w4:
-        if scale is None:
-            raise ValueError("linear_stream: mxfp4 weight tiles need their block-scale image (scale=)")
-        if scale.dtype != torch.float8_e8m0fnu or tuple(scale.shape) != (wt.shape[0], wt.shape[1], 32, 2):
-            raise ValueError(f"linear_stream: the scale of mxfp4 tiles {tuple(wt.shape)} must be their float8_e8m0fnu "
-                             f"image [N/32, K/64, 32, 2], not {scale.dtype} {tuple(scale.shape)}")
+    f = WEIGHT_FORMATS[wt.dtype]
+    if f.scale_dtype is None:
+        scale = None
+    else:
+        _check_scale("linear_stream", f, wt, scale)
         if not nt:
-            raise ValueError("linear_stream: mxfp4 weight tiles stream non-temporally only (nt=False unsupported)")
-        if wt.shape[1] * 64 != K:
-            raise ValueError(f"linear_stream: x has K={K}, the mxfp4 tiles K={wt.shape[1] * 64}")
-    if w8:
-        if scale is None:
-            raise ValueError("linear_stream: fp8 weight tiles need their row scales (scale=)")
-        if not nt:
-            raise ValueError("linear_stream: fp8 weight tiles stream non-temporally only (nt=False unsupported)")
-        if wt.shape[1] * 32 != K:
-            raise ValueError(f"linear_stream: x has K={K}, the fp8 tiles K={wt.shape[1] * 32}")
+            raise ValueError(f"linear_stream: {f.name} weight tiles stream non-temporally only (nt=False unsupported)")
+        if wt.shape[1] * f.vk != K:
+            raise ValueError(f"linear_stream: x has K={K}, the {f.name} tiles K={wt.shape[1] * f.vk}")
     N = wt.shape[0] * 32
     plan = stream_plan(M, N, K, max_splits)
     if plan is None:
@@ -442,17 +498,11 @@ def linear_stream(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, nt: bo
             y = torch.empty(M, N // 2 if glu else N, dtype=x.dtype, device=x.device)
         else:
             p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        if w4:  # (the extension takes the raw bytes of both images)
-            ext().wstream_gemm_w4(x, wt.view(torch.uint8), scale.view(torch.uint8), y, p, int(max_splits), bool(glu))
-        elif w8:
-            ext().wstream_gemm_w8(x, wt, scale, y, p, int(max_splits), bool(glu))
-        else:
-            ext().wstream_gemm(x, wt, y, p, int(max_splits), bool(nt), bool(glu))
+        if f.raw:
+            wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
+        ext().wstream_gemm(x, wt, y, p, int(max_splits), bool(nt), bool(glu), scale, f.abi)
         return y if S == 1 else p
-    if w4:
-        w = untile_weight_mxfp4(wt, scale, glu).float()
-    else:
-        w = (untile_weight_fp8(wt, scale, glu) if w8 else untile_weight(wt, glu)).float()
+    w = f.untile(wt, scale, glu).float()
     xf = x.float()
     if S == 1:
         y = xf @ w.t()
@@ -659,12 +709,34 @@ def stream_moe_supported(N: int, K: int) -> bool:
 GROUPED_PIN = True
 
 
-def _expert_scale(fn: str, wt: torch.Tensor, scale: torch.Tensor | None) -> bool:
-    """Whether ``wt`` are fp8 expert tiles; they need their row scales."""
-    w8 = is_fp8_weight(wt)
-    if w8 and scale is None:
-        raise ValueError(f"{fn}: fp8 expert tiles need their row scales (scale=)")
-    return w8
+def tile_experts_as(w: torch.Tensor, weight_dtype: str, glu: bool = False):
+    """Expert weights [E, N, K] -> (tiles [E, ...], scales [E, ...] or None): the format's ``tile`` per expert."""
+    f = weight_format(weight_dtype)
+    wt = st = None
+    for e in range(w.shape[0]):
+        t, s = f.tile(w[e], glu)
+        if wt is None:
+            wt = t.new_empty(w.shape[0], *t.shape)
+            st = None if s is None else s.new_empty(w.shape[0], *s.shape)
+        wt[e].copy_(t)
+        if st is not None:
+            st[e].copy_(s)
+    return wt, st
+
+
+def untile_experts_as(wt: torch.Tensor, scale: torch.Tensor | None, glu: bool = False) -> torch.Tensor:
+    """Row-major bf16 [E, N, K] experts of expert tiles of any format (quantised ones dequantised)."""
+    f = WEIGHT_FORMATS[wt.dtype]
+    return torch.stack([f.untile(wt[e], None if scale is None else scale[e], glu) for e in range(wt.shape[0])])
+
+
+def _expert_format(fn: str, wt: torch.Tensor, scale: torch.Tensor | None):
+    """(format, scale to pass on) of expert tiles; quantised ones need their scales."""
+    f = WEIGHT_FORMATS[wt.dtype]
+    if f.scale_dtype is None:
+        return f, None
+    _check_scale(fn, f, wt, scale)
+    return f, scale
 
 
 def grouped_stream_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: int = 0,
@@ -672,21 +744,16 @@ def grouped_stream_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo:
     """silu(gate) * up for every routed (token, local expert) entry, rows in expert-sorted order [n_ent, F]: the
     weight-streaming grouped kernel on GLU-tiled expert weights (``tile_experts(w13, glu=True)``, or the uint8 tiles
     of ``tile_experts_fp8`` with their row scales ``scale``)."""
-    w8 = _expert_scale("grouped_stream_glu", wt, scale)
+    f, scale = _expert_format("grouped_stream_glu", wt, scale)
     T = x.shape[0]
     n_ent = r.perm_tok.numel()
-    F = wt.shape[1] * 16  # (N / 32 tiles of 32 rows, N = 2 F: either tile format)
+    F = wt.shape[1] * 16  # (N / 32 tiles of 32 rows, N = 2 F: every tile format)
     y = torch.empty(n_ent, F, dtype=x.dtype, device=x.device)
     if _gpu(x):
-        if w8:
-            ext().wstream_grouped_w8(x, wt, scale, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), True, y,
-                                     None, GROUPED_PIN)
-        else:
-            ext().wstream_grouped(x, wt, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), True, y, None,
-                                  GROUPED_PIN)
+        ext().wstream_grouped(x, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), True, y,
+                              None, GROUPED_PIN)
         return y
-    w = untile_experts_fp8(wt, scale, glu=True) if w8 else untile_experts(wt, glu=True)
-    h = ref_grouped(x, w, r, e_lo, gather=True)
+    h = ref_grouped(x, untile_experts_as(wt, scale, glu=True), r, e_lo, gather=True)
     y.copy_(ref.silu_mul(h))
     return y
 
@@ -695,17 +762,12 @@ def grouped_stream_combine(a: torch.Tensor, wt: torch.Tensor, r: "MoERouting", T
                            e_lo: int = 0, scale: torch.Tensor | None = None) -> torch.Tensor:
     """out[token] += w * (a[entry] @ W_e^T) over the local experts' entries (out f32 [T, N], zeroed by the caller).
     ``scale``: the row scales of fp8 expert tiles."""
-    w8 = _expert_scale("grouped_stream_combine", wt, scale)
+    f, scale = _expert_format("grouped_stream_combine", wt, scale)
     if _gpu(a):
-        if w8:
-            ext().wstream_grouped_w8(a, wt, scale, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), False, None,
-                                     out, GROUPED_PIN)
-        else:
-            ext().wstream_grouped(a, wt, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), False, None, out,
-                                  GROUPED_PIN)
+        ext().wstream_grouped(a, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), False, None,
+                              out, GROUPED_PIN)
         return out
-    w = untile_experts_fp8(wt, scale) if w8 else untile_experts(wt)
-    ref.grouped_gemm(a, w, r.perm_tok, r.perm_w, r.expert_off, e_lo, False, None, out)
+    ref.grouped_gemm(a, untile_experts_as(wt, scale), r.perm_tok, r.perm_w, r.expert_off, e_lo, False, None, out)
     return out
 
 

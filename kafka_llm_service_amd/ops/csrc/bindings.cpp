@@ -429,16 +429,69 @@ static std::vector<int64_t> wstream_plan(int64_t M, int64_t N, int64_t K, int64_
   return {mt, kc, s};
 }
 
-// x [M, K] bf16 . W^T with W given wave-tiled as wt [N/32, K/16, 64, 8] (ops.tile_weight). Writes bf16 y [M, N]
-// (splits == 1) or fp32 slabs p [splits, M, N].
+// The A operand of the streaming GEMMs: x [M, K] bf16 on the GPU with 16-B rows
+static void check_stream_x(const char* fn, const at::Tensor& x) {
+  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_LASTDIM(x);
+  TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, fn, ": x must be [M, K] with 16-B rows");
+}
+
+// Weight tiles and their scales against the format fmt (kafka_abi.h WF_*; fp8 and mxfp4 tiles are both uint8
+// [., ., 64, 16], so the caller names it). lead = 0: wt [N/32, K/vk, 64, 8 or 16]; lead = 1: expert tiles with a leading
+// [E_local]. bf16: no scale; fp8: f32 [N] / [E_local, N]; mxfp4: uint8 [N/32, K/64, 32, 2]. Returns vk, the K columns
+// of one 16-B tile vector (16, 32 or 64).
+static int check_wfmt(const char* fn, int64_t fmt, const at::Tensor& wt, const c10::optional<at::Tensor>& scale,
+                      int lead) {
+  TORCH_CHECK(fmt == kafka::WF_BF16 || fmt == kafka::WF_FP8 || fmt == kafka::WF_MXFP4, fn, ": unknown weight format");
+  const bool bf = fmt == kafka::WF_BF16;
+  CHECK_CUDA(wt); CHECK_DT(wt, bf ? at::kBFloat16 : at::kByte);
+  TORCH_CHECK(wt.dim() == 4 + lead && wt.is_contiguous() && wt.size(lead + 2) == 64 && wt.size(lead + 3) == (bf ? 8 : 16),
+              fn, ": wt must be contiguous [N/32, K/16, 64, 8] bf16 or [N/32, K/32 (fp8) or K/64 (mxfp4), 64, 16] uint8",
+              lead ? " per local expert" : "");
+  if (bf) {
+    TORCH_CHECK(!scale.has_value(), fn, ": bf16 tiles take no scale");
+    return 16;
+  }
+  TORCH_CHECK(scale.has_value(), fn, ": quantised tiles need their scales");
+  const at::Tensor& sc = scale.value();
+  TORCH_CHECK(sc.is_contiguous() && sc.device() == wt.device(), fn, ": scale must be contiguous on the weights' device");
+  if (fmt == kafka::WF_FP8) {
+    CHECK_DT(sc, at::kFloat);
+    TORCH_CHECK(sc.dim() == 1 + lead && sc.size(lead) == wt.size(lead) * 32 && (!lead || sc.size(0) == wt.size(0)),
+                fn, ": the scale of fp8 tiles must be f32 [N]", lead ? " per local expert" : "");
+    return 32;
+  }
+  CHECK_DT(sc, at::kByte);
+  TORCH_CHECK(sc.dim() == 4 + lead && sc.size(lead) == wt.size(lead) && sc.size(lead + 1) == wt.size(lead + 1) &&
+                  sc.size(lead + 2) == 32 && sc.size(lead + 3) == 2 && (!lead || sc.size(0) == wt.size(0)),
+              fn, ": the scale of mxfp4 tiles must be uint8 [N/32, K/64, 32, 2]");
+  return 64;
+}
+
+// kw / pin of a planned launch with `chunks` K chunks per split (wstream_gemm_kernel KW / PIN), every format and epilogue
+static void wstream_kw_pin(int mt, int kc, int chunks, int* kw, int* pin) {
+  // two K halves per chunk (8 waves) for 64-row tiles with >= 6 chunks per split: the long streams (gate_up unsplit
+  // with its fused SwiGLU, down) ran 1.6-2.8 % faster in the config sweep, the short ones (qkv, o) slower; headline
+  // +0.24 % (3 / 3 interleaved pairs, profiles/r04/bench_ab_wstream_kw2.jsonl)
+  *kw = mt == 2 && kc == 256 && chunks >= 6 ? 2 : 1;
+  // weight prefetch pinned ahead of the MFMAs (wstream_gemm_kernel PIN) when a split streams >= 3 chunks: -1..-4 us
+  // per projection at 64 rows, -4..-7 us at 97..128 rows; not for 96-row tiles (their 348 registers leave one wave
+  // per SIMD and the longer live ranges lose) nor 2-chunk splits (o at 64 rows: +0.9 us)
+  // (profiles/r05/wstream_sweep_pin.jsonl)
+  *pin = mt != 3 && chunks >= 3 ? 1 : 0;
+}
+
+// x [M, K] bf16 . W^T with W given wave-tiled in format fmt: wt [N/32, K/16, 64, 8] bf16 (ops.tile_weight), or the raw
+// bytes of fp8 tiles [N/32, K/32, 64, 16] with their f32 row scales [N] (ops.tile_weight_fp8) or of MXFP4 tiles
+// [N/32, K/64, 64, 16] with their e8m0 block exponents [N/32, K/64, 32, 2] (ops.tile_weight_mxfp4). Writes bf16 y [M, N]
+// (splits == 1) or fp32 slabs p [splits, M, N]; same plan, outputs and kw / pin rules for every format. scale and fmt
+// come last and default to bf16 tiles without a scale, the call this entry has always taken.
 static void wstream_gemm(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> y, c10::optional<at::Tensor> p,
-                         int64_t max_splits, bool nt, bool glu) {
-  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_DT(wt, at::kBFloat16); CHECK_LASTDIM(x);
-  TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "wstream_gemm: x must be [M, K] with 16-B rows");
-  TORCH_CHECK(wt.dim() == 4 && wt.is_contiguous() && wt.size(2) == 64 && wt.size(3) == 8,
-              "wstream_gemm: wt must be contiguous [N/32, K/16, 64, 8]");
+                         int64_t max_splits, bool nt, bool glu, c10::optional<at::Tensor> scale, int64_t fmt) {
+  check_stream_x("wstream_gemm", x);
+  const int vk = check_wfmt("wstream_gemm", fmt, wt, scale, 0);
   const int M = x.size(0), K = x.size(1), N = wt.size(0) * 32;
-  TORCH_CHECK(wt.size(1) * 16 == K, "wstream_gemm: K mismatch");
+  TORCH_CHECK(wt.size(1) * vk == K, "wstream_gemm: K mismatch (x has K = ", K, ", the tiles ", wt.size(1) * vk, ")");
+  TORCH_CHECK(nt || fmt == kafka::WF_BF16, "wstream_gemm: quantised tiles stream non-temporally only");
   TORCH_CHECK(!glu || N % 64 == 0, "wstream_gemm: GLU weights need N % 64 == 0");
   int mt = 0, kc = 0, s = 0;
   TORCH_CHECK(kafka_wstream_plan(M, N, K, (int)max_splits, &mt, &kc, &s) == 0, "wstream_gemm: unsupported shape");
@@ -448,106 +501,22 @@ static void wstream_gemm(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> 
   if (s == 1) {
     // glu + one split: y is the activated [M, N/2]; otherwise [M, N] in gate | up column order
     TORCH_CHECK(y.has_value(), "wstream_gemm: y required for a single split");
-    CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
+    CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
     TORCH_CHECK(y->dim() == 2 && y->size(0) == M && y->size(1) == (glu ? N / 2 : N), "wstream_gemm: y shape");
     yp = bptr(y.value());
     ldy = y->stride(0);
   } else {
     TORCH_CHECK(p.has_value(), "wstream_gemm: slab output required");
-    CHECK_DT(p.value(), at::kFloat);
+    CHECK_CUDA(p.value()); CHECK_DT(p.value(), at::kFloat);
     TORCH_CHECK(p->is_contiguous() && p->dim() == 3 && p->size(0) == s && p->size(1) == M && p->size(2) == N,
                 "wstream_gemm: slab shape must be [splits, M, N]");
     pp = p->data_ptr<float>();
   }
-  // two K halves per chunk (8 waves) for 64-row tiles with >= 6 chunks per split: the long streams (gate_up unsplit
-  // with its fused SwiGLU, down) ran 1.6-2.8 % faster in the config sweep, the short ones (qkv, o) slower; headline
-  // +0.24 % (3 / 3 interleaved pairs, profiles/r04/bench_ab_wstream_kw2.jsonl)
-  const int kw = mt == 2 && kc == 256 && K / s / kc >= 6 ? 2 : 1;
-  // weight prefetch pinned ahead of the MFMAs (wstream_gemm_kernel PIN) when a split streams >= 3 chunks: -1..-4 us
-  // per projection at 64 rows, -4..-7 us at 97..128 rows; not for 96-row tiles (their 348 registers leave one wave
-  // per SIMD and the longer live ranges lose) nor 2-chunk splits (o at 64 rows: +0.9 us)
-  // (profiles/r05/wstream_sweep_pin.jsonl)
-  const int pin = mt != 3 && K / s / kc >= 3 ? 1 : 0;
-  CHECK_HIP(kafka_launch_wstream_gemm(bptr(x), x.stride(0), bptr(wt), M, N, K, mt, kc, s, nt ? 1 : 0, kw, pin,
-                                      glu ? 1 : 0,
-                                      yp, ldy, pp, cur_stream()));
-}
-
-// The same GEMM on fp8 weights: wt8 [N/32, K/32, 64, 16] e4m3 bytes and st [N] fp32 power-of-two row scales
-// (ops.tile_weight_fp8). Same plan, outputs and kw / pin rules as wstream_gemm.
-static void wstream_gemm_w8(at::Tensor x, at::Tensor wt8, at::Tensor st, c10::optional<at::Tensor> y,
-                            c10::optional<at::Tensor> p, int64_t max_splits, bool glu) {
-  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_CUDA(wt8); CHECK_DT(wt8, at::kByte); CHECK_CUDA(st);
-  CHECK_DT(st, at::kFloat); CHECK_LASTDIM(x);
-  TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "wstream_gemm_w8: x must be [M, K] with 16-B rows");
-  TORCH_CHECK(wt8.dim() == 4 && wt8.is_contiguous() && wt8.size(2) == 64 && wt8.size(3) == 16,
-              "wstream_gemm_w8: wt8 must be contiguous [N/32, K/32, 64, 16]");
-  const int M = x.size(0), K = x.size(1), N = wt8.size(0) * 32;
-  TORCH_CHECK(K % 32 == 0 && wt8.size(1) * 32 == K, "wstream_gemm_w8: K mismatch (K % 32 == 0)");
-  TORCH_CHECK(st.dim() == 1 && st.is_contiguous() && st.size(0) == N, "wstream_gemm_w8: st must be contiguous [N]");
-  TORCH_CHECK(!glu || N % 64 == 0, "wstream_gemm_w8: GLU weights need N % 64 == 0");
-  int mt = 0, kc = 0, s = 0;
-  TORCH_CHECK(kafka_wstream_plan(M, N, K, (int)max_splits, &mt, &kc, &s) == 0, "wstream_gemm_w8: unsupported shape");
-  bf16* yp = nullptr;
-  int64_t ldy = 0;
-  float* pp = nullptr;
-  if (s == 1) {
-    TORCH_CHECK(y.has_value(), "wstream_gemm_w8: y required for a single split");
-    CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
-    TORCH_CHECK(y->dim() == 2 && y->size(0) == M && y->size(1) == (glu ? N / 2 : N), "wstream_gemm_w8: y shape");
-    yp = bptr(y.value());
-    ldy = y->stride(0);
-  } else {
-    TORCH_CHECK(p.has_value(), "wstream_gemm_w8: slab output required");
-    CHECK_CUDA(p.value()); CHECK_DT(p.value(), at::kFloat);
-    TORCH_CHECK(p->is_contiguous() && p->dim() == 3 && p->size(0) == s && p->size(1) == M && p->size(2) == N,
-                "wstream_gemm_w8: slab shape must be [splits, M, N]");
-    pp = p->data_ptr<float>();
-  }
-  const int kw = mt == 2 && kc == 256 && K / s / kc >= 6 ? 2 : 1;  // (the wstream_gemm rules above)
-  const int pin = mt != 3 && K / s / kc >= 3 ? 1 : 0;
-  CHECK_HIP(kafka_launch_wstream_gemm_w8(bptr(x), x.stride(0), wt8.data_ptr<uint8_t>(), st.data_ptr<float>(), M, N, K,
-                                         mt, kc, s, kw, pin, glu ? 1 : 0, yp, ldy, pp, cur_stream()));
-}
-
-// The same GEMM on MXFP4 weights, both images as raw bytes: wt4 [N/32, K/64, 64, 16] e2m1 nibble pairs and se
-// [N/32, K/64, 32, 2] e8m0 block exponents (ops.tile_weight_mxfp4, viewed as uint8). Same plan, outputs and kw / pin
-// rules as wstream_gemm.
-static void wstream_gemm_w4(at::Tensor x, at::Tensor wt4, at::Tensor se, c10::optional<at::Tensor> y,
-                            c10::optional<at::Tensor> p, int64_t max_splits, bool glu) {
-  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_CUDA(wt4); CHECK_DT(wt4, at::kByte); CHECK_CUDA(se);
-  CHECK_DT(se, at::kByte); CHECK_LASTDIM(x);
-  TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "wstream_gemm_w4: x must be [M, K] with 16-B rows");
-  TORCH_CHECK(wt4.dim() == 4 && wt4.is_contiguous() && wt4.size(2) == 64 && wt4.size(3) == 16,
-              "wstream_gemm_w4: wt4 must be contiguous [N/32, K/64, 64, 16]");
-  const int M = x.size(0), K = x.size(1), N = wt4.size(0) * 32;
-  TORCH_CHECK(K % 64 == 0 && wt4.size(1) * 64 == K, "wstream_gemm_w4: K mismatch (K % 64 == 0)");
-  TORCH_CHECK(se.dim() == 4 && se.is_contiguous() && se.size(0) == wt4.size(0) && se.size(1) == wt4.size(1) &&
-                  se.size(2) == 32 && se.size(3) == 2,
-              "wstream_gemm_w4: se must be contiguous [N/32, K/64, 32, 2]");
-  TORCH_CHECK(!glu || N % 64 == 0, "wstream_gemm_w4: GLU weights need N % 64 == 0");
-  int mt = 0, kc = 0, s = 0;
-  TORCH_CHECK(kafka_wstream_plan(M, N, K, (int)max_splits, &mt, &kc, &s) == 0, "wstream_gemm_w4: unsupported shape");
-  bf16* yp = nullptr;
-  int64_t ldy = 0;
-  float* pp = nullptr;
-  if (s == 1) {
-    TORCH_CHECK(y.has_value(), "wstream_gemm_w4: y required for a single split");
-    CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
-    TORCH_CHECK(y->dim() == 2 && y->size(0) == M && y->size(1) == (glu ? N / 2 : N), "wstream_gemm_w4: y shape");
-    yp = bptr(y.value());
-    ldy = y->stride(0);
-  } else {
-    TORCH_CHECK(p.has_value(), "wstream_gemm_w4: slab output required");
-    CHECK_CUDA(p.value()); CHECK_DT(p.value(), at::kFloat);
-    TORCH_CHECK(p->is_contiguous() && p->dim() == 3 && p->size(0) == s && p->size(1) == M && p->size(2) == N,
-                "wstream_gemm_w4: slab shape must be [splits, M, N]");
-    pp = p->data_ptr<float>();
-  }
-  const int kw = mt == 2 && kc == 256 && K / s / kc >= 6 ? 2 : 1;  // (the wstream_gemm rules above)
-  const int pin = mt != 3 && K / s / kc >= 3 ? 1 : 0;
-  CHECK_HIP(kafka_launch_wstream_gemm_w4(bptr(x), x.stride(0), wt4.data_ptr<uint8_t>(), se.data_ptr<uint8_t>(), M, N,
-                                         K, mt, kc, s, kw, pin, glu ? 1 : 0, yp, ldy, pp, cur_stream()));
+  int kw = 1, pin = 0;
+  wstream_kw_pin(mt, kc, K / s / kc, &kw, &pin);
+  CHECK_HIP(kafka_launch_wstream_gemm(bptr(x), x.stride(0), (int)fmt, wt.data_ptr(),
+                                      scale.has_value() ? scale->data_ptr() : nullptr, M, N, K, mt, kc, s, nt ? 1 : 0,
+                                      kw, pin, glu ? 1 : 0, yp, ldy, pp, cur_stream()));
 }
 
 // Fused decode-layer GEMMs (wstream_gemm.hip FIN_*): fin 1 = o / down with the split-K finisher doing the residual
@@ -564,8 +533,8 @@ static void wstream_fin(int64_t fin, at::Tensor x, at::Tensor wt, c10::optional<
                         c10::optional<at::Tensor> slots, int64_t Hq, int64_t Hkv, int64_t max_splits,
                         c10::optional<at::Tensor> stamps) {
   TORCH_CHECK(fin >= 1 && fin <= 3, "wstream_fin: fin must be 1, 2 or 3");
-  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_DT(wt, at::kBFloat16); CHECK_LASTDIM(x);
-  TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "wstream_fin: x must be [M, K] with 16-B rows");
+  check_stream_x("wstream_fin", x);
+  CHECK_DT(wt, at::kBFloat16);
   TORCH_CHECK(wt.dim() == 4 && wt.is_contiguous() && wt.size(2) == 64 && wt.size(3) == 8,
               "wstream_fin: wt must be contiguous [N/32, K/16, 64, 8]");
   const int M = x.size(0), K = x.size(1), N = wt.size(0) * 32;
@@ -590,8 +559,8 @@ static void wstream_fin(int64_t fin, at::Tensor x, at::Tensor wt, c10::optional<
     fa.nss = ss_in->size(0);
     fa.ss_ld = ss_in->stride(0);
   }
-  const int kw = mt == 2 && kc == 256 && K / s / kc >= 6 ? 2 : 1;  // (the wstream_gemm rules above)
-  const int pin = mt != 3 && K / s / kc >= 3 ? 1 : 0;
+  int kw = 1, pin = 0;
+  wstream_kw_pin(mt, kc, K / s / kc, &kw, &pin);
   bf16* yp = nullptr;
   int64_t ldy = 0;
   float* pp = nullptr;
@@ -710,32 +679,25 @@ static void wstream_gemm_cfg(at::Tensor x, at::Tensor wt, c10::optional<at::Tens
     TORCH_CHECK(p.has_value() && p->is_contiguous() && p->numel() == s * M * N, "wstream_gemm_cfg: p");
     CHECK_DT(p.value(), at::kFloat);
   }
-  CHECK_HIP(kafka_launch_wstream_gemm(bptr(x), x.stride(0), bptr(wt), M, N, K, (int)mt, (int)kc, (int)s, nt ? 1 : 0,
-                                      (int)kw, (int)pin, 0,
+  CHECK_HIP(kafka_launch_wstream_gemm(bptr(x), x.stride(0), kafka::WF_BF16, wt.data_ptr(), nullptr, M, N, K, (int)mt,
+                                      (int)kc, (int)s, nt ? 1 : 0, (int)kw, (int)pin, 0,
                                       s == 1 ? bptr(y.value()) : nullptr, s == 1 ? y->stride(0) : 0,
                                       s == 1 ? nullptr : p->data_ptr<float>(), cur_stream()));
 }
 
-// Expert MLP halves on wave-tiled expert weights wt [E_local, N/32, K/16, 64, 8] (ops.tile_experts). glu: gate_up
-// with fused SwiGLU into y [n_ent, N/2]; else down with the weighted combine into out f32 [T, N]. max_rows = T
+// Expert MLP halves on wave-tiled expert weights in format fmt: wt [E_local, N/32, K/16, 64, 8] bf16 (ops.tile_experts)
+// or uint8 [E_local, N/32, K/32, 64, 16] fp8 tiles with their row scales f32 [E_local, N] (ops.tile_experts_fp8). glu:
+// gate_up with fused SwiGLU into y [n_ent, N/2]; else down with the weighted combine into out f32 [T, N]. max_rows = T
 // bounds every expert segment (a token picks an expert at most once).
-// st: the fp8 variant (wstream_grouped_w8 below): wt uint8 [E_local, N/32, K/32, 64, 16] and st f32 [E_local, N].
-static void wstream_grouped_impl(at::Tensor x, at::Tensor wt, const at::Tensor* st, at::Tensor perm_tok,
-                                 at::Tensor perm_w, at::Tensor expert_off, int64_t e_lo, int64_t max_rows, bool gather,
-                                 c10::optional<at::Tensor> y, c10::optional<at::Tensor> out, bool pin) {
-  const bool w8 = st != nullptr;
-  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_DT(wt, w8 ? at::kByte : at::kBFloat16); CHECK_LASTDIM(x);
+static void wstream_grouped(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> scale, int64_t fmt,
+                            at::Tensor perm_tok, at::Tensor perm_w, at::Tensor expert_off, int64_t e_lo,
+                            int64_t max_rows, bool gather, c10::optional<at::Tensor> y, c10::optional<at::Tensor> out,
+                            bool pin) {
+  check_stream_x("wstream_grouped", x);
+  TORCH_CHECK(fmt != kafka::WF_MXFP4, "wstream_grouped: no MXFP4 expert tiles");
+  const int vk = check_wfmt("wstream_grouped", fmt, wt, scale, 1);
   CHECK_DT(perm_tok, at::kInt); CHECK_DT(perm_w, at::kFloat); CHECK_DT(expert_off, at::kInt);
-  TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "wstream_grouped: x must be [rows, K] with 16-B rows");
-  TORCH_CHECK(wt.dim() == 5 && wt.is_contiguous() && wt.size(3) == 64 && wt.size(4) == (w8 ? 16 : 8),
-              "wstream_grouped: wt must be contiguous [E_local, N/32, K/16, 64, 8] (fp8: [E_local, N/32, K/32, 64, 16])");
-  const int E_local = wt.size(0), N = wt.size(1) * 32, K = wt.size(2) * (w8 ? 32 : 16);
-  if (w8) {
-    CHECK_DT(*st, at::kFloat);
-    TORCH_CHECK(st->dim() == 2 && st->is_contiguous() && st->size(0) == E_local && st->size(1) == N &&
-                    st->device() == wt.device(),
-                "wstream_grouped_w8: st must be contiguous [E_local, N] on the weights' device");
-  }
+  const int E_local = wt.size(0), N = wt.size(1) * 32, K = wt.size(2) * vk;
   TORCH_CHECK(x.size(1) == K && K % 256 == 0 && N % 64 == 0, "wstream_grouped: K / N");
   const int64_t n_ent = perm_tok.numel();
   TORCH_CHECK(perm_w.numel() == n_ent && perm_tok.is_contiguous() && perm_w.is_contiguous(), "wstream_grouped: perm");
@@ -760,30 +722,11 @@ static void wstream_grouped_impl(at::Tensor x, at::Tensor wt, const at::Tensor* 
     op = out->data_ptr<float>();
     ldo = out->stride(0);
   }
-  if (w8)
-    CHECK_HIP(kafka_launch_wstream_grouped_w8(bptr(x), x.stride(0), wt.data_ptr<uint8_t>(), st->data_ptr<float>(),
-                                              E_local, N, K, perm_tok.data_ptr<int>(), perm_w.data_ptr<float>(),
-                                              expert_off.data_ptr<int>(), (int)e_lo, (int)max_rows, gather ? 1 : 0,
-                                              yp, ldy, op, ldo, pin ? 1 : 0, cur_stream()));
-  else
-    CHECK_HIP(kafka_launch_wstream_grouped(bptr(x), x.stride(0), bptr(wt), E_local, N, K, perm_tok.data_ptr<int>(),
-                                           perm_w.data_ptr<float>(), expert_off.data_ptr<int>(), (int)e_lo,
-                                           (int)max_rows, gather ? 1 : 0, yp, ldy, op, ldo, pin ? 1 : 0,
-                                           cur_stream()));
-}
-
-static void wstream_grouped(at::Tensor x, at::Tensor wt, at::Tensor perm_tok, at::Tensor perm_w, at::Tensor expert_off,
-                            int64_t e_lo, int64_t max_rows, bool gather, c10::optional<at::Tensor> y,
-                            c10::optional<at::Tensor> out, bool pin) {
-  wstream_grouped_impl(x, wt, nullptr, perm_tok, perm_w, expert_off, e_lo, max_rows, gather, y, out, pin);
-}
-
-// The same on fp8 expert tiles wt8 [E_local, N/32, K/32, 64, 16] with row scales st [E_local, N]
-// (ops.tile_experts_fp8).
-static void wstream_grouped_w8(at::Tensor x, at::Tensor wt8, at::Tensor st, at::Tensor perm_tok, at::Tensor perm_w,
-                               at::Tensor expert_off, int64_t e_lo, int64_t max_rows, bool gather,
-                               c10::optional<at::Tensor> y, c10::optional<at::Tensor> out, bool pin) {
-  wstream_grouped_impl(x, wt8, &st, perm_tok, perm_w, expert_off, e_lo, max_rows, gather, y, out, pin);
+  CHECK_HIP(kafka_launch_wstream_grouped(bptr(x), x.stride(0), (int)fmt, wt.data_ptr(),
+                                         scale.has_value() ? scale->data_ptr() : nullptr, E_local, N, K,
+                                         perm_tok.data_ptr<int>(), perm_w.data_ptr<float>(), expert_off.data_ptr<int>(),
+                                         (int)e_lo, (int)max_rows, gather ? 1 : 0, yp, ldy, op, ldo, pin ? 1 : 0,
+                                         cur_stream()));
 }
 
 // y [M, N] bf16 = sum over the slabs p [S, M, N]
@@ -1057,12 +1000,8 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("token_logprobs", &token_logprobs, py::arg("logits"), py::arg("tokens"), py::arg("rows"), py::arg("k"),
         py::arg("tok_lp"), py::arg("top_lp"), py::arg("top_id"), py::arg("ws") = py::none(), py::arg("nsplit") = 1);
   m.def("wstream_plan", &wstream_plan);
-  m.def("wstream_gemm", &wstream_gemm, py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"),
-        py::arg("max_splits"), py::arg("nt"), py::arg("glu"));
-  m.def("wstream_gemm_w8", &wstream_gemm_w8, py::arg("x"), py::arg("wt8"), py::arg("st"), py::arg("y"), py::arg("p"),
-        py::arg("max_splits"), py::arg("glu"));
-  m.def("wstream_gemm_w4", &wstream_gemm_w4, py::arg("x"), py::arg("wt4"), py::arg("se"), py::arg("y"), py::arg("p"),
-        py::arg("max_splits"), py::arg("glu"));
+  m.def("wstream_gemm", &wstream_gemm, py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"), py::arg("max_splits"),
+        py::arg("nt"), py::arg("glu"), py::arg("scale") = py::none(), py::arg("fmt") = (int64_t)kafka::WF_BF16);
   m.def("wstream_fin", &wstream_fin, py::arg("fin"), py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"),
         py::arg("tickets"), py::arg("ss_in"), py::arg("eps"), py::arg("resid"), py::arg("nw"), py::arg("xn"),
         py::arg("ss_out"), py::arg("positions"), py::arg("cos_sin"), py::arg("q_out"), py::arg("k_cache"),
@@ -1072,12 +1011,9 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("skinny_gemm", &skinny_gemm);
   m.def("wstream_gemm_cfg", &wstream_gemm_cfg);
   m.def("slab_reduce", &slab_reduce);
-  m.def("wstream_grouped", &wstream_grouped, py::arg("x"), py::arg("wt"), py::arg("perm_tok"), py::arg("perm_w"),
-        py::arg("expert_off"), py::arg("e_lo"), py::arg("max_rows"), py::arg("gather"), py::arg("y"), py::arg("out"),
-        py::arg("pin") = true);
-  m.def("wstream_grouped_w8", &wstream_grouped_w8, py::arg("x"), py::arg("wt8"), py::arg("st"), py::arg("perm_tok"),
-        py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("max_rows"), py::arg("gather"),
-        py::arg("y"), py::arg("out"), py::arg("pin") = true);
+  m.def("wstream_grouped", &wstream_grouped, py::arg("x"), py::arg("wt"), py::arg("scale"), py::arg("fmt"),
+        py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("max_rows"),
+        py::arg("gather"), py::arg("y"), py::arg("out"), py::arg("pin") = true);
   m.def("moe_route", &moe_route);
   m.def("cu_mask_stream", &cu_mask_stream);
   m.def("stream_cu_mask", &stream_cu_mask);

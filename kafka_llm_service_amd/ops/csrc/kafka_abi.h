@@ -5,6 +5,7 @@
 // with shifted arguments. No device code and no torch in here.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
 
 // bf16 storage: the clang scalar type in the kernel units, its raw 16 bits on the g++ side
@@ -49,10 +50,18 @@ struct DecodeItem {
 static_assert(sizeof(AttnWorkItem) == ITEM_INTS * sizeof(int), "AttnWorkItem is one row of the items tensor");
 static_assert(sizeof(DecodeItem) == ITEM_INTS * sizeof(int), "DecodeItem is one row of the items tensor");
 
+// ---- weight tile formats of the streaming GEMMs (wstream_gemm.hip WFMT; ops.WEIGHT_FORMATS) ----------------------
+// bf16 tiles [N/32][K/16][64 lanes][8]; fp8: e4m3 bytes [N/32][K/32][64][16] + fp32 row scales [N]; MXFP4: e2m1 bytes
+// [N/32][K/64][64][16] + e8m0 block exponents [N/32][K/64][32][2]
+enum { WF_BF16 = 0, WF_FP8 = 1, WF_MXFP4 = 2 };
+
 // ---- arguments of the fused decode-layer GEMM epilogues (wstream_gemm.hip FIN_*) ---------------------------------
 struct FinArgs {
   int* tickets;                 // [N / 128] zeroed once, re-armed by each column block's finisher
-  const float* ss_in;           // [nss][ss_ld] partial sums of h^2 of X's rows (nullptr: X is already normalised)
+  union {
+    const float* ss_in;         // [nss][ss_ld] partial sums of h^2 of X's rows (nullptr: X is already normalised)
+    const void* wscale;         // FIN_NONE on quantised tiles: their scales (fp8 row scales / mxfp4 exponent image)
+  };
   int nss, ss_ld;
   float inv_d, eps;
   bf16* resid;                  // FIN_RES: residual stream [M, N] (row stride ldr), updated in place
@@ -73,6 +82,7 @@ struct FinArgs {
   uint64_t* stamps;             // optional phase stamps [grid][8] (100 MHz clock; benchmarks/fused_bench.py)
   int* err;                     // bit 0 set if a finisher could not reach a split's slab (wstream_gemm.hip "home XCD")
 };
+static_assert(sizeof(FinArgs) == 168 && offsetof(FinArgs, ss_in) == 8, "the union must not move the kernels' arguments");
 
 }  // namespace kafka
 
@@ -155,20 +165,13 @@ hipError_t kafka_launch_token_logprobs(const void* logits, bool is_bf16, int64_t
 // Host plan: row tiles MT, K chunk KC and split count S for a shape; returns 0 if supported (mirrored by
 // ops.stream_plan). max_splits caps S (1 forces a direct bf16 output).
 int kafka_wstream_plan(int M, int N, int K, int max_splits, int* mt, int* kc, int* splits);
-hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int mt, int kc,
-                                     int splits, int nt, int kw, int pin, int glu, bf16* Y, int64_t ldy, float* P,
-                                     hipStream_t st);
-// fp8 weights: Wt8 [N/32][K/32][64 lanes][16] e4m3 bytes (ops.tile_weight_fp8: a lane's 16 B are the B fragments of
-// two k-steps), St [N] fp32 power-of-two row scales in tile order; plans, configurations and outputs as above
-hipError_t kafka_launch_wstream_gemm_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St, int M, int N,
-                                        int K, int mt, int kc, int splits, int kw, int pin, int glu, bf16* Y,
-                                        int64_t ldy, float* P, hipStream_t st);
-// MXFP4 weights: Wt4 [N/32][K/64][64 lanes][16] e2m1 bytes (ops.tile_weight_mxfp4: a lane's 16 B are the B fragments of
-// four k-steps, low nibble first), Se [N/32][K/64][32 rows][2] e8m0 block exponents (bias 127, in [7, 247]); plans,
-// configurations and outputs as above
-hipError_t kafka_launch_wstream_gemm_w4(const bf16* X, int64_t ldx, const uint8_t* Wt4, const uint8_t* Se, int M, int N,
-                                        int K, int mt, int kc, int splits, int kw, int pin, int glu, bf16* Y,
-                                        int64_t ldy, float* P, hipStream_t st);
+// wfmt (WF_*) names the layout of Wt and scale: bf16 tiles and no scale; fp8 tiles (ops.tile_weight_fp8: a lane's
+// 16 B are the B fragments of two k-steps) with St [N] fp32 power-of-two row scales in tile order; MXFP4 tiles
+// (ops.tile_weight_mxfp4: four k-steps per 16 B, low nibble first) with Se, the e8m0 block exponents (bias 127, in
+// [7, 247]). Same plans, configurations and outputs; the quantised formats need nt.
+hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale, int M,
+                                     int N, int K, int mt, int kc, int splits, int nt, int kw, int pin, int glu,
+                                     bf16* Y, int64_t ldy, float* P, hipStream_t st);
 // Fused decode-layer GEMMs (FIN_RES / FIN_ROPE / FIN_GLU): one row tile (M <= 128), N % 128 == 0, S in
 // {1, 2, 4, 8}; P = [S][M][N] fp32 scratch (unused for S == 1); FIN_GLU needs S == 1.
 hipError_t kafka_launch_wstream_fin(int fin, const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int mt,
@@ -178,16 +181,12 @@ hipError_t kafka_launch_slab_reduce(const float* P, int S, int M, int N, bf16* Y
 // Grouped streaming GEMM for the expert MLP (see wstream_grouped_kernel). max_rows bounds any expert's segment
 // (the token count T: a token picks an expert at most once); glu: gate_up with fused SwiGLU into Y [n_ent, N/2];
 // else combine into out_f32 [T, N].
-hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, const bf16* Wt, int e_local, int N, int K,
-                                        const int* perm_tok, const float* perm_w, const int* expert_off, int e_lo,
-                                        int max_rows, int gather, bf16* Y, int64_t ldy, float* out, int64_t ldo,
-                                        int pin, hipStream_t st);
-// fp8 expert weights: Wt8 [E_local][N/32][K/32][64 lanes][16] e4m3 bytes and St [E_local][N] fp32 power-of-two row
-// scales in tile order (ops.tile_experts_fp8), both indexed by the local expert; grid, row tiles and outputs as above
-hipError_t kafka_launch_wstream_grouped_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St,
-                                           int e_local, int N, int K, const int* perm_tok, const float* perm_w,
-                                           const int* expert_off, int e_lo, int max_rows, int gather, bf16* Y,
-                                           int64_t ldy, float* out, int64_t ldo, int pin, hipStream_t st);
+// wfmt: WF_BF16 (Wt [E_local][N/32][K/16][64 lanes][8], no scale) or WF_FP8 (e4m3 bytes [E_local][N/32][K/32][64][16]
+// and St [E_local][N] fp32 power-of-two row scales in tile order, ops.tile_experts_fp8), both indexed by the local expert.
+hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale,
+                                        int e_local, int N, int K, const int* perm_tok, const float* perm_w,
+                                        const int* expert_off, int e_lo, int max_rows, int gather, bf16* Y,
+                                        int64_t ldy, float* out, int64_t ldo, int pin, hipStream_t st);
 
 // ---- skinny_gemm.hip
 // Split plan for a shape (mirrored by ops.skinny_plan): the fewest power-of-two splits that give >= 192 workgroups

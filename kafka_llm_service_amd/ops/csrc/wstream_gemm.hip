@@ -220,28 +220,38 @@ __device__ __forceinline__ void fin_rope(const float* tp, const float* P, int by
 // stays because dropping it changes register allocation — MT = 3 FIN_GLU gains 4 VGPR spills — which wants its own
 // measurement.)
 enum { WIDE_P = 1, WIDE_Y = 2 };
-// W8 (fp8 weights, ops.tile_weight_fp8): Wt is the e4m3 image Wt8[N/32][K/32][64 lanes][16 B] — bytes 0..7 of lane
-// (r, h) of tile (nb, kb2) = W[32 nb + r][32 kb2 + 8 h : +8] (k-step 2 kb2), bytes 8..15 the same 8 columns 16 further
-// (k-step 2 kb2 + 1) — so one 16-B load per lane carries the B fragments of TWO k-steps and a wave-instruction is
-// still one contiguous 1 KB run: half the loads, half the prefetch registers, half the bytes. St[32 nb + r] is the
-// power-of-two scale of the lane's row; it is the scale operand of v_cvt_scalef32_pk_bf16_fp8 (dq8), so the B
-// fragments are the exact bf16 values e4m3 * 2^e, the MFMA stays bf16 and the accumulators hold true values: every
-// epilogue is shared with the bf16 kernel. St travels in fa.ss_in (W8 is FIN_NONE only, where no epilogue reads it), so
-// the kernel's argument block — and with it every bf16 instantiation — is byte for byte what it was without W8.
+// WFMT (kafka_abi.h WF_*): the format of the weight tiles. Every format is a stream of 16-B vectors per lane, a
+// wave-instruction one contiguous 1 KB run; a vector carries the B fragments of wf_ksteps(WFMT) k-steps, and the
+// quantised formats are dequantised to the exact bf16 values right before their MFMAs, so MFMA, accumulators and
+// epilogues are the bf16 kernel's. The quantised formats are FIN_NONE and NT only.
 //
-// W4 (MXFP4 weights, ops.tile_weight_mxfp4): Wt is the e2m1 image Wt4[N/32][K/64][64 lanes][16 B] — bytes 4j..4j+3
+// WF_FP8 (ops.tile_weight_fp8): Wt is the e4m3 image Wt8[N/32][K/32][64 lanes][16 B] — bytes 0..7 of lane
+// (r, h) of tile (nb, kb2) = W[32 nb + r][32 kb2 + 8 h : +8] (k-step 2 kb2), bytes 8..15 the same 8 columns 16 further
+// (k-step 2 kb2 + 1) — so one 16-B load per lane carries the B fragments of TWO k-steps: half the loads, half the
+// prefetch registers, half the bytes. St[32 nb + r] is the power-of-two scale of the lane's row; it is the scale
+// operand of v_cvt_scalef32_pk_bf16_fp8 (dq8), so the B fragments are the exact bf16 values e4m3 * 2^e.
+//
+// WF_MXFP4 (ops.tile_weight_mxfp4): Wt is the e2m1 image Wt4[N/32][K/64][64 lanes][16 B] — bytes 4j..4j+3
 // (dword j = 0..3) of lane (r, h) of tile (nb, kb4) = the eight nibbles W[32 nb + r][64 kb4 + 16 j + 8 h : +8], low
-// nibble first (k-step 4 kb4 + j) — so one 16-B load per lane carries the B fragments of FOUR k-steps and a
-// wave-instruction is still one contiguous 1 KB run: a quarter of the loads, prefetch registers and bytes. The block
-// scales are the e8m0 image Se[N/32][K/64][32 rows][2 B]: the two bytes of (nb, kb4, r) are the exponents of columns
-// 64 kb4 : +32 (dwords 0, 1) and 64 kb4 + 32 : +32 (dwords 2, 3) of that row. The image does not depend on the plan
-// (MT, KC, KW only decide how many (nb, kb4) groups a wave walks per chunk); a lane fetches one 2-B load per weight
-// vector, and a wave's load is one contiguous 64-B run (both h halves read the same bytes). The scale loads are issued
-// with the weights, ahead of them and under the same PIN fence, stay raw until their vector is dequantised, and become
-// fp32 with a shift (uint32(e) << 23: e is clamped to [7, 247] by the quantiser). dq4 (v_cvt_scalef32_pk_bf16_fp4)
-// makes the exact bf16 values e2m1 * 2^e, so MFMA, accumulators and epilogues are the bf16 kernel's. Se travels in
-// fa.ss_in like St; FIN_NONE and NT only.
-template <int MT, int KC, bool NT, int KW, bool PIN, int FIN = FIN_NONE, bool W8 = false, bool W4 = false>
+// nibble first (k-step 4 kb4 + j) — so one 16-B load per lane carries the B fragments of FOUR k-steps: a quarter of
+// the loads, prefetch registers and bytes. The block scales are the e8m0 image Se[N/32][K/64][32 rows][2 B]: the two
+// bytes of (nb, kb4, r) are the exponents of columns 64 kb4 : +32 (dwords 0, 1) and 64 kb4 + 32 : +32 (dwords 2, 3) of
+// that row. The image does not depend on the plan (MT, KC, KW only decide how many (nb, kb4) groups a wave walks per
+// chunk); a lane fetches one 2-B load per weight vector, and a wave's load is one contiguous 64-B run (both h halves
+// read the same bytes). The scale loads are issued with the weights, ahead of them and under the same PIN fence, stay
+// raw until their vector is dequantised, and become fp32 with a shift (uint32(e) << 23: e is clamped to [7, 247] by
+// the quantiser). dq4 (v_cvt_scalef32_pk_bf16_fp4) makes the exact bf16 values e2m1 * 2^e.
+//
+// The argument list does not depend on WFMT: the scales (St / Se) travel in fa.wscale, the union partner of fa.ss_in
+// (the quantised formats are FIN_NONE, where no epilogue reads ss_in), so the kernel's argument block — and with it
+// every bf16 instantiation's register counts and occupancy — is byte for byte what it was before the quantised formats
+// (profiles/wfmt/resource_usage.txt).
+constexpr int wf_ksteps(int wfmt) { return wfmt == WF_MXFP4 ? 4 : (wfmt == WF_FP8 ? 2 : 1); }  // k-steps per 16-B vector
+constexpr int wf_vshift(int wfmt) { return wfmt == WF_MXFP4 ? 6 : (wfmt == WF_FP8 ? 5 : 4); }  // log2 of its K columns
+template <int WFMT>
+using wf_vec = typename std::conditional<WFMT == WF_BF16, bf16x8, u32x4>::type;
+
+template <int MT, int KC, bool NT, int KW, bool PIN, int FIN = FIN_NONE, int WFMT = WF_BF16>
 __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __restrict__ X, int64_t ldx,
                                                                  const bf16x8* __restrict__ Wt, int M, int N, int K,
                                                                  int ks, bf16* __restrict__ Y, int64_t ldy,
@@ -253,14 +263,14 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   constexpr int XL = ROWS * CPR / NTH;    // X chunks staged per thread
   constexpr int KSTEP = KC / 16;          // MFMA k-steps per K chunk
   constexpr int KSW = KSTEP / KW;         // k-steps of one wave (KW waves split each chunk along K)
-  // 16-B weight vectors of one wave per chunk (W8: two k-steps each, W4: four)
-  constexpr int KSV = W4 ? KSW / 4 : (W8 ? KSW / 2 : KSW);
-  constexpr int VSH = W4 ? 6 : (W8 ? 5 : 4);  // log2 of the K columns one vector covers
-  constexpr int NSC = W4 ? KSV : 1;           // W4: raw block-scale pairs prefetched per chunk (one per vector)
-  typedef typename std::conditional<W8 || W4, u32x4, bf16x8>::type wvec;
+  constexpr bool W8 = WFMT == WF_FP8, W4 = WFMT == WF_MXFP4;
+  constexpr int KSV = KSW / wf_ksteps(WFMT);  // 16-B weight vectors of one wave per chunk
+  constexpr int VSH = wf_vshift(WFMT);
+  constexpr int NSC = W4 ? KSV : 1;           // mxfp4: raw block-scale pairs prefetched per chunk (one per vector)
+  typedef wf_vec<WFMT> wvec;
   static_assert(CPR >= 16 && XL >= 1 && KSW >= 1, "chunk too small");
-  static_assert(!W8 || (KSW % 2 == 0 && FIN == FIN_NONE && NT), "fp8 tiles hold k-step pairs; plain epilogues only");
-  static_assert(!W4 || (KSW % 4 == 0 && FIN == FIN_NONE && NT && !W8), "mxfp4 tiles hold four k-steps; plain epilogues only");
+  static_assert(WFMT == WF_BF16 || (KSW % wf_ksteps(WFMT) == 0 && FIN == FIN_NONE && NT),
+                "quantised tiles hold whole vectors of k-steps; plain epilogues and non-temporal loads only");
   static_assert(2 * ROWS * KC * 2 >= 4 * (KW - 1) * MT * 16 * 64 * 4, "LDS too small for the K-half reduction");
   __shared__ __attribute__((aligned(16))) bf16 xs[2][ROWS * KC];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -295,12 +305,12 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   // chunk)
   const int64_t v0 = (int64_t)nbl * (K >> VSH) + (k0 >> VSH) + kh * KSV;  // this wave's first vector
   const wvec* wp = reinterpret_cast<const wvec*>(Wt) + v0 * 64 + lane;
-  float wsc = 1.f;  // W8: 2^e of this lane's weight row
-  if constexpr (W8) wsc = fa.ss_in[32 * nbl + r];
-  // W4: the lane's row in the block-scale image, 32 rows x 2 B per vector (same tile and vector index as wp: in range
+  float wsc = 1.f;  // fp8: 2^e of this lane's weight row
+  if constexpr (W8) wsc = static_cast<const float*>(fa.wscale)[32 * nbl + r];
+  // mxfp4: the lane's row in the block-scale image, 32 rows x 2 B per vector (same tile and vector index as wp: in range
   // wherever the weight load is)
   const uint16_t* sp = nullptr;
-  if constexpr (W4) sp = reinterpret_cast<const uint16_t*>(fa.ss_in) + v0 * 32 + r;
+  if constexpr (W4) sp = static_cast<const uint16_t*>(fa.wscale) + v0 * 32 + r;
 
   // phase stamps (FinArgs::stamps, benchmarks only): 0 start, 1 main loop done, 2 slab stores drained, 3 ticket
   // taken (finisher), 4 finisher done
@@ -391,7 +401,7 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
   };
 
   wvec wa[KSV], wb[KSV];
-  uint16_t sa[NSC], sb[NSC];  // (W4 only: dead otherwise)
+  uint16_t sa[NSC], sb[NSC];  // (mxfp4 only: dead otherwise)
   // X first: its LDS image is written while the first weight chunk is still in flight (loads return in order)
   load_x(0);
   load_w(wa, sa, 0);
@@ -712,15 +722,27 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
 // the 128-row expert tiles streamed 8 % slower, Mixtral 128 threads 5,155 vs 5,234 tok/s, profiles/r06/mixtral/;
 // MT = 2 spills 32+ registers under the same bound and keeps its 324)
 //
-// W8 (fp8 expert weights, ops.tile_experts_fp8): Wt is the e4m3 image Wt8[E_local][N/32][K/32][64][16 B] of the dense
-// W8 kernel per expert and St[E_local][N] the power-of-two row scales in tile order, both indexed by the LOCAL expert
-// (expert_off by e_lo + el). A wave loads KSTEP / 2 vectors per chunk, keeps raw fp8 in wa / wb and dequantises each
-// vector right before its two k-steps' MFMAs (dq8, the row scale being the conversion's scale operand), so the
-// accumulators hold true values and the X stage, the MT = 4 rule and both epilogues are the bf16 kernel's. St is a
-// trailing argument whose type depends on W8 — an empty struct for bf16, which never reads it: the 24 bf16
-// instantiations compile to the register counts they had without W8 (profiles/wfp8_moe/resource_usage.txt).
+// WFMT = WF_FP8 (fp8 expert weights, ops.tile_experts_fp8): Wt is the e4m3 image Wt8[E_local][N/32][K/32][64][16 B] of
+// the dense kernel's WF_FP8 per expert and St[E_local][N] the power-of-two row scales in tile order, both indexed by
+// the LOCAL expert (expert_off by e_lo + el). A wave loads KSTEP / 2 vectors per chunk, keeps raw fp8 in wa / wb and
+// dequantises each vector right before its two k-steps' MFMAs (dq8, the row scale being the conversion's scale
+// operand), so the accumulators hold true values and the X stage, the MT = 4 rule and both epilogues are the bf16
+// kernel's. St is a trailing argument whose type depends on WFMT — an empty struct for bf16, which never reads it: the
+// 24 bf16 instantiations compile to the register counts they had before fp8 (profiles/wfp8_moe/resource_usage.txt,
+// profiles/wfmt/resource_usage.txt). MXFP4 expert tiles are not built.
+// (The type is picked by a specialisation, not by std::conditional<WFMT == WF_FP8, ...>: that expression would be part
+// of the kernel's mangled name, with the unnamed enum's compiler-made name in it, which the host and the device pass
+// number differently — the host stub then registers a symbol the code object does not have.)
 struct NoScales {};
-template <int MT, int KC, bool GATHER, bool COMBINE, bool PIN, bool W8 = false>
+template <int WFMT>
+struct WfScales {
+  typedef NoScales type;
+};
+template <>
+struct WfScales<WF_FP8> {
+  typedef const float* type;
+};
+template <int MT, int KC, bool GATHER, bool COMBINE, bool PIN, int WFMT = WF_BF16>
 __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(const bf16* __restrict__ X, int64_t ldx,
                                                                const bf16x8* __restrict__ Wt, int N, int K,
                                                                const int* __restrict__ perm_tok,
@@ -728,16 +750,17 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
                                                                const int* __restrict__ expert_off, int e_lo,
                                                                bf16* __restrict__ Y, int64_t ldy,
                                                                float* __restrict__ out, int64_t ldo,
-                                                               typename std::conditional<W8, const float*,
-                                                                                         NoScales>::type St) {
+                                                               typename WfScales<WFMT>::type St) {
   constexpr int ROWS = 32 * MT;
   constexpr int CPR = KC / 8;
   constexpr int XL = ROWS * CPR / 256;
   constexpr int KSTEP = KC / 16;
-  constexpr int KSV = W8 ? KSTEP / 2 : KSTEP;  // 16-B weight vectors per chunk (W8: two k-steps each)
-  typedef typename std::conditional<W8, u32x4, bf16x8>::type wvec;
+  constexpr bool W8 = WFMT == WF_FP8;
+  constexpr int KSV = KSTEP / wf_ksteps(WFMT);  // 16-B weight vectors per chunk
+  typedef wf_vec<WFMT> wvec;
   static_assert(CPR >= 16 && XL >= 1, "chunk too small");
-  static_assert(!W8 || KSTEP % 2 == 0, "fp8 tiles hold k-step pairs");
+  static_assert(WFMT != WF_MXFP4, "the expert kernel takes bf16 and fp8 tiles");
+  static_assert(KSTEP % wf_ksteps(WFMT) == 0, "quantised tiles hold whole vectors of k-steps");
   __shared__ __attribute__((aligned(16))) bf16 xs[2][ROWS * KC];
   const int el = blockIdx.y, e = e_lo + el;
   const int seg0 = expert_off[e];
@@ -753,8 +776,8 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
   // vectors of 64 lanes x 16 B per tile row)
   const int nbl = active ? nb : (N >> 5) - 1;
   const wvec* wp =
-      reinterpret_cast<const wvec*>(Wt) + ((int64_t)el * (N >> 5) + nbl) * (W8 ? K >> 5 : K >> 4) * 64 + lane;
-  float wsc = 1.f;  // W8: 2^e of this lane's weight row
+      reinterpret_cast<const wvec*>(Wt) + ((int64_t)el * (N >> 5) + nbl) * (K >> wf_vshift(WFMT)) * 64 + lane;
+  float wsc = 1.f;  // fp8: 2^e of this lane's weight row
   if constexpr (W8) wsc = St[(int64_t)el * N + 32 * nbl + r];
   const int nchunks = K / KC;
 
@@ -933,19 +956,91 @@ extern "C" int kafka_wstream_plan(int M, int N, int K, int max_splits, int* mt, 
   return 0;
 }
 
-extern "C" hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K,
-                                               int mt, int kc, int splits, int nt, int kw, int pin, int glu, bf16* Y,
-                                               int64_t ldy, float* P, hipStream_t st) {
+// One launch of wstream_gemm_kernel: the kernel's arguments, the grid and the stream.
+struct WsLaunch {
+  const bf16* X;
+  int64_t ldx;
+  const bf16x8* wt;
+  int M, N, K, ks;
+  bf16* Y;
+  int64_t ldy;
+  float* p;
+  int glu, rt, wide;
+  FinArgs fa;
+  dim3 grid;
+  hipStream_t st;
+};
+
+// The instantiations of one (MT, KC, KW, PIN) configuration: the plain epilogue on every tile format (bf16 with
+// non-temporal or plain loads, the quantised formats non-temporal only) and, up to 128 rows, the three fused
+// epilogues on bf16 tiles.
+template <int MT, int KC, int KW, bool PIN>
+static hipError_t launch_ws_cfg(const WsLaunch& a, int fin, int wfmt, int nt) {
+  void (*k)(const bf16*, int64_t, const bf16x8*, int, int, int, int, bf16*, int64_t, float*, int, int, int, FinArgs) =
+      nullptr;
+  if (fin == FIN_NONE) {
+    if (wfmt == WF_FP8) k = wstream_gemm_kernel<MT, KC, true, KW, PIN, FIN_NONE, WF_FP8>;
+    else if (wfmt == WF_MXFP4) k = wstream_gemm_kernel<MT, KC, true, KW, PIN, FIN_NONE, WF_MXFP4>;
+    else if (nt) k = wstream_gemm_kernel<MT, KC, true, KW, PIN>;
+    else k = wstream_gemm_kernel<MT, KC, false, KW, PIN>;
+  } else if constexpr (MT != 6) {  // (the 192-row tile has no finishers)
+    if (fin == FIN_RES) k = wstream_gemm_kernel<MT, KC, true, KW, PIN, FIN_RES>;
+    else if (fin == FIN_ROPE) k = wstream_gemm_kernel<MT, KC, true, KW, PIN, FIN_ROPE>;
+    else k = wstream_gemm_kernel<MT, KC, true, KW, PIN, FIN_GLU>;
+  }
+  if (k == nullptr) return hipErrorInvalidValue;
+  k<<<a.grid, 256 * KW, 0, a.st>>>(a.X, a.ldx, a.wt, a.M, a.N, a.K, a.ks, a.Y, a.ldy, a.p, a.glu, a.rt, a.wide, a.fa);
+  return hipGetLastError();
+}
+
+// The (MT, KC, KW) configurations of wstream_gemm_kernel, for both launchers below.
+static hipError_t launch_ws(const WsLaunch& a, int mt, int kc, int kw, int pin, int fin, int wfmt, int nt) {
+#define KAFKA_WS_CFG(MT_, KC_, KW_)                                          \
+  if (mt == MT_ && kc == KC_ && kw == KW_)                                   \
+    return pin ? launch_ws_cfg<MT_, KC_, KW_, true>(a, fin, wfmt, nt)        \
+               : launch_ws_cfg<MT_, KC_, KW_, false>(a, fin, wfmt, nt);
+  KAFKA_WS_CFG(1, 256, 1)
+  KAFKA_WS_CFG(1, 256, 2)
+  KAFKA_WS_CFG(2, 256, 1)
+  KAFKA_WS_CFG(2, 256, 2)
+  KAFKA_WS_CFG(3, 256, 1)
+  KAFKA_WS_CFG(4, 128, 1)
+  KAFKA_WS_CFG(4, 128, 2)
+  KAFKA_WS_CFG(6, 128, 1)
+#undef KAFKA_WS_CFG
+  return hipErrorInvalidValue;
+}
+
+// wfmt (WF_*) names the layout of Wt and of its scales: bf16 tiles [N/32][K/16][64][8] without scales; fp8 tiles
+// [N/32][K/32][64][16] e4m3 bytes with St [N] fp32 row scales in tile order; MXFP4 tiles [N/32][K/64][64][16] e2m1
+// bytes with Se [N/32][K/64][32][2] e8m0 block exponents. Every format runs the same plans, grid, outputs and
+// (mt, kc, kw, pin) configurations; the quantised ones stream with non-temporal loads only.
+extern "C" hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale,
+                                               int M, int N, int K, int mt, int kc, int splits, int nt, int kw, int pin,
+                                               int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st) {
   if (M < 1) return hipSuccess;
   if (glu && (N % 64 != 0 || kw > 2)) return hipErrorInvalidValue;  // (the SwiGLU epilogue runs after the KW fold)
+  switch (wfmt) {
+    case WF_BF16:
+      if (scale != nullptr) return hipErrorInvalidValue;
+      break;
+    case WF_FP8:
+    case WF_MXFP4:  // whole weight vectors along K (32 / 64 columns), with their scales
+      if (K % (1 << wf_vshift(wfmt)) != 0 || N % 32 != 0 || Wt == nullptr || scale == nullptr || !nt)
+        return hipErrorInvalidValue;
+      break;
+    default: return hipErrorInvalidValue;
+  }
   if (K % (kc * splits) != 0 || (splits > 1 && P == nullptr) || (splits == 1 && P == nullptr && Y == nullptr))
     return hipErrorInvalidValue;
-  const int rt = (M + 32 * mt - 1) / (32 * mt);  // row tiles of 32 * mt rows
+  WsLaunch a{};
+  a.X = X, a.ldx = ldx, a.wt = static_cast<const bf16x8*>(Wt), a.M = M, a.N = N, a.K = K, a.Y = Y, a.ldy = ldy;
+  a.glu = glu, a.st = st;
+  a.rt = (M + 32 * mt - 1) / (32 * mt);  // row tiles of 32 * mt rows
   const int nblk = (N + 127) / 128;
-  const dim3 grid((rt > 1 ? (nblk + 7) / 8 * 8 : nblk) * rt, splits);  // (row tiles: column blocks padded to 8)
-  const int ks = K / splits;
-  const auto* wt = reinterpret_cast<const bf16x8*>(Wt);
-  float* p = splits > 1 ? P : nullptr;
+  a.grid = dim3((a.rt > 1 ? (nblk + 7) / 8 * 8 : nblk) * a.rt, splits);  // (row tiles: column blocks padded to 8)
+  a.ks = K / splits;
+  a.p = splits > 1 ? P : nullptr;
   // split-K slabs leave as 16-B sc1 stores through an LDS transpose (was one 4-B store per accumulator, the lines
   // kept dirty in the XCD's L2): +2.0 % on the headline, in-step GPU time 7.50 vs 7.65 ms
   // (profiles/r05/bench_ab_wstream_slab16_sc1.jsonl).
@@ -953,123 +1048,9 @@ extern "C" hipError_t kafka_launch_wstream_gemm(const bf16* X, int64_t ldx, cons
   // per store instruction (was one 2-B store per accumulator, half lines): +1.1..2.1 %, in-step GPU time 7.37 vs
   // 7.45-7.49 ms (profiles/r05/bench_ab_wstream_wide_y.jsonl) — 16-B stores of Y need 16-B aligned rows
   const bool y_unaligned = Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0);
-  const int wide = y_unaligned ? WIDE_P : (WIDE_P | WIDE_Y);
-#define KAFKA_WS(MT_, KC_, KW_, PIN_)                                                                            \
-  do {                                                                                                          \
-    if (nt)                                                                                                     \
-      wstream_gemm_kernel<MT_, KC_, true, KW_, PIN_><<<grid, 256 * KW_, 0, st>>>(X, ldx, wt, M, N, K, ks, Y, ldy, p, \
-                                                                              glu, rt, wide, FinArgs{});        \
-    else                                                                                                        \
-      wstream_gemm_kernel<MT_, KC_, false, KW_, PIN_><<<grid, 256 * KW_, 0, st>>>(X, ldx, wt, M, N, K, ks, Y, ldy, p, \
-                                                                               glu, rt, wide, FinArgs{});       \
-  } while (0)
-#define KAFKA_WS_IF(MT_, KC_, KW_)                                      \
-  if (mt == MT_ && kc == KC_ && kw == KW_) {                           \
-    if (pin)                                                           \
-      KAFKA_WS(MT_, KC_, KW_, true);                                   \
-    else                                                               \
-      KAFKA_WS(MT_, KC_, KW_, false);                                  \
-  }
-  KAFKA_WS_IF(1, 256, 1)
-  else KAFKA_WS_IF(1, 256, 2)
-  else KAFKA_WS_IF(2, 256, 1)
-  else KAFKA_WS_IF(2, 256, 2)
-  else KAFKA_WS_IF(3, 256, 1)
-  else KAFKA_WS_IF(4, 128, 1)
-  else KAFKA_WS_IF(4, 128, 2)
-  else KAFKA_WS_IF(6, 128, 1)
-  else return hipErrorInvalidValue;
-#undef KAFKA_WS_IF
-#undef KAFKA_WS
-  return hipGetLastError();
-}
-
-// fp8 weights (W8 above): Wt8 [N/32][K/32][64][16] e4m3 bytes, St [N] fp32 row scales in tile order. Same plans,
-// grid, outputs and (mt, kc, kw, pin) configurations as kafka_launch_wstream_gemm; always non-temporal loads.
-extern "C" hipError_t kafka_launch_wstream_gemm_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St,
-                                                  int M, int N, int K, int mt, int kc, int splits, int kw, int pin,
-                                                  int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st) {
-  if (M < 1) return hipSuccess;
-  if (glu && (N % 64 != 0 || kw > 2)) return hipErrorInvalidValue;
-  if (K % 32 != 0 || N % 32 != 0 || Wt8 == nullptr || St == nullptr) return hipErrorInvalidValue;
-  if (K % (kc * splits) != 0 || (splits > 1 && P == nullptr) || (splits == 1 && P == nullptr && Y == nullptr))
-    return hipErrorInvalidValue;
-  const int rt = (M + 32 * mt - 1) / (32 * mt);
-  const int nblk = (N + 127) / 128;
-  const dim3 grid((rt > 1 ? (nblk + 7) / 8 * 8 : nblk) * rt, splits);
-  const int ks = K / splits;
-  const auto* wt = reinterpret_cast<const bf16x8*>(Wt8);
-  float* p = splits > 1 ? P : nullptr;
-  const bool y_unaligned = Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0);
-  const int wide = y_unaligned ? WIDE_P : (WIDE_P | WIDE_Y);
-  FinArgs fa{};
-  fa.ss_in = St;  // (the W8 kernel's row scales: see the kernel's header comment)
-#define KAFKA_W8(MT_, KC_, KW_, PIN_)                                                                              \
-  wstream_gemm_kernel<MT_, KC_, true, KW_, PIN_, FIN_NONE, true><<<grid, 256 * KW_, 0, st>>>(                      \
-      X, ldx, wt, M, N, K, ks, Y, ldy, p, glu, rt, wide, fa)
-#define KAFKA_W8_IF(MT_, KC_, KW_)                                      \
-  if (mt == MT_ && kc == KC_ && kw == KW_) {                           \
-    if (pin)                                                           \
-      KAFKA_W8(MT_, KC_, KW_, true);                                   \
-    else                                                               \
-      KAFKA_W8(MT_, KC_, KW_, false);                                  \
-  }
-  KAFKA_W8_IF(1, 256, 1)
-  else KAFKA_W8_IF(1, 256, 2)
-  else KAFKA_W8_IF(2, 256, 1)
-  else KAFKA_W8_IF(2, 256, 2)
-  else KAFKA_W8_IF(3, 256, 1)
-  else KAFKA_W8_IF(4, 128, 1)
-  else KAFKA_W8_IF(4, 128, 2)
-  else KAFKA_W8_IF(6, 128, 1)
-  else return hipErrorInvalidValue;
-#undef KAFKA_W8_IF
-#undef KAFKA_W8
-  return hipGetLastError();
-}
-
-// MXFP4 weights (W4 above): Wt4 [N/32][K/64][64][16] e2m1 bytes, Se [N/32][K/64][32][2] e8m0 block exponents. Same
-// plans, grid, outputs and (mt, kc, kw, pin) configurations as kafka_launch_wstream_gemm; always non-temporal loads.
-extern "C" hipError_t kafka_launch_wstream_gemm_w4(const bf16* X, int64_t ldx, const uint8_t* Wt4, const uint8_t* Se,
-                                                  int M, int N, int K, int mt, int kc, int splits, int kw, int pin,
-                                                  int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st) {
-  if (M < 1) return hipSuccess;
-  if (glu && (N % 64 != 0 || kw > 2)) return hipErrorInvalidValue;
-  if (K % 64 != 0 || N % 32 != 0 || Wt4 == nullptr || Se == nullptr) return hipErrorInvalidValue;
-  if (K % (kc * splits) != 0 || (splits > 1 && P == nullptr) || (splits == 1 && P == nullptr && Y == nullptr))
-    return hipErrorInvalidValue;
-  const int rt = (M + 32 * mt - 1) / (32 * mt);
-  const int nblk = (N + 127) / 128;
-  const dim3 grid((rt > 1 ? (nblk + 7) / 8 * 8 : nblk) * rt, splits);
-  const int ks = K / splits;
-  const auto* wt = reinterpret_cast<const bf16x8*>(Wt4);
-  float* p = splits > 1 ? P : nullptr;
-  const bool y_unaligned = Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0);
-  const int wide = y_unaligned ? WIDE_P : (WIDE_P | WIDE_Y);
-  FinArgs fa{};
-  fa.ss_in = reinterpret_cast<const float*>(Se);  // (the W4 kernel's block-scale image: see the kernel's header comment)
-#define KAFKA_W4(MT_, KC_, KW_, PIN_)                                                                              \
-  wstream_gemm_kernel<MT_, KC_, true, KW_, PIN_, FIN_NONE, false, true><<<grid, 256 * KW_, 0, st>>>(               \
-      X, ldx, wt, M, N, K, ks, Y, ldy, p, glu, rt, wide, fa)
-#define KAFKA_W4_IF(MT_, KC_, KW_)                                      \
-  if (mt == MT_ && kc == KC_ && kw == KW_) {                           \
-    if (pin)                                                           \
-      KAFKA_W4(MT_, KC_, KW_, true);                                   \
-    else                                                               \
-      KAFKA_W4(MT_, KC_, KW_, false);                                  \
-  }
-  KAFKA_W4_IF(1, 256, 1)
-  else KAFKA_W4_IF(1, 256, 2)
-  else KAFKA_W4_IF(2, 256, 1)
-  else KAFKA_W4_IF(2, 256, 2)
-  else KAFKA_W4_IF(3, 256, 1)
-  else KAFKA_W4_IF(4, 128, 1)
-  else KAFKA_W4_IF(4, 128, 2)
-  else KAFKA_W4_IF(6, 128, 1)
-  else return hipErrorInvalidValue;
-#undef KAFKA_W4_IF
-#undef KAFKA_W4
-  return hipGetLastError();
+  a.wide = y_unaligned ? WIDE_P : (WIDE_P | WIDE_Y);
+  a.fa.wscale = scale;  // (see the kernel's header comment)
+  return launch_ws(a, mt, kc, kw, pin, FIN_NONE, wfmt, nt);
 }
 
 // Fused decode-layer GEMMs (FIN_RES / FIN_ROPE / FIN_GLU above): one row tile (M <= 128), N % 128 == 0, S in
@@ -1097,41 +1078,16 @@ extern "C" hipError_t kafka_launch_wstream_fin(int fin, const bf16* X, int64_t l
   }
   if (fin != FIN_GLU && ((splits > 1 && (P == nullptr || fa.tickets == nullptr))))
     return hipErrorInvalidValue;
-  const dim3 grid(N / 128, splits);
-  const int ks = K / splits;
-  const auto* wt = reinterpret_cast<const bf16x8*>(Wt);
-  float* p = splits > 1 ? P : nullptr;
+  WsLaunch a{};
+  a.X = X, a.ldx = ldx, a.wt = reinterpret_cast<const bf16x8*>(Wt), a.M = M, a.N = N, a.K = K, a.Y = Y, a.ldy = ldy;
+  a.fa = fa, a.st = st, a.rt = 1;
+  a.grid = dim3(N / 128, splits);
+  a.ks = K / splits;
+  a.p = splits > 1 ? P : nullptr;
   // (only FIN_GLU's Y consults it: wide stores when its rows are 16-B aligned)
-  const int wide = (Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0)) ? 0 : WIDE_Y;
-  const int glu = fin == FIN_GLU ? 1 : 0;
-#define KAFKA_WF(MT_, KC_, KW_, PIN_, FIN_)                                                                      \
-  wstream_gemm_kernel<MT_, KC_, true, KW_, PIN_, FIN_><<<grid, 256 * KW_, 0, st>>>(X, ldx, wt, M, N, K, ks, Y, ldy, p, \
-                                                                                  glu, 1, wide, fa)
-#define KAFKA_WF_FIN(MT_, KC_, KW_, PIN_)                                    \
-  do {                                                                       \
-    if (fin == FIN_RES) KAFKA_WF(MT_, KC_, KW_, PIN_, FIN_RES);              \
-    else if (fin == FIN_ROPE) KAFKA_WF(MT_, KC_, KW_, PIN_, FIN_ROPE);       \
-    else KAFKA_WF(MT_, KC_, KW_, PIN_, FIN_GLU);                             \
-  } while (0)
-#define KAFKA_WF_IF(MT_, KC_, KW_)                                \
-  if (mt == MT_ && kc == KC_ && kw == KW_) {                      \
-    if (pin)                                                      \
-      KAFKA_WF_FIN(MT_, KC_, KW_, true);                          \
-    else                                                          \
-      KAFKA_WF_FIN(MT_, KC_, KW_, false);                         \
-  }
-  KAFKA_WF_IF(1, 256, 1)
-  else KAFKA_WF_IF(1, 256, 2)
-  else KAFKA_WF_IF(2, 256, 1)
-  else KAFKA_WF_IF(2, 256, 2)
-  else KAFKA_WF_IF(3, 256, 1)
-  else KAFKA_WF_IF(4, 128, 1)
-  else KAFKA_WF_IF(4, 128, 2)
-  else return hipErrorInvalidValue;
-#undef KAFKA_WF_IF
-#undef KAFKA_WF_FIN
-#undef KAFKA_WF
-  return hipGetLastError();
+  a.wide = (Y != nullptr && (ldy % 8 != 0 || reinterpret_cast<uintptr_t>(Y) % 16 != 0)) ? 0 : WIDE_Y;
+  a.glu = fin == FIN_GLU ? 1 : 0;
+  return launch_ws(a, mt, kc, kw, pin, fin, WF_BF16, 1);
 }
 
 extern "C" hipError_t kafka_launch_slab_reduce(const float* P, int S, int M, int N, bf16* Y, int64_t ldy,
@@ -1146,87 +1102,81 @@ extern "C" hipError_t kafka_launch_slab_reduce(const float* P, int S, int M, int
 }  // namespace kafka
 
 namespace kafka {
+// One launch of wstream_grouped_kernel: the kernel's arguments (scale: St for fp8 tiles), the grid and the stream.
+struct WgLaunch {
+  const bf16* X;
+  int64_t ldx;
+  const bf16x8* wt;
+  int N, K;
+  const int* perm_tok;
+  const float* perm_w;
+  const int* expert_off;
+  int e_lo;
+  bf16* Y;
+  int64_t ldy;
+  float* out;
+  int64_t ldo;
+  const void* scale;
+  dim3 grid;
+  hipStream_t st;
+};
+
+template <int MT, bool G, bool C>
+static void launch_wg_cfg(const WgLaunch& a, int wfmt, int pin) {
+  constexpr int KC = MT == 4 ? 128 : 256;
+  auto go = [&](auto kern, auto sc) {
+    kern<<<a.grid, 256, 0, a.st>>>(a.X, a.ldx, a.wt, a.N, a.K, a.perm_tok, a.perm_w, a.expert_off, a.e_lo, a.Y, a.ldy,
+                                   a.out, a.ldo, sc);
+  };
+  if (wfmt == WF_FP8) {
+    const auto* st = static_cast<const float*>(a.scale);
+    pin ? go(wstream_grouped_kernel<MT, KC, G, C, true, WF_FP8>, st)
+        : go(wstream_grouped_kernel<MT, KC, G, C, false, WF_FP8>, st);
+  } else {
+    pin ? go(wstream_grouped_kernel<MT, KC, G, C, true>, NoScales{})
+        : go(wstream_grouped_kernel<MT, KC, G, C, false>, NoScales{});
+  }
+}
+
 // Grouped streaming GEMM for the expert MLP (see wstream_grouped_kernel). max_rows bounds any expert's segment
 // (the token count T: a token picks an expert at most once); glu: gate_up with fused SwiGLU into Y [n_ent, N/2];
 // else combine into out_f32 [T, N].
-static int grouped_mt(int max_rows) { return max_rows <= 32 ? 1 : (max_rows <= 192 ? 2 : 4); }
-
-extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, const bf16* Wt, int e_local, int N,
-                                                  int K, const int* perm_tok, const float* perm_w,
-                                                  const int* expert_off, int e_lo, int max_rows, int gather,
-                                                  bf16* Y, int64_t ldy, float* out, int64_t ldo, int pin,
+// wfmt: bf16 expert tiles Wt [E_local][N/32][K/16][64][8] without scales, or fp8 ones [E_local][N/32][K/32][64][16]
+// e4m3 bytes with St [E_local][N] fp32 row scales in tile order (ops.tile_experts_fp8); same grid, MT choice and
+// outputs.
+extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, int wfmt, const void* Wt,
+                                                  const void* scale, int e_local, int N, int K, const int* perm_tok,
+                                                  const float* perm_w, const int* expert_off, int e_lo, int max_rows,
+                                                  int gather, bf16* Y, int64_t ldy, float* out, int64_t ldo, int pin,
                                                   hipStream_t st) {
   if (max_rows < 1 || e_local < 1) return hipSuccess;
   if (N % 64 != 0 || K % 256 != 0 || (out == nullptr) == (Y == nullptr)) return hipErrorInvalidValue;
+  switch (wfmt) {
+    case WF_BF16:
+      if (scale != nullptr) return hipErrorInvalidValue;
+      break;
+    case WF_FP8:
+      if (Wt == nullptr || scale == nullptr) return hipErrorInvalidValue;
+      break;
+    default: return hipErrorInvalidValue;  // (no MXFP4 expert tiles)
+  }
   // MT = 4 (128-row tiles on 128-deep K chunks) for large steps: with 64-row tiles every
   // row tile of an expert re-streams its weights, and those tiles run far apart in dispatch order (blockIdx.z is the
   // slowest dimension), so no cache keeps the slice between them — an expert with 65..128 rows read its 352 MB twice.
   // (64-row tiles stay below 193 rows: an expert then rarely fills a second tile, and they stream faster there —
   // benchmarks/moe_bench.py T = 128 / 192: 493 / 522 vs 517 / 551 us per layer; T = 256 / 384 / 512: 761 / 1002 /
   // 1303 vs 601 / 691 / 1004, profiles/r06/mixtral/)
-  const int MT = grouped_mt(max_rows);
-  const dim3 grid((N + 127) / 128, e_local, (max_rows + 32 * MT - 1) / (32 * MT));
-  const auto* wt = reinterpret_cast<const bf16x8*>(Wt);
-#define KAFKA_WG(MT_, G_, C_)                                                                                   \
-  do {                                                                                                         \
-    constexpr int KC_ = MT_ == 4 ? 128 : 256;                                                                  \
-    if (pin)                                                                                                   \
-      wstream_grouped_kernel<MT_, KC_, G_, C_, true><<<grid, 256, 0, st>>>(X, ldx, wt, N, K, perm_tok, perm_w,      \
-                                                                           expert_off, e_lo, Y, ldy, out, ldo, NoScales{});  \
-    else                                                                                                       \
-      wstream_grouped_kernel<MT_, KC_, G_, C_, false><<<grid, 256, 0, st>>>(X, ldx, wt, N, K, perm_tok, perm_w,     \
-                                                                            expert_off, e_lo, Y, ldy, out, ldo, NoScales{}); \
-  } while (0)
+  const int MT = max_rows <= 32 ? 1 : (max_rows <= 192 ? 2 : 4);
+  const WgLaunch a{X, ldx, static_cast<const bf16x8*>(Wt), N, K, perm_tok, perm_w, expert_off, e_lo, Y, ldy, out, ldo,
+                   scale, dim3((N + 127) / 128, e_local, (max_rows + 32 * MT - 1) / (32 * MT)), st};
   const bool comb = out != nullptr;
-  if (MT == 1) {
-    if (gather) { if (comb) KAFKA_WG(1, true, true); else KAFKA_WG(1, true, false); }
-    else { if (comb) KAFKA_WG(1, false, true); else KAFKA_WG(1, false, false); }
-  } else if (MT == 2) {
-    if (gather) { if (comb) KAFKA_WG(2, true, true); else KAFKA_WG(2, true, false); }
-    else { if (comb) KAFKA_WG(2, false, true); else KAFKA_WG(2, false, false); }
-  } else {
-    if (gather) { if (comb) KAFKA_WG(4, true, true); else KAFKA_WG(4, true, false); }
-    else { if (comb) KAFKA_WG(4, false, true); else KAFKA_WG(4, false, false); }
-  }
+#define KAFKA_WG(MT_)                                                                                        \
+  (gather ? (comb ? launch_wg_cfg<MT_, true, true>(a, wfmt, pin) : launch_wg_cfg<MT_, true, false>(a, wfmt, pin))   \
+          : (comb ? launch_wg_cfg<MT_, false, true>(a, wfmt, pin) : launch_wg_cfg<MT_, false, false>(a, wfmt, pin)))
+  if (MT == 1) KAFKA_WG(1);
+  else if (MT == 2) KAFKA_WG(2);
+  else KAFKA_WG(4);
 #undef KAFKA_WG
-  return hipGetLastError();
-}
-
-// fp8 expert weights: Wt8 [E_local][N/32][K/32][64][16] e4m3 bytes, St [E_local][N] fp32 row scales in tile order
-// (ops.tile_experts_fp8). Same grid, MT choice and outputs as kafka_launch_wstream_grouped.
-extern "C" hipError_t kafka_launch_wstream_grouped_w8(const bf16* X, int64_t ldx, const uint8_t* Wt8, const float* St,
-                                                     int e_local, int N, int K, const int* perm_tok,
-                                                     const float* perm_w, const int* expert_off, int e_lo,
-                                                     int max_rows, int gather, bf16* Y, int64_t ldy, float* out,
-                                                     int64_t ldo, int pin, hipStream_t st) {
-  if (max_rows < 1 || e_local < 1) return hipSuccess;
-  if (N % 64 != 0 || K % 256 != 0 || (out == nullptr) == (Y == nullptr) || Wt8 == nullptr || St == nullptr)
-    return hipErrorInvalidValue;
-  const int MT = grouped_mt(max_rows);
-  const dim3 grid((N + 127) / 128, e_local, (max_rows + 32 * MT - 1) / (32 * MT));
-  const auto* wt = reinterpret_cast<const bf16x8*>(Wt8);
-#define KAFKA_WG8(MT_, G_, C_)                                                                                  \
-  do {                                                                                                         \
-    constexpr int KC_ = MT_ == 4 ? 128 : 256;                                                                  \
-    if (pin)                                                                                                   \
-      wstream_grouped_kernel<MT_, KC_, G_, C_, true, true><<<grid, 256, 0, st>>>(                                 \
-          X, ldx, wt, N, K, perm_tok, perm_w, expert_off, e_lo, Y, ldy, out, ldo, St);                         \
-    else                                                                                                       \
-      wstream_grouped_kernel<MT_, KC_, G_, C_, false, true><<<grid, 256, 0, st>>>(                                \
-          X, ldx, wt, N, K, perm_tok, perm_w, expert_off, e_lo, Y, ldy, out, ldo, St);                         \
-  } while (0)
-  const bool comb = out != nullptr;
-  if (MT == 1) {
-    if (gather) { if (comb) KAFKA_WG8(1, true, true); else KAFKA_WG8(1, true, false); }
-    else { if (comb) KAFKA_WG8(1, false, true); else KAFKA_WG8(1, false, false); }
-  } else if (MT == 2) {
-    if (gather) { if (comb) KAFKA_WG8(2, true, true); else KAFKA_WG8(2, true, false); }
-    else { if (comb) KAFKA_WG8(2, false, true); else KAFKA_WG8(2, false, false); }
-  } else {
-    if (gather) { if (comb) KAFKA_WG8(4, true, true); else KAFKA_WG8(4, true, false); }
-    else { if (comb) KAFKA_WG8(4, false, true); else KAFKA_WG8(4, false, false); }
-  }
-#undef KAFKA_WG8
   return hipGetLastError();
 }
 }  // namespace kafka
