@@ -23,26 +23,13 @@ every TP rank, from the same plan, so every rank samples the same token.
 from __future__ import annotations
 
 from collections import OrderedDict
-from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
+from kafka_llm_service_amd.engine.step_plan import ProcUpdates  # (the record travels in a step's wire format)
+
 MASK_ROWS = 512
-
-
-@dataclass
-class ProcUpdates:
-    """Device table writes a step needs before its sampler runs (identical on every TP rank)."""
-    mask_rows: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))     # [k] rows of mask_tab
-    mask_words: np.ndarray = field(default_factory=lambda: np.zeros((0, 0), np.int32))  # [k, W] their bits
-    zero_slots: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))    # [z] count rows to clear
-    # [d, 2] (slot, token): counts[slot][token] -= 1 — a token the sampler counted and the engine rolled back
-    dec: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.int32))
-
-    @property
-    def empty(self) -> bool:
-        return not (self.mask_rows.size or self.zero_slots.size or self.dec.size)
 
 
 def pack_bits(keep: np.ndarray, words: int) -> np.ndarray:

@@ -105,9 +105,6 @@ def _tickets(dev: torch.device, n: int, pool: str = "decode") -> torch.Tensor:
     return t
 
 
-DECODE_ITEM = 8  # int32 fields of a decode work item: (b, lo, hi, split, nsplit, npre, 0, 0)
-
-
 def attn_decode_items(q, k_cache, v_cache, block_tables, items, out_part, lse_part, scale: float, out=None,
                       pre_part=None, merge=None) -> None:
     """Paged decode attention over work items (int32 [n, 8]: row b, key range [lo, hi), piece ``split`` of

@@ -604,7 +604,8 @@ def test_retired_switches_stay_retired():
                "KAFKA_FUSED_PREFILL_MERGE", "KAFKA_RETILE_JOINS", "KAFKA_FIXED_DECODE_ITEMS"]
     root = Path(pkg.__file__).resolve().parent
     files = [p for d in ("ops", "models") for p in (root / d).rglob("*")
-             if p.suffix in (".py", ".hip", ".h", ".cpp")] + [root / "engine" / "model_runner.py"]
+             if p.suffix in (".py", ".hip", ".h", ".cpp")] + [root / "engine" / "model_runner.py",
+                                                                root / "engine" / "step_plan.py"]
     assert len(files) > 10
     found = [(p.name, n) for p in files for n in retired if n in p.read_text(errors="replace")]
     assert not found, found
