@@ -1,14 +1,71 @@
-import torch, time, statistics
+"""Sampler time at 64 rows x 128,256 bf16 logits, greedy and T = 0.7, one JSON line per case (device events around
+200 back-to-back launches, median of 5 windows).
+
+  --proc none      no logits processing (the headline path)
+  --proc penalty   every row a penalty-only processing row (presence 0.5, frequency 1.5, zero counts)
+  --logit-bias N   every row carries N bias entries (its own table row; implies a processing row); 0 = none
+
+The script also runs on a tree from before logit_bias (``ops.sample`` without ``bias_tab``): there --logit-bias must
+be 0, which is how the parent's numbers beside this tree's were taken."""
+import argparse
+import inspect
+import json
+import statistics
+
+import numpy as np
+import torch
+
 from kafka_llm_service_amd import ops
-dev=torch.device("cuda:0")
-B,V=64,128256
-lg=torch.randn(B,V,device=dev).to(torch.bfloat16)
-t=torch.full((B,),0.7,device=dev); tp=torch.ones(B,device=dev); tk=torch.zeros(B,dtype=torch.int32,device=dev)
-sd=torch.arange(B,dtype=torch.int64,device=dev)
-res=[]
-for r in range(5):
-    s,e=torch.cuda.Event(enable_timing=True),torch.cuda.Event(enable_timing=True)
-    ops.sample(lg,t,tp,tk,sd); torch.cuda.synchronize(); s.record()
-    for i in range(50): ops.sample(lg,t,tp,tk,sd)
-    e.record(); torch.cuda.synchronize(); res.append(s.elapsed_time(e)*1e3/50)
-print("sample 64x128256 bf16 T=0.7 us/call", round(statistics.median(res),1))
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--proc", choices=("none", "penalty"), default="none")
+ap.add_argument("--logit-bias", type=int, default=0)
+ap.add_argument("--rows", type=int, default=64)
+ap.add_argument("--vocab", type=int, default=128256)
+ap.add_argument("--tag", default="")
+a = ap.parse_args()
+
+dev = torch.device("cuda:0")
+B, V = a.rows, a.vocab
+lg = (torch.randn(B, V, generator=torch.Generator().manual_seed(0)) * 3).to(torch.bfloat16).to(dev)
+sd = torch.arange(B, dtype=torch.int64, device=dev)
+has_bias = "bias_tab" in inspect.signature(ops.sample).parameters
+kw = {}
+if a.proc != "none" or a.logit_bias:
+    proc = np.zeros((B, 8), dtype=np.int32)
+    proc[:, 2] = -1
+    kw["mask_tab"] = torch.zeros(1, -(-V // 32), dtype=torch.int32, device=dev)
+    if a.proc == "penalty":
+        proc[:, 2] = np.arange(B)
+        proc[:, 3:5] = np.array([0.5, 1.5], dtype=np.float32).view(np.int32)
+        kw["counts"] = torch.zeros(B, -(-V // 8) * 8, dtype=torch.int32, device=dev)
+    if has_bias:
+        n, M = a.logit_bias, ops.LOGIT_BIAS_MAX
+        tab = np.zeros((B, 2 * M), dtype=np.int32)
+        rng = np.random.default_rng(1)
+        for i in range(B if n else 0):
+            tab[i, :n] = np.sort(rng.choice(V, n, replace=False))
+            tab[i, M:M + n] = (rng.integers(-32, 33, n) / 8.0).astype(np.float32).view(np.int32)
+            proc[i, 5:7] = (i, n)
+        kw["bias_tab"] = torch.from_numpy(tab).to(dev)  # (always passed: without it ops.sample checks proc on the host)
+    elif a.logit_bias:
+        raise SystemExit("this tree's sampler has no logit_bias")
+    kw["proc"] = torch.from_numpy(proc).to(dev)
+
+for name, temp in (("greedy", 0.0), ("T0.7", 0.7)):
+    t = torch.full((B,), temp, device=dev)
+    res = []
+    for r in range(5):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(20):
+            ops.sample(lg, t, seeds=sd, **kw)
+        torch.cuda.synchronize()
+        s.record()
+        for _ in range(200):
+            ops.sample(lg, t, seeds=sd, **kw)
+        e.record()
+        torch.cuda.synchronize()
+        res.append(s.elapsed_time(e) * 1e3 / 200)
+    print(json.dumps({"bench": "sample", "tag": a.tag, "rows": B, "vocab": V, "mode": name, "proc": a.proc,
+                      "logit_bias": a.logit_bias, "us_per_call": round(statistics.median(res), 2),
+                      "min": round(min(res), 2), "max": round(max(res), 2)}), flush=True)

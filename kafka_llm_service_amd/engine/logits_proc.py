@@ -10,13 +10,19 @@ Per step the host builds one int32 row per sampled sequence (``proc``, 8 ints):
     [0] mode  0 none | 1 bitmask row [1] of ``mask_tab`` | 2 forced token [1] (the kernel writes it, no draw)
     [2] penalty slot: row of ``counts`` holding the sequence's generated-token counts (-1: no penalty)
     [3] presence, [4] frequency penalty (fp32 bits)
+    [5] row of ``bias_tab`` holding the request's ``logit_bias``, [6] its entry count (0: no bias)
+The kernel computes ``(x - freq * c - (c > 0 ? pres : 0)) + b`` in fp32 and applies the grammar mask after it: a
+masked-out token stays -inf whatever its bias. The bias is stateless (nothing to undo on a rollback or a re-prefill).
 The proc rows ride in the step's single H2D upload (and in the TP plan); the two tables live on the device at fixed
-addresses (hipGraph-capturable):
+addresses (hipGraph-capturable), and so does the bias table:
   * ``mask_tab`` uint32 [MASK_ROWS, ceil(V / 32)]: one row per distinct allowed set (a constraint state's cached
     vocab mask + its extra ids, or an explicit id list), LRU-managed by key; a new set costs one 16 KB row upload,
     after that the same state is a row index;
   * ``counts`` int32 [slots, V]: a slot per penalised live sequence, zeroed on (re)assignment; the sampler bumps
-    ``counts[slot][token]`` with every token it draws, so the next step (stream-ordered) sees it without the host.
+    ``counts[slot][token]`` with every token it draws, so the next step (stream-ordered) sees it without the host;
+  * ``bias_tab`` int32 [BIAS_ROWS, 2 * LOGIT_BIAS_MAX]: one row per distinct ``logit_bias`` object — the ids in
+    strictly ascending order, then the fp32 bits of their biases — keyed by content and LRU-managed like the mask
+    rows: a thread sends the same object every turn, so after one 2.4 KB row upload it is a row index.
 Table writes (new mask rows, slot zeroing, count decrements of rolled-back tokens) are ``ProcUpdates`` applied on the stream before the step's sampler — on
 every TP rank, from the same plan, so every rank samples the same token.
 """
@@ -27,9 +33,11 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from kafka_llm_service_amd.engine.step_plan import ProcUpdates  # (the record travels in a step's wire format)
+# (the update record travels in a step's wire format)
+from kafka_llm_service_amd.engine.step_plan import BIAS_ROW_INTS, LOGIT_BIAS_MAX, ProcUpdates
 
 MASK_ROWS = 512
+BIAS_ROWS = 512
 
 
 def pack_bits(keep: np.ndarray, words: int) -> np.ndarray:
@@ -47,50 +55,77 @@ def spec_forced(spec) -> int | None:
 
 
 class LogitsProcessor:
-    def __init__(self, device: torch.device, vocab: int, max_slots: int = 256, mask_rows: int = MASK_ROWS):
+    def __init__(self, device: torch.device, vocab: int, max_slots: int = 256, mask_rows: int = MASK_ROWS,
+                 bias_rows: int = BIAS_ROWS):
         self.device = torch.device(device)
         self.V = vocab
         self.W = -(-vocab // 32)
         self.cnt_ld = -(-vocab // 8) * 8
         self.n_mask_rows = mask_rows
+        self.n_bias_rows = bias_rows
         self.max_slots = max_slots
         self.mask_tab: torch.Tensor | None = None
         self.counts: torch.Tensor | None = None
+        self.bias_tab: torch.Tensor | None = None
         self._rows: OrderedDict = OrderedDict()  # key -> mask row (LRU order)
+        self._brows: OrderedDict = OrderedDict()  # ("B", ((id, bias), ...)) -> bias row (LRU order)
         self._slots: dict[int, tuple[int, object]] = {}  # seq_id -> (slot, seq)
         self._free: list[int] = list(range(max_slots - 1, -1, -1))
         self._dec: list[tuple[int, int]] = []  # (slot, token) decrements queued by uncount()
-        self.stats = {"mask_uploads": 0, "proc_steps": 0, "forced_rows": 0, "mask_rows_used": 0, "penalty_rows": 0}
+        self.stats = {"mask_uploads": 0, "proc_steps": 0, "forced_rows": 0, "mask_rows_used": 0, "penalty_rows": 0,
+                      "bias_uploads": 0, "bias_rows_used": 0}
 
-    # ---- tables (allocated together on first use: a captured graph sees both addresses) -------------------------
+    # ---- tables (allocated together on first use: a captured graph sees every address) --------------------------
     def tables(self) -> tuple[torch.Tensor, torch.Tensor]:
         if self.mask_tab is None:
             self.mask_tab = torch.zeros(self.n_mask_rows, self.W, dtype=torch.int32, device=self.device)
             self.counts = torch.zeros(self.max_slots, self.cnt_ld, dtype=torch.int32, device=self.device)
+            self.bias_tab = torch.zeros(self.n_bias_rows, BIAS_ROW_INTS, dtype=torch.int32, device=self.device)
         return self.mask_tab, self.counts
 
+    def bias_table(self) -> torch.Tensor:
+        """The logit-bias table (allocated with the other two)."""
+        self.tables()
+        return self.bias_tab
+
     # ---- host side ----------------------------------------------------------------------------------------------
-    def _mask_row(self, key, bits_fn, upd_rows: list, upd_words: list, used: set) -> int:
-        r = self._rows.get(key)
+    def _table_row(self, lru: OrderedDict, n_rows: int, key, words_fn, upd_rows: list, upd_words: list, used: set,
+                   stat: str) -> int:
+        """The table row of ``key`` in ``lru`` (a table of ``n_rows`` rows); a new key takes a free row or evicts the
+        least recently used one, and its words (``words_fn()``) join the step's updates."""
+        r = lru.get(key)
         if r is not None:
-            self._rows.move_to_end(key)
+            lru.move_to_end(key)
             used.add(r)
             return r
-        if len(self._rows) < self.n_mask_rows:
-            r = len(self._rows)
+        if len(lru) < n_rows:
+            r = len(lru)
         else:  # evict the least recently used key not needed by this step (a step has <= max_slots rows)
-            for k in self._rows:
-                if self._rows[k] not in used:
-                    r = self._rows.pop(k)
+            for k in lru:
+                if lru[k] not in used:
+                    r = lru.pop(k)
                     break
             else:  # pragma: no cover - more distinct sets in one step than table rows
-                raise RuntimeError("logits processor: more distinct allowed sets in one step than mask rows")
-        self._rows[key] = r
+                raise RuntimeError("logits processor: more distinct sets in one step than table rows")
+        lru[key] = r
         used.add(r)
         upd_rows.append(r)
-        upd_words.append(bits_fn())
-        self.stats["mask_uploads"] += 1
+        upd_words.append(words_fn())
+        self.stats[stat] += 1
         return r
+
+    def _mask_row(self, key, bits_fn, upd_rows: list, upd_words: list, used: set) -> int:
+        return self._table_row(self._rows, self.n_mask_rows, key, bits_fn, upd_rows, upd_words, used, "mask_uploads")
+
+    def _bias_row(self, pairs: tuple, upd_rows: list, upd_words: list, used: set) -> int:
+        def words(pairs=pairs):
+            w = np.zeros(BIAS_ROW_INTS, dtype=np.int32)
+            w[:len(pairs)] = [t for t, _ in pairs]
+            w[LOGIT_BIAS_MAX:LOGIT_BIAS_MAX + len(pairs)] = np.array([b for _, b in pairs],
+                                                                      dtype=np.float32).view(np.int32)
+            return w
+        return self._table_row(self._brows, self.n_bias_rows, ("B", pairs), words, upd_rows, upd_words, used,
+                               "bias_uploads")
 
     def _slot(self, seq, zero: list) -> int:
         e = self._slots.get(seq.seq_id)
@@ -124,6 +159,7 @@ class LogitsProcessor:
         proc = np.zeros((n, 8), dtype=np.int32)
         proc[:, 2] = -1
         upd_rows, upd_words, zero, used = [], [], [], set()
+        b_rows, b_words, b_used = [], [], set()
         V, W = self.V, self.W
         for i, s, spec in rows:
             p = s.params
@@ -161,6 +197,17 @@ class LogitsProcessor:
                 proc[i, 2] = self._slot(s, zero)
                 proc[i, 3:5] = np.array([p.presence_penalty, p.frequency_penalty], dtype=np.float32).view(np.int32)
                 self.stats["penalty_rows"] += 1
+            bias = getattr(p, "logit_bias", None)
+            if bias:
+                pairs = tuple(sorted((int(t), float(b)) for t, b in bias if float(b) != 0.0))
+                ids = [t for t, _ in pairs]
+                if len(pairs) > LOGIT_BIAS_MAX:
+                    raise ValueError(f"logit_bias holds {len(pairs)} entries, more than {LOGIT_BIAS_MAX}")
+                if any(not 0 <= t < V for t in ids) or len(set(ids)) != len(ids):
+                    raise ValueError(f"logit_bias names a token outside [0, {V}) or names one twice")
+                if pairs:
+                    proc[i, 5], proc[i, 6] = self._bias_row(pairs, b_rows, b_words, b_used), len(pairs)
+                    self.stats["bias_rows_used"] += 1
         self.stats["proc_steps"] += 1
         upd = ProcUpdates()
         if upd_rows:
@@ -171,6 +218,9 @@ class LogitsProcessor:
         if self._dec:
             upd.dec = np.asarray(self._dec, dtype=np.int32).reshape(-1, 2)
             self._dec = []
+        if b_rows:
+            upd.bias_rows = np.asarray(b_rows, dtype=np.int32)
+            upd.bias_words = np.stack(b_words)
         return proc, upd
 
     # ---- device side ----------------------------------------------------------------------------------------------
@@ -184,6 +234,12 @@ class LogitsProcessor:
                 raise ValueError("logits processor: mask update does not fit the table")
             rows = upload(upd.mask_rows.astype(np.int64))
             mask_tab.index_copy_(0, rows, upload(upd.mask_words))
+        if upd.bias_rows.size:
+            bias_tab = self.bias_table()
+            if int(upd.bias_rows.min()) < 0 or int(upd.bias_rows.max()) >= bias_tab.shape[0] \
+                    or upd.bias_words.shape != (upd.bias_rows.size, bias_tab.shape[1]):
+                raise ValueError("logits processor: logit-bias update does not fit the table")
+            bias_tab.index_copy_(0, upload(upd.bias_rows.astype(np.int64)), upload(upd.bias_words))
         if upd.dec.size:  # before the zeroing: a recycled slot starts from zero whatever was queued for it
             if int(upd.dec[:, 0].max()) >= counts.shape[0] or int(upd.dec[:, 1].max()) >= counts.shape[1]:
                 raise ValueError("logits processor: count decrement outside the count table")

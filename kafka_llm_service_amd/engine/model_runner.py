@@ -366,8 +366,8 @@ class ModelRunner:
         return self.sample_device(logits, self.sample_params(seqs))
 
     def sample_params(self, seqs: list[Sequence]) -> "SampleParams":
-        """Per-row sampling parameters of a step; rows with a token constraint or penalties get a logits-processing
-        row (engine/logits_proc.py) that the sampler kernel applies on the device. A constrained row's spec is
+        """Per-row sampling parameters of a step; rows with a token constraint, penalties or a logit bias get a
+        logits-processing row (engine/logits_proc.py) that the sampler kernel applies on the device. A constrained row's spec is
         computed from its landed tokens, or past a pending one when the grammar can guess its successor state
         (engine/constrained.py: a wrong guess rolls the row back one token); a forced token is returned in
         ``known`` so the engine writes it at launch."""
@@ -397,7 +397,7 @@ class ModelRunner:
                 if f is not None:
                     known = known or {}
                     known[i] = f
-            if allowed is not None or p.presence_penalty or p.frequency_penalty:
+            if allowed is not None or p.presence_penalty or p.frequency_penalty or p.logit_bias:
                 rows.append((i, s, allowed))
         proc = upd = None
         if rows:
@@ -427,7 +427,7 @@ class ModelRunner:
         if sp.proc is None:
             return {}
         mask_tab, counts = self.lp.tables()
-        return {"mask_tab": mask_tab, "counts": counts}
+        return {"mask_tab": mask_tab, "counts": counts, "bias_tab": self.lp.bias_table()}
 
     def sample_device(self, logits: torch.Tensor, sp: "SampleParams") -> torch.Tensor:
         n = logits.shape[0]

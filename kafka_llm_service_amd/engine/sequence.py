@@ -14,6 +14,8 @@ import time
 from dataclasses import dataclass, field
 from typing import Callable
 
+from kafka_llm_service_amd.engine.step_plan import LOGIT_BIAS_MAX
+
 
 PENDING = -1  # placeholder of a token still being sampled by the in-flight engine step (async scheduling)
 
@@ -40,8 +42,23 @@ class SamplingParams:
     # ops/csrc/logprobs.hip). They ride back in ``StepOutput.logprobs``.
     logprobs: bool = False
     top_logprobs: int = 0
+    # OpenAI ``logit_bias``: (token id, bias in [-100, 100]) pairs, at most LOGIT_BIAS_MAX of them, added to the
+    # logits inside the sampler kernel after the penalties and before temperature and the grammar mask; normalised
+    # here to a tuple sorted by id without zero entries, or None (picklable: it crosses the worker pipes)
+    logit_bias: tuple | None = None
 
     def __post_init__(self):
+        if self.logit_bias is not None:
+            items = self.logit_bias.items() if isinstance(self.logit_bias, dict) else self.logit_bias
+            pairs = tuple(sorted((int(t), float(b)) for t, b in items if float(b) != 0.0))
+            ids = [t for t, _ in pairs]
+            if any(t < 0 for t in ids) or len(set(ids)) != len(ids):
+                raise ValueError("logit_bias token ids must be distinct non-negative integers")
+            if any(not -100.0 <= b <= 100.0 for _, b in pairs):  # (a NaN fails both comparisons)
+                raise ValueError("logit_bias values must lie in [-100, 100]")
+            if len(pairs) > LOGIT_BIAS_MAX:
+                raise ValueError(f"logit_bias holds more than {LOGIT_BIAS_MAX} entries")
+            self.logit_bias = pairs or None
         if not isinstance(self.top_logprobs, int) or isinstance(self.top_logprobs, bool) \
                 or not 0 <= self.top_logprobs <= 20:
             raise ValueError("top_logprobs must be an integer in 0..20")

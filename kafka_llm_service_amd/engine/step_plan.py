@@ -27,6 +27,8 @@ MIN_DECODE_KEYS = 256      # smallest key range of one decode work item
 DECODE_TARGET_ITEMS = 1344  # (768 / 1536 / 2304 lose to it: profiles/r04/bench_ab_decode_target_blas.jsonl)
 MAX_PARTIALS = 64           # partial slots per row that the decode kernel's fused merge reads (one lane each)
 MAX_PREFIX_CHUNKS = 32
+LOGIT_BIAS_MAX = 300                # entries of one request's logit_bias (kafka_abi.h LOGIT_BIAS_MAX)
+BIAS_ROW_INTS = 2 * LOGIT_BIAS_MAX  # one row of the sampler's bias table: ids, then the fp32 bits of their biases
 
 
 def cdiv(a, b):
@@ -169,10 +171,13 @@ class ProcUpdates:
     zero_slots: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))    # [z] count rows to clear
     # [d, 2] (slot, token): counts[slot][token] -= 1 — a token the sampler counted and the engine rolled back
     dec: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.int32))
+    # logit-bias rows: [k] rows of bias_tab and [k, 2 * LOGIT_BIAS_MAX] their words (ascending ids, then fp32 bits)
+    bias_rows: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    bias_words: np.ndarray = field(default_factory=lambda: np.zeros((0, BIAS_ROW_INTS), np.int32))
 
     @property
     def empty(self) -> bool:
-        return not (self.mask_rows.size or self.zero_slots.size or self.dec.size)
+        return not (self.mask_rows.size or self.zero_slots.size or self.dec.size or self.bias_rows.size)
 
 
 @dataclass
@@ -226,7 +231,10 @@ def pack_plan(h: HostStep, sp: SampleParams) -> tuple[np.ndarray, np.ndarray]:
              sp.topk.astype(np.int32, copy=False), sp.seeds.astype(np.int64, copy=False),
              proc.astype(np.int32, copy=False), upd.mask_rows.astype(np.int32, copy=False),
              upd.mask_words.astype(np.int32, copy=False), upd.zero_slots.astype(np.int32, copy=False),
-             upd.dec.astype(np.int32, copy=False)]
+             upd.dec.astype(np.int32, copy=False), upd.bias_rows.astype(np.int32, copy=False),
+             upd.bias_words.astype(np.int32, copy=False)]
+    if upd.bias_rows.size and upd.bias_words.shape != (upd.bias_rows.size, BIAS_ROW_INTS):
+        raise ValueError("plan: logit-bias update rows and words disagree")
     payload = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in parts])
     hdr = np.zeros(PLAN_HDR, dtype=np.int64)
     hdr[0] = 1
@@ -235,6 +243,7 @@ def pack_plan(h: HostStep, sp: SampleParams) -> tuple[np.ndarray, np.ndarray]:
     W = upd.mask_words.shape[1] if upd.mask_rows.size else 0
     hdr[1 + k:1 + k + 10] = [h.i64.size, i32.size, n, int(sp.greedy), payload.size, proc.shape[0],
                              upd.mask_rows.size, W, upd.zero_slots.size, upd.dec.shape[0]]
+    hdr[1 + k + 10] = upd.bias_rows.size  # (0 and no bytes behind ``dec`` for a step without new bias rows)
     return hdr, payload
 
 
@@ -242,6 +251,7 @@ def unpack_plan(hdr: np.ndarray, payload: np.ndarray) -> tuple[HostStep, SampleP
     k = len(_PLAN_SCALARS)
     h = HostStep(**{f: int(v) for f, v in zip(_PLAN_SCALARS, hdr[1:1 + k])})
     n64, n32, n, greedy, _, n_proc, n_mask, W, n_zero, n_dec = (int(v) for v in hdr[1 + k:1 + k + 10])
+    n_bias = int(hdr[1 + k + 10])
     o = 0
 
     def take(dt, cnt):
@@ -259,7 +269,8 @@ def unpack_plan(hdr: np.ndarray, payload: np.ndarray) -> tuple[HostStep, SampleP
                       bool(greedy))
     proc = take(np.int32, n_proc * 8).reshape(n_proc, 8)
     upd = ProcUpdates(take(np.int32, n_mask), take(np.int32, n_mask * W).reshape(n_mask, W),
-                      take(np.int32, n_zero), take(np.int32, 2 * n_dec).reshape(n_dec, 2))
+                      take(np.int32, n_zero), take(np.int32, 2 * n_dec).reshape(n_dec, 2), take(np.int32, n_bias),
+                      take(np.int32, n_bias * BIAS_ROW_INTS).reshape(n_bias, BIAS_ROW_INTS))
     sp.proc = proc if n_proc else None
     sp.upd = None if upd.empty else upd
     return h, sp

@@ -4,13 +4,17 @@ Same field names and validation bounds (temperature in [0, 2], max_tokens > 0, t
 [-2, 2]). ``usage`` is populated from real engine token counts (quirk Q8); ``stream_options.include_usage`` adds a
 final usage chunk like the OpenAI API; ``tool_choice`` / ``tools`` are accepted (the server's own tool set is used,
 ``tool_choice`` steers constrained decoding); ``logprobs`` / ``top_logprobs`` (0..20, only with ``logprobs: true``)
-return per-token log-probabilities of the model's raw logits.
+return per-token log-probabilities of the model's raw logits; ``logit_bias`` maps token ids (JSON string keys) to
+biases in [-100, 100], at most 300 of them, added to the logits inside the sampler.
 """
 from __future__ import annotations
 
+import math
 from typing import Any, Optional
 
-from pydantic import BaseModel, Field, model_validator
+from pydantic import BaseModel, Field, field_validator, model_validator
+
+LOGIT_BIAS_MAX = 300  # non-zero entries of one request's logit_bias (the sampler's table row, engine/logits_proc.py)
 
 
 class ChatMessage(BaseModel):
@@ -43,6 +47,27 @@ class ChatCompletionRequest(BaseModel):
     # per-token log-probabilities of the model's raw logits, and the 0..20 most likely tokens at each position
     logprobs: Optional[bool] = None
     top_logprobs: Optional[int] = Field(None, ge=0, le=20)
+    # token id (a base-10 string key, as JSON has it) -> bias in [-100, 100] added to that token's logit
+    logit_bias: Optional[dict[str, float]] = None
+
+    @field_validator("logit_bias")
+    @classmethod
+    def _logit_bias_bounds(cls, v):
+        if v is None:
+            return v
+        ids = set()
+        for k, b in v.items():
+            if not (k.isascii() and k.isdigit()):
+                raise ValueError(f"logit_bias key {k!r} is not a non-negative base-10 token id")
+            if not math.isfinite(b) or not -100 <= b <= 100:
+                raise ValueError(f"logit_bias value for token {k} must be a finite number in [-100, 100]")
+            if b != 0:
+                if int(k) in ids:
+                    raise ValueError(f"logit_bias names token {int(k)} twice")
+                ids.add(int(k))
+        if len(ids) > LOGIT_BIAS_MAX:
+            raise ValueError(f"logit_bias holds more than {LOGIT_BIAS_MAX} non-zero entries")
+        return v
 
     @model_validator(mode="after")
     def _top_logprobs_needs_logprobs(self):

@@ -151,14 +151,29 @@ class EngineLLMProvider(LLMProvider):
                                 frequency_penalty: float | None = None, presence_penalty: float | None = None,
                                 seed: int | None = None, routing_key: str | None = None,
                                 tool_choice: Any = None, logprobs: bool | None = None,
-                                top_logprobs: int | None = None,
+                                top_logprobs: int | None = None, logit_bias: dict | None = None,
                                 **kwargs: Any) -> AsyncGenerator[StreamChunk, None]:
         """``logprobs`` / ``top_logprobs``: every non-special token the provider consumes yields one OpenAI entry
         ({token, logprob, bytes, top_logprobs}) over the model's RAW logits; a content chunk carries the entries of
         the tokens landed since the last chunk that carried any, the final chunk the rest. The stop-string hold-back
         buffers text, not entries, and a stop-string cut ends the text inside a token: past such a cut the entries'
-        bytes may run a few characters beyond the returned text. Tool-call replies carry none."""
+        bytes may run a few characters beyond the returned text. Tool-call replies carry none.
+
+        ``logit_bias``: {token id: bias in [-100, 100]} added to those tokens' logits in the sampler kernel (after
+        the penalties, before temperature and the grammar mask); logprobs stay those of the raw logits. An id outside
+        the model's vocabulary is refused before anything is submitted."""
         self.validate_messages(messages)
+        bias = None
+        if logit_bias:
+            V = self.client.model_cfg.vocab_size
+            try:
+                bias = {int(k): float(b) for k, b in logit_bias.items()}
+            except (TypeError, ValueError):
+                raise LLMProviderError("logit_bias must map token ids to numbers", provider="engine", status_code=400)
+            bad = [t for t in bias if not 0 <= t < V]
+            if bad:
+                raise LLMProviderError(f"logit_bias names token id {bad[0]}, outside this model's vocabulary of {V} "
+                                       "tokens", provider="engine", status_code=400)
         if tools is None:
             tools = await self.get_tools()
         with trace.span("api_render", "api", f"thr:{routing_key}", messages=len(messages)):
@@ -173,7 +188,7 @@ class EngineLLMProvider(LLMProvider):
                                 frequency_penalty=float(frequency_penalty or 0.0),
                                 presence_penalty=float(presence_penalty or 0.0), seed=seed,
                                 ignore_eos=self.ignore_eos, logprobs=bool(logprobs),
-                                top_logprobs=int(top_logprobs or 0) if logprobs else 0,
+                                top_logprobs=int(top_logprobs or 0) if logprobs else 0, logit_bias=bias,
                                 tool_grammar=({"tools": tools, "tool_choice": self._choice(tool_choice, messages)}
                                               if tools and self.constrain_tools else None))
         stops = [s for s in (stop or []) if s]

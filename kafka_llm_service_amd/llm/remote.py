@@ -60,6 +60,8 @@ class RemoteOpenAIProvider(LLMProvider):
         for k in ("top_p", "frequency_penalty", "presence_penalty", "seed", "user", "tool_choice"):
             if kw.get(k) is not None:
                 body[k] = kw[k]
+        if kw.get("logit_bias"):  # token id -> bias, unchanged (JSON keys are strings on the wire)
+            body["logit_bias"] = {str(k): b for k, b in kw["logit_bias"].items()}
         return body
 
     async def stream_completion(self, messages: list[Message], *, temperature: Optional[float] = None,

@@ -199,21 +199,28 @@ def _sample_ws(dev: torch.device, n: int) -> torch.Tensor:
     return t
 
 
+LOGIT_BIAS_MAX = ref.LOGIT_BIAS_MAX  # entries of one request's logit_bias; a bias_tab row is twice as many ints
+
+
 def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
-           mask_tab=None, counts=None) -> torch.Tensor:
+           mask_tab=None, counts=None, bias_tab=None) -> torch.Tensor:
     """Sampled ids [B] (int64). ``proc`` int32 [B, 8] turns on the per-row logits processing of the kernel (grammar
     bitmask rows of ``mask_tab``, forced ids, presence / frequency penalties from ``counts``, which the sampler
-    updates with every drawn token; engine/logits_proc.py builds all three)."""
+    updates with every drawn token, sparse logit biases from rows of ``bias_tab``; engine/logits_proc.py builds all
+    four). A ``proc`` row that names bias entries without a ``bias_tab`` is an error."""
     B = logits.shape[0]
     if out is None:
         out = torch.empty(B, dtype=torch.long, device=logits.device)
+    if proc is not None and bias_tab is None and bool((proc[:B, 6] > 0).any()):  # (the engine always passes the table)
+        raise ValueError("sample: proc rows carry logit-bias entries but no bias_tab was given")
     if _gpu(logits):
         V = logits.shape[1]
         nsplit = _SAMPLE_SPLIT if V >= 16384 else 1  # a row over 8 workgroups (greedy / plain temperature)
         ws = _sample_ws(logits.device, 65536 + 2 * B * nsplit) if nsplit > 1 else None
-        ext().sample(logits, temperature, top_p, top_k, seeds, step, out, ws, nsplit, proc, mask_tab, counts)
+        ext().sample(logits, temperature, top_p, top_k, seeds, step, out, ws, nsplit, proc, mask_tab, counts,
+                     bias_tab)
     else:
-        ref.sample(logits, temperature, top_p, top_k, seeds, step, out, proc, mask_tab, counts)
+        ref.sample(logits, temperature, top_p, top_k, seeds, step, out, proc, mask_tab, counts, bias_tab)
     return out
 
 

@@ -318,7 +318,8 @@ static void attn_merge(at::Tensor part, at::Tensor lse, at::Tensor out, c10::opt
 static void sample(at::Tensor logits, c10::optional<at::Tensor> temperature, c10::optional<at::Tensor> top_p,
                    c10::optional<at::Tensor> top_k, c10::optional<at::Tensor> seeds, c10::optional<at::Tensor> step,
                    at::Tensor out, c10::optional<at::Tensor> ws, int64_t nsplit, c10::optional<at::Tensor> proc,
-                   c10::optional<at::Tensor> mask_tab, c10::optional<at::Tensor> counts) {
+                   c10::optional<at::Tensor> mask_tab, c10::optional<at::Tensor> counts,
+                   c10::optional<at::Tensor> bias_tab) {
   CHECK_CUDA(logits); CHECK_DT(out, at::kLong);
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [B, V]");
   const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
@@ -350,7 +351,8 @@ static void sample(at::Tensor logits, c10::optional<at::Tensor> temperature, c10
   const int* pp = nullptr;
   const uint32_t* mt = nullptr;
   int* cp = nullptr;
-  int64_t mld = 0, cld = 0;
+  const int* bt = nullptr;
+  int64_t mld = 0, cld = 0, bld = 0;
   if (proc.has_value()) {
     TORCH_CHECK(proc->is_cuda() && proc->scalar_type() == at::kInt && proc->is_contiguous() && proc->dim() == 2 &&
                     proc->size(0) >= B && proc->size(1) == 8, "sample: proc must be int32 [>= B, 8] on the GPU");
@@ -367,12 +369,20 @@ static void sample(at::Tensor logits, c10::optional<at::Tensor> temperature, c10
       cp = counts->data_ptr<int>();
       cld = counts->size(1);
     }
+    // logit-bias rows (proc[5] = row, proc[6] = entries): ids then fp32 bits, kafka_abi.h; a row start is 16-B aligned
+    if (bias_tab.has_value()) {
+      TORCH_CHECK(bias_tab->is_cuda() && bias_tab->scalar_type() == at::kInt && bias_tab->is_contiguous() &&
+                      bias_tab->dim() == 2 && bias_tab->size(1) % 4 == 0,
+                  "sample: bias_tab must be int32 [rows, 2 * LOGIT_BIAS_MAX] on the GPU");
+      bt = bias_tab->data_ptr<int>();
+      bld = bias_tab->size(1);
+    }
   }
   CHECK_HIP(kafka_launch_sample(logits.data_ptr(), is_bf16, logits.stride(0), B, V,
                                  (const float*)fp(temperature, at::kFloat), (const float*)fp(top_p, at::kFloat),
                                  (const int*)fp(top_k, at::kInt), (const int64_t*)fp(seeds, at::kLong),
                                  (const int64_t*)st, out.data_ptr<int64_t>(), wp, wp ? (int)nsplit : 1, pp, mt, mld,
-                                 cp, cld, cur_stream()));
+                                 cp, cld, bt, bld, cur_stream()));
 }
 
 // Per-token logprobs (logprobs.hip). rows: int32 [R] or none (rows 0..R-1); tok_lp f32 [R], top_lp f32 [R, K] and
@@ -996,7 +1006,8 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("pre") = py::none(), py::arg("npre") = 0);
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"), py::arg("top_p"), py::arg("top_k"),
         py::arg("seeds"), py::arg("step"), py::arg("out"), py::arg("ws") = py::none(), py::arg("nsplit") = 1,
-        py::arg("proc") = py::none(), py::arg("mask_tab") = py::none(), py::arg("counts") = py::none());
+        py::arg("proc") = py::none(), py::arg("mask_tab") = py::none(), py::arg("counts") = py::none(),
+        py::arg("bias_tab") = py::none());
   m.def("token_logprobs", &token_logprobs, py::arg("logits"), py::arg("tokens"), py::arg("rows"), py::arg("k"),
         py::arg("tok_lp"), py::arg("top_lp"), py::arg("top_id"), py::arg("ws") = py::none(), py::arg("nsplit") = 1);
   m.def("wstream_plan", &wstream_plan);

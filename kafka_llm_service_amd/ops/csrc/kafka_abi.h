@@ -50,6 +50,11 @@ struct DecodeItem {
 static_assert(sizeof(AttnWorkItem) == ITEM_INTS * sizeof(int), "AttnWorkItem is one row of the items tensor");
 static_assert(sizeof(DecodeItem) == ITEM_INTS * sizeof(int), "DecodeItem is one row of the items tensor");
 
+// ---- sampler logit bias (sampling.hip RowProc; engine/logits_proc.py) ---------------------------------------------
+// bias_tab int32 [rows, >= 2 * LOGIT_BIAS_MAX]: per row the token ids in strictly ascending order at [0, n), the fp32
+// bits of their biases at [LOGIT_BIAS_MAX, LOGIT_BIAS_MAX + n); proc[5] names the row, proc[6] is n (0: no bias)
+constexpr int LOGIT_BIAS_MAX = 300;  // OpenAI's bound on the entries of one request's logit_bias
+
 // ---- weight tile formats of the streaming GEMMs (wstream_gemm.hip WFMT; ops.WEIGHT_FORMATS) ----------------------
 // bf16 tiles [N/32][K/16][64 lanes][8]; fp8: e4m3 bytes [N/32][K/32][64][16] + fp32 row scales [N]; MXFP4: e2m1 bytes
 // [N/32][K/64][64][16] + e8m0 block exponents [N/32][K/64][32][2]
@@ -144,11 +149,13 @@ hipError_t kafka_launch_attn_tile(const void* items, int n_items, const bf16* q,
 // ws (optional): int32 workspace of >= SAMPLE_MAX_ROWS + 2 * B * nsplit entries whose first SAMPLE_MAX_ROWS are zero
 // (tickets, re-armed by the kernel); without it every row is one workgroup. proc (optional, int32 [B, 8], see
 // RowProc) selects the logits-processing instantiation; mask_tab uint32 [rows, mask_ld] and counts int32
-// [slots, cnt_ld] (cnt_ld >= V rounded up to 8) are only read for rows that name them.
+// [slots, cnt_ld] (cnt_ld >= V rounded up to 8) are only read for rows that name them; bias_tab (optional, int32
+// [rows, bias_ld], bias_ld >= 2 * LOGIT_BIAS_MAX and a multiple of 4) likewise — without it no row is biased.
 hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int64_t stride, int B, int V, const float* temperature,
                                const float* top_p, const int* top_k, const int64_t* seeds, const int64_t* step,
                                int64_t* out_tokens, int* ws, int nsplit, const int* proc, const uint32_t* mask_tab,
-                               int64_t mask_ld, int* counts, int64_t cnt_ld, hipStream_t st);
+                               int64_t mask_ld, int* counts, int64_t cnt_ld, const int* bias_tab, int64_t bias_ld,
+                               hipStream_t st);
 
 // ---- logprobs.hip
 // Log softmax of the RAW logits (no temperature / penalties / mask) at each scored row's sampled token, and the row's

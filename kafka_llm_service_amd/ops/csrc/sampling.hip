@@ -98,21 +98,29 @@ __device__ __forceinline__ float gumbel_fast(uint64_t key, uint32_t idx) {
 //   [0] mode: 0 = none, 1 = vocab bitmask (row [1] of mask_tab), 2 = forced token ([1] is the id: no draw at all)
 //   [2] penalty slot: row of counts[slot][V] (the row's generated-token counts, -1 = none)
 //   [3] presence penalty, [4] frequency penalty (fp32 bits)
-// The logit of token i becomes  x_i - freq * c_i - (c_i > 0 ? pres : 0)  (OpenAI presence / frequency penalties,
-// before temperature), or -inf where the grammar mask has a zero bit; the sampler then runs unchanged over it, and
-// the thread that writes the row's token also bumps counts[slot][token] — the next step (stream-ordered) sees it, so
-// penalties need no landed tokens on the host and no per-row torch ops over the [B, V] logits.
+//   [5] logit-bias row of bias_tab, [6] its entry count (0 = no bias; clamped to LOGIT_BIAS_MAX)
+// The logit of token i becomes  (x_i - freq * c_i - (c_i > 0 ? pres : 0)) + b_i  (OpenAI presence / frequency
+// penalties, then the request's logit_bias, before temperature), or -inf where the grammar mask has a zero bit; the
+// sampler then runs unchanged over it, and the thread that writes the row's token also bumps counts[slot][token] —
+// the next step (stream-ordered) sees it, so penalties need no landed tokens on the host and no per-row torch ops
+// over the [B, V] logits.
+// The bias is sparse: a row of bias_tab holds n <= LOGIT_BIAS_MAX ascending ids and their biases (kafka_abi.h). A
+// workgroup stages its row's pairs in LDS once; every 16-byte logit load then finds the first id >= its index by
+// binary search there (<= 9 LDS reads) and adds the few biases that fall into its 8 indices: no dense [slots, V]
+// table, no HBM traffic per pass.
 struct RowProc {
   int mode, arg, slot;
   float pres, freq;
   const uint32_t* mask;
   int* cnt;
+  int nb;           // staged logit-bias pairs (bias_lds)
+  const int* bias;  // the row of bias_tab they come from
 };
 
 template <bool PROC>
 __device__ __forceinline__ RowProc row_proc(const int* proc, const uint32_t* mask_tab, int64_t mask_ld, int* counts,
-                                            int64_t cnt_ld, int row) {
-  RowProc r{0, -1, -1, 0.f, 0.f, nullptr, nullptr};
+                                            int64_t cnt_ld, const int* bias_tab, int64_t bias_ld, int row) {
+  RowProc r{0, -1, -1, 0.f, 0.f, nullptr, nullptr, 0, nullptr};
   if constexpr (PROC) {
     const int* p = proc + (int64_t)row * 8;
     r.mode = p[0];
@@ -122,8 +130,31 @@ __device__ __forceinline__ RowProc row_proc(const int* proc, const uint32_t* mas
     r.freq = __int_as_float(p[4]);
     if (r.mode == 1) r.mask = mask_tab + (int64_t)r.arg * mask_ld;
     if (r.slot >= 0) r.cnt = counts + (int64_t)r.slot * cnt_ld;
+    if (bias_tab != nullptr && p[6] > 0) {
+      r.nb = min(p[6], LOGIT_BIAS_MAX);
+      r.bias = bias_tab + (int64_t)p[5] * bias_ld;
+    }
   }
   return r;
+}
+
+// The workgroup's staged bias pairs: ids at [0, nb), biases (fp32 bits) at [LOGIT_BIAS_MAX, LOGIT_BIAS_MAX + nb).
+// Only the PROC instantiations name it, so the others carry no LDS for it.
+template <bool PROC>
+__device__ __forceinline__ int* bias_lds() {
+  static_assert(PROC, "the plain sampler has no bias table");
+  __shared__ int sb[2 * LOGIT_BIAS_MAX];
+  return sb;
+}
+
+// index of the first staged id >= i (nb if none)
+__device__ __forceinline__ int bias_lower_bound(const int* sb, int nb, int i) {
+  int lo = 0, hi = nb;
+  while (lo < hi) {
+    const int m = (lo + hi) >> 1;
+    if (sb[m] < i) lo = m + 1; else hi = m;
+  }
+  return lo;
 }
 
 // 8 logits starting at index i0 (a multiple of 8), processed
@@ -137,6 +168,17 @@ __device__ __forceinline__ void load8p(const T* x, int i0, const RowProc& rp, fl
       const int c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] -= rp.freq * (float)c[j] + (c[j] > 0 ? rp.pres : 0.f);
+    }
+    if (rp.nb > 0) {
+      const int* sb = bias_lds<PROC>();
+      for (int k = bias_lower_bound(sb, rp.nb, i0); k < rp.nb; ++k) {
+        const int d = sb[k] - i0;
+        if (d >= 8) break;
+        const float b = __int_as_float(sb[LOGIT_BIAS_MAX + k]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)  // (v stays in registers: no indexing by d)
+          if (j == d) v[j] += b;
+      }
     }
     if (rp.mask != nullptr) {
       const uint32_t bits = (rp.mask[i0 >> 5] >> (i0 & 31)) & 0xffu;
@@ -154,6 +196,11 @@ __device__ __forceinline__ float load1p(const T* x, int i, const RowProc& rp) {
     if (rp.cnt != nullptr) {
       const int c = rp.cnt[i];
       v -= rp.freq * (float)c + (c > 0 ? rp.pres : 0.f);
+    }
+    if (rp.nb > 0) {
+      const int* sb = bias_lds<PROC>();
+      const int k = bias_lower_bound(sb, rp.nb, i);
+      if (k < rp.nb && sb[k] == i) v += __int_as_float(sb[LOGIT_BIAS_MAX + k]);
     }
     if (rp.mask != nullptr && !((rp.mask[i >> 5] >> (i & 31)) & 1u)) v = -INFINITY;
   }
@@ -177,16 +224,27 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
                                                       int64_t* __restrict__ out_tokens, int max_rounds,
                                                       int* __restrict__ ws, const int* __restrict__ proc,
                                                       const uint32_t* __restrict__ mask_tab, int64_t mask_ld,
-                                                      int* __restrict__ counts, int64_t cnt_ld) {
+                                                      int* __restrict__ counts, int64_t cnt_ld,
+                                                      const int* __restrict__ bias_tab, int64_t bias_ld) {
   __shared__ float sv[SNT / 64];
   __shared__ int si[SNT / 64];
   __shared__ float red[SNT / 64];
   const int row = blockIdx.x, sp = blockIdx.y, nsplit = gridDim.y;
   const T* x = logits + (int64_t)row * stride;
-  const RowProc rp = row_proc<PROC>(proc, mask_tab, mask_ld, counts, cnt_ld, row);
+  const RowProc rp = row_proc<PROC>(proc, mask_tab, mask_ld, counts, cnt_ld, bias_tab, bias_ld, row);
   if (PROC && rp.mode == 2) {  // forced token (a fixed piece of a tool-call grammar): every split returns, no ticket
     if (sp == 0 && threadIdx.x == 0) emit_token<PROC>(out_tokens, row, rp.arg, V, rp);
     return;
+  }
+  if constexpr (PROC) {
+    if (rp.nb > 0) {  // rp is the row's, so the branch and its barrier are uniform; every split stages the same pairs
+      int* sb = bias_lds<PROC>();
+      if ((int)threadIdx.x < rp.nb) {
+        sb[threadIdx.x] = rp.bias[threadIdx.x];
+        sb[LOGIT_BIAS_MAX + threadIdx.x] = rp.bias[LOGIT_BIAS_MAX + threadIdx.x];
+      }
+      __syncthreads();
+    }
   }
   const float temp = temperature ? temperature[row] : 0.f;
   const int nvec = V >> 3;
@@ -340,21 +398,24 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
 // ws (optional): int32 workspace of >= SAMPLE_MAX_ROWS + 2 * B * nsplit entries whose first SAMPLE_MAX_ROWS are zero
 // (tickets, re-armed by the kernel); without it every row is one workgroup. proc (optional, int32 [B, 8], see
 // RowProc) selects the logits-processing instantiation; mask_tab uint32 [rows, mask_ld] and counts int32
-// [slots, cnt_ld] (cnt_ld >= V rounded up to 8) are only read for rows that name them.
+// [slots, cnt_ld] (cnt_ld >= V rounded up to 8) are only read for rows that name them; bias_tab int32 [rows, bias_ld]
+// (kafka_abi.h) likewise — without it the kernel biases no row, whatever proc[6] says.
 extern "C" hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int64_t stride, int B, int V, const float* temperature,
                          const float* top_p, const int* top_k, const int64_t* seeds, const int64_t* step,
                          int64_t* out_tokens, int* ws, int nsplit, const int* proc, const uint32_t* mask_tab,
-                         int64_t mask_ld, int* counts, int64_t cnt_ld, hipStream_t st) {
+                         int64_t mask_ld, int* counts, int64_t cnt_ld, const int* bias_tab, int64_t bias_ld,
+                         hipStream_t st) {
   if (B == 0) return hipSuccess;
   if (ws == nullptr || nsplit < 1) nsplit = 1;
   if (B > SAMPLE_MAX_ROWS || nsplit > 64) return hipErrorInvalidValue;
   if (proc != nullptr && (mask_ld * 32 < V || (counts != nullptr && cnt_ld < ((V + 7) & ~7))))
     return hipErrorInvalidValue;
+  if (proc != nullptr && bias_tab != nullptr && bias_ld < 2 * LOGIT_BIAS_MAX) return hipErrorInvalidValue;
   const dim3 grid(B, nsplit);
 #define KAFKA_SAMPLE(T_, P_)                                                                                       \
   sample_kernel<T_, P_><<<grid, SNT, 0, st>>>(reinterpret_cast<const T_*>(logits), stride, V, temperature, top_p, \
                                               top_k, seeds, step, out_tokens, 32, ws, proc, mask_tab, mask_ld,     \
-                                              counts, cnt_ld)
+                                              counts, cnt_ld, bias_tab, bias_ld)
   if (is_bf16) {
     if (proc) KAFKA_SAMPLE(bf16, true); else KAFKA_SAMPLE(bf16, false);
   } else {

@@ -447,9 +447,14 @@ def attn_merge(part, lse, out, lse_out=None, pre=None, npre=0):
                                                  torch.full_like(L[..., 0], float("-inf"))))
 
 
-def process_logits(logits, proc, mask_tab, counts):
+LOGIT_BIAS_MAX = 300  # entries of one bias_tab row (csrc/kafka_abi.h): ids at [0, n), fp32 bits at [LOGIT_BIAS_MAX, ..)
+
+
+def process_logits(logits, proc, mask_tab, counts, bias_tab=None):
     """The sampler's per-row logits processing (csrc/sampling.hip RowProc) in fp32: penalties from the row's token
-    counts, then the grammar bitmask (-inf where a bit is 0). Returns (processed fp32 logits, forced ids or -1)."""
+    counts, then the row's sparse logit bias — ``(x - freq * c - (c > 0 ? pres : 0)) + b``, one fp32 add after the
+    penalty arithmetic — then the grammar bitmask (-inf where a bit is 0, whatever the bias). Returns (processed fp32
+    logits, forced ids or -1)."""
     B, V = logits.shape
     x = logits.float().clone()
     forced = torch.full((B,), -1, dtype=torch.long)
@@ -463,6 +468,13 @@ def process_logits(logits, proc, mask_tab, counts):
         if slot >= 0:
             c = counts[slot, :V].to(x.device).float()
             x[b] -= freq * c + pres * (c > 0).float()
+        nb = min(int(pr[b, 6]), LOGIT_BIAS_MAX)  # (the kernel's clamp)
+        if nb > 0:
+            if bias_tab is None:
+                raise ValueError("process_logits: a proc row carries logit-bias entries but no bias_tab was given")
+            row = bias_tab[int(pr[b, 5])].cpu()
+            ids = row[:nb].long().to(x.device)
+            x[b, ids] += row[LOGIT_BIAS_MAX:LOGIT_BIAS_MAX + nb].clone().view(torch.float32).to(x.device)
         if mode == 1:
             words = mask_tab[arg].to(torch.int64) & 0xFFFFFFFF
             bits = (words[:, None] >> torch.arange(32)) & 1
@@ -472,14 +484,14 @@ def process_logits(logits, proc, mask_tab, counts):
 
 
 def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
-           mask_tab=None, counts=None):
+           mask_tab=None, counts=None, bias_tab=None):
     """CPU sampler with the same semantics (not the same random stream) as the HIP kernel: the sort-based definition
     of top-k / top-p and the CPU engine path. ``sample_replay`` below reproduces the kernel's own stream and
     decisions draw by draw."""
     B, V = logits.shape
     forced = None
     if proc is not None:
-        x, forced = process_logits(logits, proc, mask_tab, counts)
+        x, forced = process_logits(logits, proc, mask_tab, counts, bias_tab)
     else:
         x = logits.float()
     res = torch.empty(B, dtype=torch.long, device=logits.device)
@@ -657,7 +669,7 @@ def _replay_filtered(x, xv, tp, tk, seeds, steps):
 
 
 def sample_replay(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
-                  mask_tab=None, counts=None, nsplit: int = 1) -> SampleReplay:
+                  mask_tab=None, counts=None, nsplit: int = 1, bias_tab=None) -> SampleReplay:
     """CPU replay of csrc/sampling.hip with the kernel's own random stream: the arguments of ``ops.sample`` plus
     ``nsplit`` (the workgroups a greedy / plain-temperature row is split over; it must not change the result). Every
     row whose ``ambiguous`` flag is clear has exactly one right token and the kernel must return it. Logits are finite
@@ -667,7 +679,7 @@ def sample_replay(logits, temperature=None, top_p=None, top_k=None, seeds=None, 
     assert 1 <= nsplit <= 64
     forced = None
     if proc is not None:
-        x, forced = process_logits(logits, proc, mask_tab, counts)
+        x, forced = process_logits(logits, proc, mask_tab, counts, bias_tab)
     else:
         x = logits.float()
     x = x.cpu().contiguous().numpy()

@@ -110,6 +110,10 @@ def _sampling_kwargs(req: ChatCompletionRequest) -> dict[str, Any]:
     if req.logprobs:  # (a request that does not ask passes nothing new down)
         kw["logprobs"] = True
         kw["top_logprobs"] = req.top_logprobs or 0
+    if req.logit_bias:  # (an empty or all-zero object means "no bias": nothing new goes down)
+        bias = {int(k): float(b) for k, b in req.logit_bias.items() if b != 0}
+        if bias:
+            kw["logit_bias"] = bias
     return kw
 
 
@@ -432,6 +436,15 @@ def create_app(config: ServerConfig | None = None, state: ServerState | None = N
     @app.exception_handler(ValueError)
     async def _value_error(request: Request, exc: ValueError):
         return JSONResponse({"detail": str(exc)}, status_code=400)
+
+    from kafka_llm_service_amd.llm.types import LLMProviderError
+
+    @app.exception_handler(LLMProviderError)
+    async def _provider_error(request: Request, exc: LLMProviderError):
+        # a request the provider refused before submitting it (a logit_bias id outside the vocabulary, a prompt over
+        # the context length) keeps the provider's 4xx on non-stream requests; the stream path sends an error frame
+        code = exc.status_code if exc.status_code and 400 <= exc.status_code < 500 else 500
+        return JSONResponse({"detail": str(exc)}, status_code=code)
 
     from kafka_llm_service_amd.engine.client import EngineUnavailable
 
