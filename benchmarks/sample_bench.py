@@ -4,6 +4,9 @@
   --proc none      no logits processing (the headline path)
   --proc penalty   every row a penalty-only processing row (presence 0.5, frequency 1.5, zero counts)
   --logit-bias N   every row carries N bias entries (its own table row; implies a processing row); 0 = none
+  --min-p P        every row carries min_p = P in proc[7] (implies a processing row): under T = 0.7 a split two-pass
+                   row, or one more test in the rejection loop with --top-p; greedy rows ignore it; 0 = none
+  --top-p P        every row samples with top_p = P (the one-workgroup rejection loop under T = 0.7); 1 = none
 
 The script also runs on a tree from before logit_bias (``ops.sample`` without ``bias_tab``): there --logit-bias must
 be 0, which is how the parent's numbers beside this tree's were taken."""
@@ -20,6 +23,8 @@ from kafka_llm_service_amd import ops
 ap = argparse.ArgumentParser()
 ap.add_argument("--proc", choices=("none", "penalty"), default="none")
 ap.add_argument("--logit-bias", type=int, default=0)
+ap.add_argument("--min-p", type=float, default=0.0)
+ap.add_argument("--top-p", type=float, default=1.0)
 ap.add_argument("--rows", type=int, default=64)
 ap.add_argument("--vocab", type=int, default=128256)
 ap.add_argument("--tag", default="")
@@ -31,9 +36,15 @@ lg = (torch.randn(B, V, generator=torch.Generator().manual_seed(0)) * 3).to(torc
 sd = torch.arange(B, dtype=torch.int64, device=dev)
 has_bias = "bias_tab" in inspect.signature(ops.sample).parameters
 kw = {}
-if a.proc != "none" or a.logit_bias:
+if a.top_p < 1.0:
+    kw["top_p"] = torch.full((B,), a.top_p, device=dev)
+if a.proc != "none" or a.logit_bias or a.min_p:
     proc = np.zeros((B, 8), dtype=np.int32)
     proc[:, 2] = -1
+    if a.min_p:
+        from kafka_llm_service_amd.engine.logits_proc import min_p_bits  # (a tree before min_p has none: an error)
+
+        proc[:, 7] = min_p_bits(a.min_p)
     kw["mask_tab"] = torch.zeros(1, -(-V // 32), dtype=torch.int32, device=dev)
     if a.proc == "penalty":
         proc[:, 2] = np.arange(B)
@@ -67,5 +78,5 @@ for name, temp in (("greedy", 0.0), ("T0.7", 0.7)):
         torch.cuda.synchronize()
         res.append(s.elapsed_time(e) * 1e3 / 200)
     print(json.dumps({"bench": "sample", "tag": a.tag, "rows": B, "vocab": V, "mode": name, "proc": a.proc,
-                      "logit_bias": a.logit_bias, "us_per_call": round(statistics.median(res), 2),
-                      "min": round(min(res), 2), "max": round(max(res), 2)}), flush=True)
+                      "logit_bias": a.logit_bias, "min_p": a.min_p, "top_p": a.top_p,
+                      "us_per_call": round(statistics.median(res), 2), "min": round(min(res), 2), "max": round(max(res), 2)}), flush=True)

@@ -11,8 +11,12 @@ Per step the host builds one int32 row per sampled sequence (``proc``, 8 ints):
     [2] penalty slot: row of ``counts`` holding the sequence's generated-token counts (-1: no penalty)
     [3] presence, [4] frequency penalty (fp32 bits)
     [5] row of ``bias_tab`` holding the request's ``logit_bias``, [6] its entry count (0: no bias)
+    [7] ``min_p``: the fp32 bits of ``float32(ln(min_p))`` (``min_p_bits``; 0: off, min_p = 1 travels as -0.0)
 The kernel computes ``(x - freq * c - (c > 0 ? pres : 0)) + b`` in fp32 and applies the grammar mask after it: a
 masked-out token stays -inf whatever its bias. The bias is stateless (nothing to undo on a rollback or a re-prefill).
+``min_p`` acts on the processed row under temperature: token i is kept iff ``x_i / T >= max(x / T) + ln(min_p)`` (one
+fp32 add of the host's logarithm, so the kernel, its replay and the CPU reference share one threshold bit for bit),
+intersected with top-k / top-p; greedy and forced rows ignore it.
 The proc rows ride in the step's single H2D upload (and in the TP plan); the two tables live on the device at fixed
 addresses (hipGraph-capturable), and so does the bias table:
   * ``mask_tab`` uint32 [MASK_ROWS, ceil(V / 32)]: one row per distinct allowed set (a constraint state's cached
@@ -28,6 +32,7 @@ every TP rank, from the same plan, so every rank samples the same token.
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 
 import numpy as np
@@ -54,6 +59,17 @@ def spec_forced(spec) -> int | None:
     return None
 
 
+def min_p_bits(min_p: float) -> int:
+    """``proc[7]`` of a row: the int32 bits of ``float32(ln(min_p))``; 0 for min_p = 0 (off). ln(1) = 0 is sent as
+    -0.0 (0x80000000), which keeps "on" apart from "off" and adds the same."""
+    if not 0.0 <= min_p <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError("min_p must lie in [0, 1]")
+    if min_p == 0.0:
+        return 0
+    lmp = np.float32(math.log(min_p))
+    return int((-np.float32(0.0) if lmp == 0 else lmp).view(np.int32))
+
+
 class LogitsProcessor:
     def __init__(self, device: torch.device, vocab: int, max_slots: int = 256, mask_rows: int = MASK_ROWS,
                  bias_rows: int = BIAS_ROWS):
@@ -73,7 +89,7 @@ class LogitsProcessor:
         self._free: list[int] = list(range(max_slots - 1, -1, -1))
         self._dec: list[tuple[int, int]] = []  # (slot, token) decrements queued by uncount()
         self.stats = {"mask_uploads": 0, "proc_steps": 0, "forced_rows": 0, "mask_rows_used": 0, "penalty_rows": 0,
-                      "bias_uploads": 0, "bias_rows_used": 0}
+                      "bias_uploads": 0, "bias_rows_used": 0, "min_p_rows": 0}
 
     # ---- tables (allocated together on first use: a captured graph sees every address) --------------------------
     def tables(self) -> tuple[torch.Tensor, torch.Tensor]:
@@ -208,6 +224,10 @@ class LogitsProcessor:
                 if pairs:
                     proc[i, 5], proc[i, 6] = self._bias_row(pairs, b_rows, b_words, b_used), len(pairs)
                     self.stats["bias_rows_used"] += 1
+            min_p = getattr(p, "min_p", 0.0)
+            if min_p:
+                proc[i, 7] = min_p_bits(float(min_p))
+                self.stats["min_p_rows"] += 1
         self.stats["proc_steps"] += 1
         upd = ProcUpdates()
         if upd_rows:

@@ -366,7 +366,7 @@ class ModelRunner:
         return self.sample_device(logits, self.sample_params(seqs))
 
     def sample_params(self, seqs: list[Sequence]) -> "SampleParams":
-        """Per-row sampling parameters of a step; rows with a token constraint, penalties or a logit bias get a
+        """Per-row sampling parameters of a step; rows with a token constraint, penalties, a logit bias or min_p get a
         logits-processing row (engine/logits_proc.py) that the sampler kernel applies on the device. A constrained row's spec is
         computed from its landed tokens, or past a pending one when the grammar can guess its successor state
         (engine/constrained.py: a wrong guess rolls the row back one token); a forced token is returned in
@@ -397,7 +397,9 @@ class ModelRunner:
                 if f is not None:
                     known = known or {}
                     known[i] = f
-            if allowed is not None or p.presence_penalty or p.frequency_penalty or p.logit_bias:
+            # (min_p acts under temperature only: a greedy row needs no processing row for it)
+            if allowed is not None or p.presence_penalty or p.frequency_penalty or p.logit_bias \
+                    or (p.min_p and p.temperature > 0):
                 rows.append((i, s, allowed))
         proc = upd = None
         if rows:

@@ -46,8 +46,15 @@ class SamplingParams:
     # logits inside the sampler kernel after the penalties and before temperature and the grammar mask; normalised
     # here to a tuple sorted by id without zero entries, or None (picklable: it crosses the worker pipes)
     logit_bias: tuple | None = None
+    # keep the tokens with p_i >= min_p * p_max (0: off), intersected with top-k / top-p; the sampler kernel tests
+    # x_i / T >= max + ln(min_p) per token (engine/logits_proc.py proc[7]). Greedy and forced rows ignore it.
+    min_p: float = 0.0
 
     def __post_init__(self):
+        if isinstance(self.min_p, bool) or not isinstance(self.min_p, (int, float)) \
+                or not 0.0 <= self.min_p <= 1.0:  # (a NaN fails both comparisons)
+            raise ValueError("min_p must be a number in [0, 1]")
+        self.min_p = float(self.min_p)
         if self.logit_bias is not None:
             items = self.logit_bias.items() if isinstance(self.logit_bias, dict) else self.logit_bias
             pairs = tuple(sorted((int(t), float(b)) for t, b in items if float(b) != 0.0))

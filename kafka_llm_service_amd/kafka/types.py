@@ -5,7 +5,8 @@ Same field names and validation bounds (temperature in [0, 2], max_tokens > 0, t
 final usage chunk like the OpenAI API; ``tool_choice`` / ``tools`` are accepted (the server's own tool set is used,
 ``tool_choice`` steers constrained decoding); ``logprobs`` / ``top_logprobs`` (0..20, only with ``logprobs: true``)
 return per-token log-probabilities of the model's raw logits; ``logit_bias`` maps token ids (JSON string keys) to
-biases in [-100, 100], at most 300 of them, added to the logits inside the sampler.
+biases in [-100, 100], at most 300 of them, added to the logits inside the sampler. Two fields go beyond the OpenAI
+schema: ``min_p`` in [0, 1] and ``top_k`` >= 0 (0 turns either off), the sampler's other two truncation rules.
 """
 from __future__ import annotations
 
@@ -49,6 +50,10 @@ class ChatCompletionRequest(BaseModel):
     top_logprobs: Optional[int] = Field(None, ge=0, le=20)
     # token id (a base-10 string key, as JSON has it) -> bias in [-100, 100] added to that token's logit
     logit_bias: Optional[dict[str, float]] = None
+    # extensions beyond the OpenAI schema, applied inside the sampler: ``min_p`` keeps the tokens whose probability is
+    # at least min_p times the most likely token's (0: off); ``top_k`` keeps the k most likely tokens (0: off)
+    min_p: Optional[float] = Field(None, ge=0, le=1)
+    top_k: Optional[int] = Field(None, ge=0)
 
     @field_validator("logit_bias")
     @classmethod

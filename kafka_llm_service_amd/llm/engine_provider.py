@@ -152,6 +152,7 @@ class EngineLLMProvider(LLMProvider):
                                 seed: int | None = None, routing_key: str | None = None,
                                 tool_choice: Any = None, logprobs: bool | None = None,
                                 top_logprobs: int | None = None, logit_bias: dict | None = None,
+                                min_p: float | None = None, top_k: int | None = None,
                                 **kwargs: Any) -> AsyncGenerator[StreamChunk, None]:
         """``logprobs`` / ``top_logprobs``: every non-special token the provider consumes yields one OpenAI entry
         ({token, logprob, bytes, top_logprobs}) over the model's RAW logits; a content chunk carries the entries of
@@ -161,7 +162,10 @@ class EngineLLMProvider(LLMProvider):
 
         ``logit_bias``: {token id: bias in [-100, 100]} added to those tokens' logits in the sampler kernel (after
         the penalties, before temperature and the grammar mask); logprobs stay those of the raw logits. An id outside
-        the model's vocabulary is refused before anything is submitted."""
+        the model's vocabulary is refused before anything is submitted.
+
+        ``min_p`` / ``top_k`` (extensions beyond the OpenAI schema; None or 0: off): the sampler's truncation rules
+        next to ``top_p`` — keep the tokens with p >= min_p * p_max, keep the k most likely — intersected."""
         self.validate_messages(messages)
         bias = None
         if logit_bias:
@@ -185,6 +189,7 @@ class EngineLLMProvider(LLMProvider):
         max_new = min(max_tokens or self.default_max_tokens, limit - len(prompt))
         params = SamplingParams(temperature=0.7 if temperature is None else float(temperature),
                                 top_p=1.0 if not top_p else float(top_p), max_tokens=max_new,
+                                min_p=float(min_p or 0.0), top_k=int(top_k or 0),
                                 frequency_penalty=float(frequency_penalty or 0.0),
                                 presence_penalty=float(presence_penalty or 0.0), seed=seed,
                                 ignore_eos=self.ignore_eos, logprobs=bool(logprobs),

@@ -62,6 +62,9 @@ class RemoteOpenAIProvider(LLMProvider):
                 body[k] = kw[k]
         if kw.get("logit_bias"):  # token id -> bias, unchanged (JSON keys are strings on the wire)
             body["logit_bias"] = {str(k): b for k, b in kw["logit_bias"].items()}
+        for k in ("min_p", "top_k"):  # extensions beyond the OpenAI schema: sent only when set (0 is "off")
+            if kw.get(k):
+                body[k] = kw[k]
         return body
 
     async def stream_completion(self, messages: list[Message], *, temperature: Optional[float] = None,

@@ -151,6 +151,8 @@ hipError_t kafka_launch_attn_tile(const void* items, int n_items, const bf16* q,
 // RowProc) selects the logits-processing instantiation; mask_tab uint32 [rows, mask_ld] and counts int32
 // [slots, cnt_ld] (cnt_ld >= V rounded up to 8) are only read for rows that name them; bias_tab (optional, int32
 // [rows, bias_ld], bias_ld >= 2 * LOGIT_BIAS_MAX and a multiple of 4) likewise — without it no row is biased.
+// proc[7] carries min_p as the fp32 bits of float32(ln(min_p)) (0: off, min_p = 1 is -0.0): a row under temperature
+// keeps the tokens with x / T >= max(x / T) + that value. The same workspace serves min_p rows (two ints per split).
 hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int64_t stride, int B, int V, const float* temperature,
                                const float* top_p, const int* top_k, const int64_t* seeds, const int64_t* step,
                                int64_t* out_tokens, int* ws, int nsplit, const int* proc, const uint32_t* mask_tab,

@@ -11,6 +11,8 @@
 //                             count neither toward k nor toward the mass, and tokens tied with the pivot are not
 //                             redrawn (top_k = 1 over a maximum that occurs twice returns either of the two).
 //                             ops/reference.py sample_replay replays these decisions with the same random stream.
+//   min_p (RowProc [7])    -> keep x_i >= max + ln(min_p): one more test on a top-k / top-p row's candidates; alone
+//                             it stays on the plain stream and split (sample_min_p_split), two passes per slice.
 // All reads are 16-byte vectors; every pass is one streaming read of the row (bf16 or fp32 logits).
 // Greedy and plain-temperature rows (no top-k / top-p) are split over `nsplit` workgroups (grid (B, nsplit)): each
 // takes a slice of the vocabulary, publishes its (value, index) winner, and the last of a row's workgroups to take
@@ -99,6 +101,9 @@ __device__ __forceinline__ float gumbel_fast(uint64_t key, uint32_t idx) {
 //   [2] penalty slot: row of counts[slot][V] (the row's generated-token counts, -1 = none)
 //   [3] presence penalty, [4] frequency penalty (fp32 bits)
 //   [5] logit-bias row of bias_tab, [6] its entry count (0 = no bias; clamped to LOGIT_BIAS_MAX)
+//   [7] min_p: the fp32 bits of lmp = float32(ln(min_p)), the host's logarithm (0 = off; min_p = 1 is -0.0). Under
+//       temperature token i is kept iff x_i / T >= max(x / T) + lmp — one fp32 add, so every token is tested on its own
+//       once the maximum is known — intersected with top-k / top-p; greedy and forced rows ignore it.
 // The logit of token i becomes  (x_i - freq * c_i - (c_i > 0 ? pres : 0)) + b_i  (OpenAI presence / frequency
 // penalties, then the request's logit_bias, before temperature), or -inf where the grammar mask has a zero bit; the
 // sampler then runs unchanged over it, and the thread that writes the row's token also bumps counts[slot][token] —
@@ -115,14 +120,18 @@ struct RowProc {
   int* cnt;
   int nb;           // staged logit-bias pairs (bias_lds)
   const int* bias;  // the row of bias_tab they come from
+  bool minp;        // proc[7] != 0
+  float lmp;        // ln(min_p) <= 0 (0 when off)
 };
 
 template <bool PROC>
 __device__ __forceinline__ RowProc row_proc(const int* proc, const uint32_t* mask_tab, int64_t mask_ld, int* counts,
                                             int64_t cnt_ld, const int* bias_tab, int64_t bias_ld, int row) {
-  RowProc r{0, -1, -1, 0.f, 0.f, nullptr, nullptr, 0, nullptr};
+  RowProc r{0, -1, -1, 0.f, 0.f, nullptr, nullptr, 0, nullptr, false, 0.f};
   if constexpr (PROC) {
     const int* p = proc + (int64_t)row * 8;
+    r.minp = p[7] != 0;
+    r.lmp = fminf(__int_as_float(p[7]), 0.f);  // (a positive or NaN word from a broken host keeps the maximum itself)
     r.mode = p[0];
     r.arg = p[1];
     r.slot = p[2];
@@ -216,6 +225,102 @@ __device__ __forceinline__ void emit_token(int64_t* out_tokens, int row, int tok
   }
 }
 
+// min_p alone (T > 0, no effective top-k / top-p; PROC rows only): the kept set {xv >= max + lmp} needs the row maximum
+// and nothing else, so the row stays on the plain stream (gumbel_fast, the plain rows' key: the token does not depend
+// on nsplit) and stays split. A split reads its slice twice: the slice maximum m_s, then the argmax of xv + noise over
+// {xv >= m_s + lmp} (the second read comes from L2). It publishes (m_s, winner index) in the two-int partial. The last
+// workgroup forms thr = max m_s + lmp. fp32 add is monotonic, so m_s + lmp <= thr: a slice's own candidate set held the
+// row's, and a winner that passes thr is exactly the slice's argmax over the row's set (its score is a pure function of
+// (key, index, logit), recomputed here). A slice below thr gives nothing; a slice at or above thr whose winner fell
+// below it is rescanned with thr by the whole workgroup (one slice of V / nsplit; rare on a peaked row, common on flat
+// random logits, where most of a slice's mass lies between the two thresholds).
+template <typename T>
+__device__ __forceinline__ void sample_min_p_split(const T* x, int V, const RowProc& rp, float inv_t, uint64_t key,
+                                                   int row, int sp, int nsplit, int* ws, int64_t* out_tokens,
+                                                   float* sv, int* si, float* red) {
+  __shared__ float pm[64];  // per slice (nsplit <= 64): maximum, winner, "rescan"
+  __shared__ int pw[64];
+  __shared__ int pflag[64];
+  __shared__ int s_last;
+  const int nvec = V >> 3, tail0 = nvec << 3;
+  const int per = (nvec + nsplit - 1) / nsplit;
+  // best of xv + noise over slice k's tokens with xv >= thr (the last slice owns the scalar tail)
+  auto scan = [&](int k, float thr, ArgMax a) -> ArgMax {
+    const int v0 = k * per, v1 = min(nvec, v0 + per);
+    for (int vi = v0 + threadIdx.x; vi < v1; vi += SNT) {
+      float v[8];
+      load8p<T, true>(x, vi * 8, rp, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float xv = v[j] * inv_t;
+        if (xv >= thr) a = better(a, ArgMax{xv + gumbel_fast(key, vi * 8 + j), vi * 8 + j});
+      }
+    }
+    if (k == nsplit - 1)
+      for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
+        const float xv = load1p<T, true>(x, i, rp) * inv_t;
+        if (xv >= thr) a = better(a, ArgMax{xv + gumbel_fast(key, i), i});
+      }
+    return a;
+  };
+  float m = -INFINITY;
+  {
+    const int v0 = sp * per, v1 = min(nvec, v0 + per);
+    for (int vi = v0 + threadIdx.x; vi < v1; vi += SNT) {
+      float v[8];
+      load8p<T, true>(x, vi * 8, rp, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) m = fmaxf(m, v[j] * inv_t);
+    }
+    if (sp == nsplit - 1)
+      for (int i = tail0 + threadIdx.x; i < V; i += SNT) m = fmaxf(m, load1p<T, true>(x, i, rp) * inv_t);
+  }
+  m = block_max<SNT>(m, red);
+  ArgMax a = block_argmax(scan(sp, m + rp.lmp, ArgMax{-INFINITY, 0x7fffffff}), sv, si);
+  if (nsplit == 1) {  // one slice: its threshold is the row's
+    if (threadIdx.x == 0) emit_token<true>(out_tokens, row, a.i, V, rp);
+    return;
+  }
+  if (threadIdx.x == 0) {  // the ticket protocol of the plain rows (sample_kernel), its order unchanged
+    int* tk_row = ws + row;
+    int* part = ws + SAMPLE_MAX_ROWS + ((int64_t)row * nsplit + sp) * 2;
+    __hip_atomic_store(part, __float_as_int(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(part + 1, a.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int t = __hip_atomic_fetch_add(tk_row, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = t == nsplit - 1;
+    if (last) {
+      __hip_atomic_store(tk_row, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int* p0 = ws + SAMPLE_MAX_ROWS + (int64_t)row * nsplit * 2;
+      for (int k = 0; k < nsplit; ++k) {
+        pm[k] = __int_as_float(__hip_atomic_load(p0 + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        pw[k] = __hip_atomic_load(p0 + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    s_last = last;
+  }
+  __syncthreads();
+  if (!s_last) return;  // (uniform) the whole last workgroup stays: a rescan is a job for all of it
+  float M = -INFINITY;
+  for (int k = 0; k < nsplit; ++k) M = fmaxf(M, pm[k]);
+  const float thr = M + rp.lmp;
+  ArgMax r{-INFINITY, 0x7fffffff};
+  if ((int)threadIdx.x < nsplit) {  // thread k judges slice k
+    const int w = pw[threadIdx.x];
+    int flag = 0;
+    if (pm[threadIdx.x] >= thr && w >= 0 && w < V) {
+      const float xv = load1p<T, true>(x, w, rp) * inv_t;
+      if (xv >= thr) r = ArgMax{xv + gumbel_fast(key, w), w}; else flag = 1;
+    }
+    pflag[threadIdx.x] = flag;
+  }
+  __syncthreads();
+  for (int k = 0; k < nsplit; ++k)
+    if (pflag[k]) r = scan(k, thr, r);
+  r = block_argmax(r, sv, si);
+  if (threadIdx.x == 0) emit_token<true>(out_tokens, row, r.i, V, rp);
+}
+
 template <typename T, bool PROC>
 __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logits, int64_t stride, int V,
                                                       const float* __restrict__ temperature,
@@ -260,6 +365,12 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
     const uint64_t seed = seeds ? (uint64_t)seeds[row] : 0x1234ull;
     const uint64_t stream = (uint64_t)(step_ptr ? step_ptr[0] : 0) << 8;  // round 0 of the filtered path
     const uint64_t key = mix64(seed ^ mix64(stream * 0x632BE59BD9B4E019ull));
+    if constexpr (PROC) {
+      if (rp.minp && !greedy) {  // the row's proc[7]: uniform over its workgroups; every other row runs what it ran
+        sample_min_p_split<T>(x, V, rp, inv_t, key, row, sp, nsplit, ws, out_tokens, sv, si, red);
+        return;
+      }
+    }
     const int per = (nvec + nsplit - 1) / nsplit;
     const int v0 = sp * per, v1 = min(nvec, v0 + per);
     ArgMax a{-INFINITY, 0x7fffffff};
@@ -328,6 +439,9 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
   }
   for (int i = tail0 + threadIdx.x; i < V; i += SNT) z += __expf(load1p<T, PROC>(x, i, rp) * inv_t - mx);
   z = block_sum<SNT>(z, red);
+  // min_p: a candidate also passes the row's threshold (z and the mass stay the whole row's: the ratio to the maximum
+  // does not change under renormalisation). The maximum passes its own threshold, so round 0 has a candidate.
+  const float thr = PROC && rp.minp ? mx + rp.lmp : -INFINITY;
 
   float pivot = -INFINITY;
   int result = -1;
@@ -340,12 +454,13 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float xv = v[j] * inv_t;
-        if (xv > pivot) a = better(a, ArgMax{xv + gumbel(seed, stream, vi * 8 + j), vi * 8 + j});
+        if (PROC ? (xv > pivot && xv >= thr) : xv > pivot)
+          a = better(a, ArgMax{xv + gumbel(seed, stream, vi * 8 + j), vi * 8 + j});
       }
     }
     for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
       const float xv = load1p<T, PROC>(x, i, rp) * inv_t;
-      if (xv > pivot) a = better(a, ArgMax{xv + gumbel(seed, stream, i), i});
+      if (PROC ? (xv > pivot && xv >= thr) : xv > pivot) a = better(a, ArgMax{xv + gumbel(seed, stream, i), i});
     }
     a = block_argmax(a, sv, si);
     if (a.i == 0x7fffffff) break;

@@ -486,8 +486,9 @@ def process_logits(logits, proc, mask_tab, counts, bias_tab=None):
 def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
            mask_tab=None, counts=None, bias_tab=None):
     """CPU sampler with the same semantics (not the same random stream) as the HIP kernel: the sort-based definition
-    of top-k / top-p and the CPU engine path. ``sample_replay`` below reproduces the kernel's own stream and
-    decisions draw by draw."""
+    of top-k / top-p and the CPU engine path. ``proc[:, 7]`` (the fp32 bits of ln(min_p), 0 = off) adds the min_p
+    set ``x / T >= max(x / T) + ln(min_p)`` with the kernel's fp32 threshold, intersected with the other two; greedy
+    and forced rows ignore it. ``sample_replay`` below reproduces the kernel's own stream and decisions draw by draw."""
     B, V = logits.shape
     forced = None
     if proc is not None:
@@ -515,6 +516,10 @@ def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=No
         if tp < 1.0:
             above = torch.cumsum(ps, 0) - ps
             keep &= above < tp
+        if proc is not None and int(proc[b, 7]) != 0:  # min_p: xv >= max + ln(min_p), the kernel's fp32 threshold
+            lmp = proc[b, 7:8].cpu().clone().view(torch.float32)[0]
+            xv = x[b] * (torch.tensor(1.0) / torch.tensor(t, dtype=torch.float32)).to(x.device)
+            keep &= (xv >= xv.max() + lmp.to(x.device))[order]
         ps = torch.where(keep, ps, torch.zeros_like(ps))
         gen = torch.Generator(device="cpu")
         seed = int(seeds[b]) if seeds is not None else 0x1234
@@ -558,6 +563,7 @@ class SampleReplay(NamedTuple):
     rounds: torch.Tensor     # int64 [B]: draws of the rejection loop (0 for greedy / plain / forced rows)
     fell_back: torch.Tensor  # bool [B]: the loop ended without an accepted draw (token = argmax)
     plain: torch.Tensor      # bool [B]: drawn from the plain-temperature stream (gumbel_fast), not the filtered one
+    rescans: torch.Tensor    # int64 [B]: slices of a min_p-only row whose own winner fell below the row's threshold
 
 
 def _mix64(z: np.ndarray) -> np.ndarray:
@@ -593,41 +599,87 @@ def _first_max(s: np.ndarray):
     return m, np.where(hit.any(1), hit.argmax(1), _NO_IDX).astype(np.int64)
 
 
-def _replay_plain(xv, greedy, seeds, steps, nsplit):
+def _min_p_threshold(xv, lmp):
+    """Per row the fp32 threshold max(xv) + lmp (one fp32 add; fmaxf drops a NaN) — -inf where lmp is NaN (no min_p)."""
+    mx = np.where(np.isnan(xv), np.float32(-np.inf), xv).max(1) if xv.shape[1] else np.full(xv.shape[0], -np.inf)
+    thr = mx.astype(np.float32) + np.where(np.isnan(lmp), np.float32(0), lmp).astype(np.float32)
+    return np.where(np.isnan(lmp), np.float32(-np.inf), thr).astype(np.float32)
+
+
+def _replay_plain(xv, greedy, seeds, steps, nsplit, lmp=None):
     """Greedy / plain-temperature rows: argmax of x (greedy) or x / T + gumbel_fast over ``nsplit`` slices of the row
-    and the reduction of the slices' winners, as the split workgroups do. -> (token, ambiguous)."""
+    and the reduction of the slices' winners, as the split workgroups do. ``lmp`` (fp32 [R], NaN = none): ln(min_p) of
+    a min_p row — its slices draw over {xv >= slice max + lmp}, and the last workgroup keeps a slice's winner if it
+    passes the row's threshold, drops a slice whose maximum does not, and rescans a slice whose winner fell below it
+    (sample_min_p_split); the same draw over the row's kept set must give the same token.
+    -> (token, ambiguous, rescans)."""
     R, V = xv.shape
     key = _mix64(seeds ^ _mix64((steps << np.uint64(8)) * _STREAM_MUL))
     idx = np.arange(V, dtype=np.uint32)[None, :]
     h = _lowbias32(_lowbias32(idx + key.astype(np.uint32)[:, None]) ^ (key >> np.uint64(32)).astype(np.uint32)[:, None])
     s = xv.astype(np.float64)
     s = np.where(greedy[:, None], s, s + _gumbel(h >> np.uint32(8)))
+    on = np.zeros(R, dtype=bool) if lmp is None else (~np.isnan(lmp) & ~greedy)
+    lmp = np.where(on, lmp, np.float32(np.nan)).astype(np.float32) if on.any() else None
     nvec = V >> 3
     per = -(-nvec // nsplit)
     vals = np.full((R, nsplit), -np.inf)
     ids = np.full((R, nsplit), _NO_IDX, dtype=np.int64)
+    ms = np.full((R, nsplit), -np.inf, dtype=np.float32)  # min_p rows: the slices' maxima
+    slices = []
     for sp in range(nsplit):
         v0 = sp * per
         v1 = min(nvec, v0 + per)
         cols = np.r_[v0 * 8:max(v0, v1) * 8, (nvec * 8 if sp == nsplit - 1 else V):V]  # the last split owns the tail
-        vals[:, sp], i = _first_max(s[:, cols])
+        slices.append(cols)
+        sc = s[:, cols]
+        if lmp is not None and cols.size:
+            xs = xv[:, cols]
+            ms[:, sp] = np.where(np.isnan(xs), np.float32(-np.inf), xs).max(1)  # (fmaxf drops a NaN)
+            thr_s = ms[:, sp] + lmp  # one fp32 add (NaN in the other rows, which keep every score)
+            sc = np.where(on[:, None] & ~(xs >= thr_s[:, None]), np.nan, sc)
+        vals[:, sp], i = _first_max(sc)
         if cols.size:
             ids[:, sp] = np.where(i != _NO_IDX, cols[np.minimum(i, cols.size - 1)], _NO_IDX)
-    m = vals.max(1)
-    tok = np.where(vals == m[:, None], ids, _NO_IDX).min(1)
+    r = np.arange(R)
+    rescans = np.zeros(R, dtype=np.int64)
+    kept = s
+    if lmp is not None:  # the last workgroup of a min_p row
+        thr = ms.max(1) + lmp  # fp32
+        for sp, cols in enumerate(slices):
+            w = ids[:, sp]
+            has = on & (ms[:, sp] >= thr) & (w != _NO_IDX)
+            redo = has & ~(xv[r, np.minimum(w, V - 1)] >= thr)
+            none = on & ~has
+            vals[none, sp], ids[none, sp] = np.nan, _NO_IDX
+            if redo.any():
+                rescans[redo] += 1
+                q = np.nonzero(redo)[0]
+                sub = xv[np.ix_(q, cols)]
+                vals[q, sp], i = _first_max(np.where(sub >= thr[q, None], s[np.ix_(q, cols)], np.nan))
+                ids[q, sp] = np.where(i != _NO_IDX, cols[np.minimum(i, cols.size - 1)], _NO_IDX)
+        kept = np.where(on[:, None] & ~(xv >= thr[:, None]), np.nan, s)
+    dead = np.isnan(vals)  # (a min_p slice that contributes nothing; a plain slice's value is never NaN)
+    vm = np.where(dead, -np.inf, vals)
+    m = vm.max(1)
+    tok = np.where((vm == m[:, None]) & ~dead, ids, _NO_IDX).min(1)
+    if lmp is not None:  # the split draw is the draw over the row's kept set
+        whole = _first_max(kept)[1]
+        assert (tok[on] == whole[on]).all(), "min_p replay: the sliced draw and the draw over the kept set differ"
     tok = np.where((tok >= 0) & (tok < V), tok, 0)  # emit_token: an index outside the vocabulary becomes 0
     # greedy compares the fp32 values themselves (exact, lowest index among equals): never ambiguous
-    r = np.arange(R)
-    rest = s.copy()
+    rest = kept.copy()
     rest[r, tok] = -np.inf
-    amb = ~greedy & (s[r, tok] - _first_max(rest)[0] < SAMPLE_SCORE_BAND)
-    return tok, amb
+    amb = ~greedy & (kept[r, tok] - _first_max(rest)[0] < SAMPLE_SCORE_BAND)
+    return tok, amb, rescans
 
 
-def _replay_filtered(x, xv, tp, tk, seeds, steps):
+def _replay_filtered(x, xv, tp, tk, seeds, steps, lmp=None):
     """top-k / top-p rows: the rejection loop round by round. x: the processed fp32 logits (the fallback's argmax),
-    xv = x / T in fp32. -> (token, ambiguous, rounds, fell_back)."""
+    xv = x / T in fp32; ``lmp`` (fp32 [R], NaN = none): a candidate also passes xv >= max + ln(min_p), compared in
+    fp32 as the kernel compares it (no band). -> (token, ambiguous, rounds, fell_back)."""
     R, V = xv.shape
+    thr = _min_p_threshold(xv, np.full(R, np.nan, dtype=np.float32) if lmp is None else lmp)
     xd = xv.astype(np.float64)
     e = np.exp(xd - _first_max(xd)[0][:, None])
     z = e.sum(1)
@@ -638,7 +690,8 @@ def _replay_filtered(x, xv, tp, tk, seeds, steps):
     base = steps << np.uint64(8)
     live = np.arange(R)
     for rnd in range(SAMPLE_MAX_ROUNDS):
-        cand = xv[live] > pivot[live, None]  # strict: tokens tied with the pivot are out
+        # strict: tokens tied with the pivot are out (thr is -inf without min_p, and a NaN fails the first test already)
+        cand = (xv[live] > pivot[live, None]) & (xv[live] >= thr[live, None])
         n = cand.sum(1)
         live, cand, n = live[n > 0], cand[n > 0], n[n > 0]  # nothing above the pivot ends the loop (fallback)
         if live.size == 0:
@@ -674,7 +727,9 @@ def sample_replay(logits, temperature=None, top_p=None, top_k=None, seeds=None, 
     ``nsplit`` (the workgroups a greedy / plain-temperature row is split over; it must not change the result). Every
     row whose ``ambiguous`` flag is clear has exactly one right token and the kernel must return it. Logits are finite
     or -inf. ``step`` holds one value as for the kernel, or (replay only) one per row. ``counts`` is bumped with every
-    token like the kernel bumps it."""
+    token like the kernel bumps it. min_p (``proc[:, 7]``) is a threshold max + ln(min_p) formed and compared in fp32
+    exactly as the kernel does, so it adds no ambiguity band; ``rescans`` counts, per min_p-only row, the slices the
+    kernel's last workgroup reads again."""
     B, V = logits.shape
     assert 1 <= nsplit <= 64
     forced = None
@@ -699,6 +754,12 @@ def sample_replay(logits, temperature=None, top_p=None, top_k=None, seeds=None, 
     amb = np.zeros(B, dtype=bool)
     rounds = np.zeros(B, dtype=np.int64)
     fell = np.zeros(B, dtype=bool)
+    rescans = np.zeros(B, dtype=np.int64)
+    lmp = None  # proc[7]: the fp32 bits of ln(min_p), 0 = none (NaN here)
+    if proc is not None:
+        bits = np.ascontiguousarray(proc[:B, 7].detach().cpu().numpy().astype(np.int32))
+        if bits.any():
+            lmp = np.where(bits != 0, bits.view(np.float32), np.float32(np.nan)).astype(np.float32)
     with np.errstate(all="ignore"):
         greedy = ~(temp > 0)
         inv_t = np.where(greedy, np.float32(1.0), np.float32(1.0) / temp).astype(np.float32)
@@ -712,11 +773,13 @@ def sample_replay(logits, temperature=None, top_p=None, top_k=None, seeds=None, 
             for i in range(0, sel.size, chunk):
                 rows = sel[i:i + chunk]
                 xv = x[rows] * inv_t[rows, None]  # fp32 product, as the kernel forms it
+                lm = None if lmp is None else lmp[rows]
                 if filt:
                     tokens[rows], amb[rows], rounds[rows], fell[rows] = _replay_filtered(x[rows], xv, tp[rows], tk[rows],
-                                                                                        sd[rows], st[rows])
+                                                                                        sd[rows], st[rows], lm)
                 else:
-                    tokens[rows], amb[rows] = _replay_plain(xv, greedy[rows], sd[rows], st[rows], nsplit)
+                    tokens[rows], amb[rows], rescans[rows] = _replay_plain(xv, greedy[rows], sd[rows], st[rows], nsplit,
+                                                                           lm)
     res = torch.from_numpy(tokens)
     if proc is not None and counts is not None:
         for b in range(B):
@@ -726,7 +789,7 @@ def sample_replay(logits, temperature=None, top_p=None, top_k=None, seeds=None, 
     if out is not None:
         out[:B].copy_(res)
     return SampleReplay(res, torch.from_numpy(amb), torch.from_numpy(rounds), torch.from_numpy(fell),
-                        torch.from_numpy(plain & ~greedy))
+                        torch.from_numpy(plain & ~greedy), torch.from_numpy(rescans))
 
 
 def token_logprobs(logits, tokens, rows=None, k: int = 0):

@@ -114,6 +114,10 @@ def _sampling_kwargs(req: ChatCompletionRequest) -> dict[str, Any]:
         bias = {int(k): float(b) for k, b in req.logit_bias.items() if b != 0}
         if bias:
             kw["logit_bias"] = bias
+    if req.min_p:  # (the two extensions beyond the OpenAI schema: absent or 0 is "off", and nothing new goes down)
+        kw["min_p"] = float(req.min_p)
+    if req.top_k:
+        kw["top_k"] = int(req.top_k)
     return kw
 
 
