@@ -68,8 +68,8 @@ class EngineConfig:
     # dense projections, lm_head and MoE experts: "bf16", or "fp8" = e4m3 wave tiles with one power-of-two scale per
     # output row (half the bytes of every decode GEMM and of the tiled copy; the row-major weights become the dequantised
     # values, so every path and the oracle run the same quantised model; models/llama.py enable_stream_weights).
-    # "mxfp4" = OCP MXFP4 wave tiles of the dense projections and the lm_head (e2m1 in 32-column blocks along K, one
-    # e8m0 exponent per block: 4.25 bits per weight; same semantics; MoE experts keep bf16 tiles).
+    # "mxfp4" = OCP MXFP4 wave tiles of the same weights, MoE experts included (e2m1 in 32-column blocks along K, one
+    # e8m0 exponent per block: 4.25 bits per weight; same semantics).
     # fp8 and mxfp4 need the streaming decode GEMM (auto resolves to stream); env KAFKA_WEIGHT_DTYPE overrides
     weight_dtype: str = "bf16"          # bf16 | fp8 | mxfp4
     async_scheduling: bool = True       # plan step n+1 on the host while step n runs on the GPU

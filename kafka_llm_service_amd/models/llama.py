@@ -146,7 +146,7 @@ class TransformerLM:
         """Bytes enable_stream_weights would add (the wave-tiled copies; 0 in tiled-only mode). ``"fp8"``: one byte
         per element plus a 4-byte scale per row for the dense projections, the lm_head and the MoE experts (a scale
         per row of every expert). ``"mxfp4"``: half a byte per element plus one exponent byte per 32 (4.25 bits) for the
-        dense projections and the lm_head; the MoE experts keep bf16 tiles."""
+        dense projections, the lm_head and the MoE experts alike."""
         expert_dtype = self._expert_dtype(weight_dtype)  # (refuses an unknown weight_dtype)
 
         n = 0
@@ -165,7 +165,8 @@ class TransformerLM:
 
     @staticmethod
     def _expert_dtype(weight_dtype: str) -> str:
-        """The tile format of the MoE experts under ``weight_dtype``: bf16 where the grouped kernel does not take it."""
+        """The tile format of the MoE experts under ``weight_dtype``: bf16 where the grouped kernel does not take it
+        (bf16, fp8 and mxfp4 all have their grouped kernel)."""
         return weight_dtype if ops.weight_format(weight_dtype).experts else "bf16"
 
     def enable_stream_weights(self, tiled_only: bool = False, weight_dtype: str = "bf16") -> int:
@@ -191,14 +192,17 @@ class TransformerLM:
         experts that ``ops.grouped_gemm`` runs on prefill-sized steps. Embedding, norms and router stay bf16; the
         skinny GEMM and the fused decode layer do not take fp8 tiles (hipBLASLt / the unfused layer run).
 
-        ``weight_dtype="mxfp4"``: the tiles of the dense projections and the lm_head are OCP MXFP4 — e2m1 elements in
-        32-column blocks along K with one e8m0 exponent per block (ops.tile_weight_mxfp4: ``<name>_t``
+        ``weight_dtype="mxfp4"``: the tiles of the dense projections, the lm_head and the MoE experts are OCP MXFP4 —
+        e2m1 elements in 32-column blocks along K with one e8m0 exponent per block (ops.tile_weight_mxfp4: ``<name>_t``
         float4_e2m1fn_x2, ``<name>_s`` the float8_e8m0fnu block-scale image), 4.25 bits per weight. Semantics and
         exclusions are fp8's: the row-major tensors become the dequantised values (e2m1 * 2^e, exact in bf16), so every
         step size, export and the oracle see one quantised model; no skinny GEMM, fused decode layer or overlapped TP
         seam. Blocks run along K and every rank quantises its own shard, so a row-parallel shard cut on a multiple of
-        64 columns has exactly the matching slice of the unsharded model's tiles. The MoE experts keep bf16 tiles in
-        this mode (attention projections and the lm_head are quantised)."""
+        64 columns has exactly the matching slice of the unsharded model's tiles. The experts are quantised where
+        their tiled copy is made, as for fp8 (ops.tile_experts_mxfp4: ``w13_t`` / ``w2_t`` float4_e2m1fn_x2
+        [E_local, N/32, K/64, 64, 16], ``w13_s`` / ``w2_s`` the e8m0 images [E_local, N/32, K/64, 32, 2]; every
+        expert-parallel rank quantises its own whole experts; row-major ``w13`` / ``w2`` become the dequantised experts),
+        and in tiled-only mode their single row-major copy stays unquantised bf16 as well."""
         expert_dtype = self._expert_dtype(weight_dtype)  # (refuses an unknown weight_dtype)
         added = 0
 

@@ -13,8 +13,9 @@ expert sort, no host sync) -> ``ops.grouped_gemm`` gate_up (HIP MFMA, A rows gat
 
 Decode-sized steps (T <= MOE_STREAM_MAX_T) of a model with streamed weights instead run ``ops.grouped_stream_glu`` /
 ``ops.grouped_stream_combine`` on the wave-tiled expert copies ``w13_t`` / ``w2_t``. With ``weight_dtype="fp8"`` those
-are e4m3 tiles with per-row scales ``w13_s`` / ``w2_s`` (half the streamed bytes) and the row-major ``w13`` / ``w2``
-hold the dequantised values, so larger steps (``ops.grouped_gemm``) compute with the same quantised experts.
+are e4m3 tiles with per-row scales ``w13_s`` / ``w2_s`` (half the streamed bytes), with ``weight_dtype="mxfp4"`` e2m1
+tiles with their e8m0 block-scale images in the same slots (4.25 / 16 of the bytes); either way the row-major ``w13`` /
+``w2`` hold the dequantised values, so larger steps (``ops.grouped_gemm``) compute with the same quantised experts.
 """
 from __future__ import annotations
 
@@ -67,7 +68,7 @@ class MoEBlock:
         if self.model.stream and lw.w13_t is not None and T <= MOE_STREAM_MAX_T:
             # decode-sized steps: expert weights streamed from their wave-tiled copies, SwiGLU fused into the gate_up
             # epilogue, weighted combine fused into the down epilogue (csrc/wstream_gemm.hip, grouped variant)
-            # (fp8 weights: e4m3 expert tiles with their row scales w13_s / w2_s, None for bf16 tiles)
+            # (w13_s / w2_s: the row scales of fp8 expert tiles or the block-scale images of mxfp4 ones, None for bf16)
             a = ops.grouped_stream_glu(x, lw.w13_t, r, e_lo=self.e0, scale=lw.w13_s)
             out = torch.zeros(T, d, dtype=torch.float32, device=x.device)
             ops.grouped_stream_combine(a, lw.w2_t, r, T, out, e_lo=self.e0, scale=lw.w2_s)

@@ -356,7 +356,7 @@ WEIGHT_FORMATS = {
                               lambda s: (*s[:-4], s[-4] * 32), "row scales", False, True),
     _F4: WeightFormat("mxfp4", 2, 64, lambda w, glu=False: tile_weight_mxfp4(w, glu),
                       lambda wt, scale, glu=False: untile_weight_mxfp4(wt, scale, glu), torch.float8_e8m0fnu,
-                      lambda s: (*s[:-2], 32, 2), "block-scale image", True, False),
+                      lambda s: (*s[:-2], 32, 2), "block-scale image", True, True),
 }
 WEIGHT_DTYPES = {f.name: f for f in WEIGHT_FORMATS.values()}
 
@@ -703,8 +703,23 @@ tile_experts_fp8 = ref.tile_experts_fp8
 untile_experts_fp8 = ref.untile_experts_fp8
 
 
+# MXFP4 expert weights: float4_e2m1fn_x2 [E, N/32, K/64, 64, 16] tiles plus the float8_e8m0fnu block-scale images
+# [E, N/32, K/64, 32, 2] — the dense MXFP4 images per expert; grouped_stream_glu / grouped_stream_combine take them with
+# ``scale``.
+
+def tile_experts_mxfp4(w: torch.Tensor, glu: bool = False):
+    """Expert weights [E, N, K] -> (float4_e2m1fn_x2 tiles [E, N/32, K/64, 64, 16], float8_e8m0fnu block-scale images
+    [E, N/32, K/64, 32, 2]): ``tile_weight_mxfp4`` per expert (every expert quantised on its own, blocks along K)."""
+    return tile_experts_as(w, "mxfp4", glu)
+
+
+def untile_experts_mxfp4(wt4: torch.Tensor, se: torch.Tensor, glu: bool = False) -> torch.Tensor:
+    """The dequantised row-major bf16 [E, N, K] experts of MXFP4 expert tiles (e2m1 * 2^e, exact in bf16)."""
+    return untile_experts_as(wt4, se, glu)
+
+
 def stream_moe_supported(N: int, K: int) -> bool:
-    # (bf16 and fp8 tiles alike: the kernel's 256- and 128-deep K chunks are 8 and 4 fp8 vectors, both even)
+    # (every tile format: the kernel's 256- and 128-deep K chunks are 8 and 4 fp8 vectors or 4 and 2 mxfp4 ones)
     return N % 64 == 0 and K % 256 == 0
 
 
@@ -746,14 +761,17 @@ def _expert_format(fn: str, wt: torch.Tensor, scale: torch.Tensor | None):
 def grouped_stream_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: int = 0,
                        scale: torch.Tensor | None = None) -> torch.Tensor:
     """silu(gate) * up for every routed (token, local expert) entry, rows in expert-sorted order [n_ent, F]: the
-    weight-streaming grouped kernel on GLU-tiled expert weights (``tile_experts(w13, glu=True)``, or the uint8 tiles
-    of ``tile_experts_fp8`` with their row scales ``scale``)."""
+    weight-streaming grouped kernel on GLU-tiled expert weights (``tile_experts(w13, glu=True)``, the uint8 tiles
+    of ``tile_experts_fp8`` with their row scales ``scale``, or the float4_e2m1fn_x2 tiles of ``tile_experts_mxfp4``
+    with their e8m0 block-scale images ``scale``)."""
     f, scale = _expert_format("grouped_stream_glu", wt, scale)
     T = x.shape[0]
     n_ent = r.perm_tok.numel()
     F = wt.shape[1] * 16  # (N / 32 tiles of 32 rows, N = 2 F: every tile format)
     y = torch.empty(n_ent, F, dtype=x.dtype, device=x.device)
     if _gpu(x):
+        if f.raw:
+            wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
         ext().wstream_grouped(x, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), True, y,
                               None, GROUPED_PIN)
         return y
@@ -765,9 +783,11 @@ def grouped_stream_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo:
 def grouped_stream_combine(a: torch.Tensor, wt: torch.Tensor, r: "MoERouting", T: int, out: torch.Tensor,
                            e_lo: int = 0, scale: torch.Tensor | None = None) -> torch.Tensor:
     """out[token] += w * (a[entry] @ W_e^T) over the local experts' entries (out f32 [T, N], zeroed by the caller).
-    ``scale``: the row scales of fp8 expert tiles."""
+    ``scale``: the row scales of fp8 expert tiles / the block-scale images of MXFP4 ones."""
     f, scale = _expert_format("grouped_stream_combine", wt, scale)
     if _gpu(a):
+        if f.raw:
+            wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
         ext().wstream_grouped(a, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), int(T), False, None,
                               out, GROUPED_PIN)
         return out

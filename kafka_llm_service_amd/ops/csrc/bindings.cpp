@@ -447,7 +447,7 @@ static void check_stream_x(const char* fn, const at::Tensor& x) {
 
 // Weight tiles and their scales against the format fmt (kafka_abi.h WF_*; fp8 and mxfp4 tiles are both uint8
 // [., ., 64, 16], so the caller names it). lead = 0: wt [N/32, K/vk, 64, 8 or 16]; lead = 1: expert tiles with a leading
-// [E_local]. bf16: no scale; fp8: f32 [N] / [E_local, N]; mxfp4: uint8 [N/32, K/64, 32, 2]. Returns vk, the K columns
+// [E_local]. bf16: no scale; fp8: f32 [N] / [E_local, N]; mxfp4: uint8 [(E_local,) N/32, K/64, 32, 2]. Returns vk, the K columns
 // of one 16-B tile vector (16, 32 or 64).
 static int check_wfmt(const char* fn, int64_t fmt, const at::Tensor& wt, const c10::optional<at::Tensor>& scale,
                       int lead) {
@@ -473,7 +473,7 @@ static int check_wfmt(const char* fn, int64_t fmt, const at::Tensor& wt, const c
   CHECK_DT(sc, at::kByte);
   TORCH_CHECK(sc.dim() == 4 + lead && sc.size(lead) == wt.size(lead) && sc.size(lead + 1) == wt.size(lead + 1) &&
                   sc.size(lead + 2) == 32 && sc.size(lead + 3) == 2 && (!lead || sc.size(0) == wt.size(0)),
-              fn, ": the scale of mxfp4 tiles must be uint8 [N/32, K/64, 32, 2]");
+              fn, ": the scale of mxfp4 tiles must be uint8 [N/32, K/64, 32, 2]", lead ? " per local expert" : "");
   return 64;
 }
 
@@ -696,19 +696,22 @@ static void wstream_gemm_cfg(at::Tensor x, at::Tensor wt, c10::optional<at::Tens
 }
 
 // Expert MLP halves on wave-tiled expert weights in format fmt: wt [E_local, N/32, K/16, 64, 8] bf16 (ops.tile_experts)
-// or uint8 [E_local, N/32, K/32, 64, 16] fp8 tiles with their row scales f32 [E_local, N] (ops.tile_experts_fp8). glu:
-// gate_up with fused SwiGLU into y [n_ent, N/2]; else down with the weighted combine into out f32 [T, N]. max_rows = T
-// bounds every expert segment (a token picks an expert at most once).
+// or uint8 [E_local, N/32, K/32, 64, 16] fp8 tiles with their row scales f32 [E_local, N] (ops.tile_experts_fp8), or the
+// raw bytes of MXFP4 tiles [E_local, N/32, K/64, 64, 16] with their e8m0 block exponents [E_local, N/32, K/64, 32, 2]
+// (ops.tile_experts_mxfp4). fp8 and mxfp4 tiles look alike (uint8, [.., 64, 16]): fmt names the format, and the scale's
+// dtype and shape and x's K (32 or 64 columns per tile vector) must agree with it. glu: gate_up with fused SwiGLU into
+// y [n_ent, N/2]; else down with the weighted combine into out f32 [T, N]. max_rows = T bounds every expert segment (a
+// token picks an expert at most once).
 static void wstream_grouped(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> scale, int64_t fmt,
                             at::Tensor perm_tok, at::Tensor perm_w, at::Tensor expert_off, int64_t e_lo,
                             int64_t max_rows, bool gather, c10::optional<at::Tensor> y, c10::optional<at::Tensor> out,
                             bool pin) {
   check_stream_x("wstream_grouped", x);
-  TORCH_CHECK(fmt != kafka::WF_MXFP4, "wstream_grouped: no MXFP4 expert tiles");
   const int vk = check_wfmt("wstream_grouped", fmt, wt, scale, 1);
   CHECK_DT(perm_tok, at::kInt); CHECK_DT(perm_w, at::kFloat); CHECK_DT(expert_off, at::kInt);
   const int E_local = wt.size(0), N = wt.size(1) * 32, K = wt.size(2) * vk;
-  TORCH_CHECK(x.size(1) == K && K % 256 == 0 && N % 64 == 0, "wstream_grouped: K / N");
+  TORCH_CHECK(x.size(1) == K, "wstream_grouped: K mismatch (x has K = ", x.size(1), ", the tiles ", K, ")");
+  TORCH_CHECK(K % 256 == 0 && N % 64 == 0, "wstream_grouped: K / N");
   const int64_t n_ent = perm_tok.numel();
   TORCH_CHECK(perm_w.numel() == n_ent && perm_tok.is_contiguous() && perm_w.is_contiguous(), "wstream_grouped: perm");
   TORCH_CHECK(expert_off.is_contiguous() && e_lo >= 0 && expert_off.numel() >= e_lo + E_local + 1,

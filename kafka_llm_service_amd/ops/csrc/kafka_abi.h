@@ -190,8 +190,10 @@ hipError_t kafka_launch_slab_reduce(const float* P, int S, int M, int N, bf16* Y
 // Grouped streaming GEMM for the expert MLP (see wstream_grouped_kernel). max_rows bounds any expert's segment
 // (the token count T: a token picks an expert at most once); glu: gate_up with fused SwiGLU into Y [n_ent, N/2];
 // else combine into out_f32 [T, N].
-// wfmt: WF_BF16 (Wt [E_local][N/32][K/16][64 lanes][8], no scale) or WF_FP8 (e4m3 bytes [E_local][N/32][K/32][64][16]
-// and St [E_local][N] fp32 power-of-two row scales in tile order, ops.tile_experts_fp8), both indexed by the local expert.
+// wfmt: WF_BF16 (Wt [E_local][N/32][K/16][64 lanes][8], no scale), WF_FP8 (e4m3 bytes [E_local][N/32][K/32][64][16]
+// and St [E_local][N] fp32 power-of-two row scales in tile order, ops.tile_experts_fp8) or WF_MXFP4 (e2m1 bytes
+// [E_local][N/32][K/64][64][16] and Se [E_local][N/32][K/64][32][2] e8m0 block exponents, ops.tile_experts_mxfp4: the
+// dense images per expert), tiles and scales indexed by the local expert.
 hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale,
                                         int e_local, int N, int K, const int* perm_tok, const float* perm_w,
                                         const int* expert_off, int e_lo, int max_rows, int gather, bf16* Y,

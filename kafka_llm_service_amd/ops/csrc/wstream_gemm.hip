@@ -729,7 +729,19 @@ __global__ __launch_bounds__(256 * KW) void wstream_gemm_kernel(const bf16* __re
 // operand), so the accumulators hold true values and the X stage, the MT = 4 rule and both epilogues are the bf16
 // kernel's. St is a trailing argument whose type depends on WFMT — an empty struct for bf16, which never reads it: the
 // 24 bf16 instantiations compile to the register counts they had before fp8 (profiles/wfp8_moe/resource_usage.txt,
-// profiles/wfmt/resource_usage.txt). MXFP4 expert tiles are not built.
+// profiles/wfmt/resource_usage.txt).
+//
+// WFMT = WF_MXFP4 (MXFP4 expert weights, ops.tile_experts_mxfp4): Wt is the e2m1 image Wt4[E_local][N/32][K/64][64][16 B]
+// of the dense kernel's WF_MXFP4 per expert (GLU-interleaved for w13) and Se[E_local][N/32][K/64][32 rows][2 B] the dense
+// e8m0 block-scale image per expert, both indexed by the LOCAL expert like the fp8 pair. A wave loads KSTEP / 4 vectors
+// per chunk (4 at KC = 256, 2 at KC = 128) and with each one its raw 2-B scale pair (byte 0: dwords 0, 1; byte 1: dwords
+// 2, 3), issued ahead of the weight vectors under the same PIN fence; nibbles and exponent bytes stay raw in wa / wb and
+// sa / sb and each k-step's dword is dequantised right before its MFMAs (dq4 with uint32(e) << 23 as its scale
+// operand), exactly as the dense W4 path. The B fragments are the exact bf16 values e2m1 * 2^e, so every accumulator
+// sees the MFMA sequence of the bf16 kernel on the dequantised experts (the GLU half is bit-equal to it). The scale
+// address is in range wherever the weight address is (same tile and vector index), inactive tail waves included, so
+// every load stays unconditional. MT = 4 fits its 256-register bound without scratch (the raw prefetch is 2 x 2
+// vectors, a quarter of bf16's), so it keeps the shared occupancy bound (profiles/wfp4_moe/resource_usage.txt).
 // (The type is picked by a specialisation, not by std::conditional<WFMT == WF_FP8, ...>: that expression would be part
 // of the kernel's mangled name, with the unnamed enum's compiler-made name in it, which the host and the device pass
 // number differently — the host stub then registers a symbol the code object does not have.)
@@ -741,6 +753,10 @@ struct WfScales {
 template <>
 struct WfScales<WF_FP8> {
   typedef const float* type;
+};
+template <>
+struct WfScales<WF_MXFP4> {
+  typedef const uint16_t* type;  // raw e8m0 pairs
 };
 template <int MT, int KC, bool GATHER, bool COMBINE, bool PIN, int WFMT = WF_BF16>
 __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(const bf16* __restrict__ X, int64_t ldx,
@@ -755,11 +771,11 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
   constexpr int CPR = KC / 8;
   constexpr int XL = ROWS * CPR / 256;
   constexpr int KSTEP = KC / 16;
-  constexpr bool W8 = WFMT == WF_FP8;
+  constexpr bool W8 = WFMT == WF_FP8, W4 = WFMT == WF_MXFP4;
   constexpr int KSV = KSTEP / wf_ksteps(WFMT);  // 16-B weight vectors per chunk
+  constexpr int NSC = W4 ? KSV : 1;             // mxfp4: raw block-scale pairs prefetched per chunk (one per vector)
   typedef wf_vec<WFMT> wvec;
   static_assert(CPR >= 16 && XL >= 1, "chunk too small");
-  static_assert(WFMT != WF_MXFP4, "the expert kernel takes bf16 and fp8 tiles");
   static_assert(KSTEP % wf_ksteps(WFMT) == 0, "quantised tiles hold whole vectors of k-steps");
   __shared__ __attribute__((aligned(16))) bf16 xs[2][ROWS * KC];
   const int el = blockIdx.y, e = e_lo + el;
@@ -772,13 +788,17 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
   const int r = lane & 31, h = lane >> 5;
   const int nb = blockIdx.x * 4 + w;
   const bool active = nb < (N >> 5);
-  // (an inactive tail wave streams the last tile, and reads its scales; both layouts: K / 16 bf16 or K / 32 fp8
-  // vectors of 64 lanes x 16 B per tile row)
+  // (an inactive tail wave streams the last tile, and reads its scales; every layout: K / 16 bf16, K / 32 fp8 or
+  // K / 64 mxfp4 vectors of 64 lanes x 16 B per tile row)
   const int nbl = active ? nb : (N >> 5) - 1;
-  const wvec* wp =
-      reinterpret_cast<const wvec*>(Wt) + ((int64_t)el * (N >> 5) + nbl) * (K >> wf_vshift(WFMT)) * 64 + lane;
+  const int64_t v0 = ((int64_t)el * (N >> 5) + nbl) * (K >> wf_vshift(WFMT));  // this wave's first vector
+  const wvec* wp = reinterpret_cast<const wvec*>(Wt) + v0 * 64 + lane;
   float wsc = 1.f;  // fp8: 2^e of this lane's weight row
   if constexpr (W8) wsc = St[(int64_t)el * N + 32 * nbl + r];
+  // mxfp4: the lane's row in the block-scale image, 32 rows x 2 B per vector (same expert, tile and vector index as wp:
+  // in range wherever the weight load is)
+  const uint16_t* sp = nullptr;
+  if constexpr (W4) sp = St + v0 * 32 + r;
   const int nchunks = K / KC;
 
   // A-row sources of this thread's staged chunks (fixed over K)
@@ -804,7 +824,12 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
       *reinterpret_cast<bf16x8*>(&xs[buf][row * KC + 8 * (c ^ (row & 15))]) = xr[i];
     }
   };
-  auto load_w = [&](wvec(&wv)[KSV], int ch) {
+  auto load_w = [&](wvec(&wv)[KSV], uint16_t(&sv)[NSC], int ch) {
+    if constexpr (W4) {
+      // the block scales first: loads return in order, so the first dequantisation waits for them and vector 0 only
+#pragma unroll
+      for (int t = 0; t < KSV; ++t) sv[t] = __builtin_nontemporal_load(sp + (int64_t)(ch * KSV + t) * 32);
+    }
 #pragma unroll
     for (int t = 0; t < KSV; ++t) wv[t] = __builtin_nontemporal_load(wp + (int64_t)(ch * KSV + t) * 64);
     if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);  // (prefetch kept ahead of the MFMAs, as wstream_gemm)
@@ -815,11 +840,18 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[mt][i] = 0.f;
-  auto compute = [&](int buf, const wvec(&wv)[KSV]) {
+  auto compute = [&](int buf, const wvec(&wv)[KSV], const uint16_t(&sv)[NSC]) {
 #pragma unroll
     for (int t = 0; t < KSTEP; ++t) {
       bf16x8 wf;
-      if constexpr (W8) {
+      if constexpr (W4) {
+        // dequantised right before its MFMAs: the prefetch registers keep the raw nibbles and exponent bytes; dword
+        // t & 3 of vector t >> 2 is this k-step, its block exponent byte (t & 3) >> 1 of the vector's pair
+        const u32x4 v = wv[t >> 2];
+        const uint32_t e2 = sv[t >> 2];
+        const uint32_t eb = (t & 2) ? e2 >> 8 : e2 & 0xffu;
+        wf = dq4(v[t & 3], __builtin_bit_cast(float, eb << 23));
+      } else if constexpr (W8) {
         // dequantised right before its MFMAs: the prefetch registers keep the raw fp8
         const u32x4 v = wv[t >> 1];
         wf = (t & 1) ? dq8(v[2], v[3], wsc) : dq8(v[0], v[1], wsc);
@@ -841,32 +873,33 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void wstream_grouped_kernel(c
     }
   };
   wvec wa[KSV], wb[KSV];
+  uint16_t sa[NSC], sb[NSC];  // (mxfp4 only: dead otherwise)
   load_x(0);
-  load_w(wa, 0);
+  load_w(wa, sa, 0);
   store_x(0);
   __syncthreads();
   int ch = 0;
   for (; ch + 2 < nchunks; ch += 2) {
     load_x(ch + 1);
-    load_w(wb, ch + 1);
-    compute(0, wa);
+    load_w(wb, sb, ch + 1);
+    compute(0, wa, sa);
     store_x(1);
     __syncthreads();
     load_x(ch + 2);
-    load_w(wa, ch + 2);
-    compute(1, wb);
+    load_w(wa, sa, ch + 2);
+    compute(1, wb, sb);
     store_x(0);
     __syncthreads();
   }
   if (ch + 1 < nchunks) {
     load_x(ch + 1);
-    load_w(wb, ch + 1);
-    compute(0, wa);
+    load_w(wb, sb, ch + 1);
+    compute(0, wa, sa);
     store_x(1);
     __syncthreads();
-    compute(1, wb);
+    compute(1, wb, sb);
   } else {
-    compute(0, wa);
+    compute(0, wa, sa);
   }
 
   if constexpr (!COMBINE) {
@@ -1102,7 +1135,8 @@ extern "C" hipError_t kafka_launch_slab_reduce(const float* P, int S, int M, int
 }  // namespace kafka
 
 namespace kafka {
-// One launch of wstream_grouped_kernel: the kernel's arguments (scale: St for fp8 tiles), the grid and the stream.
+// One launch of wstream_grouped_kernel: the kernel's arguments (scale: St for fp8 tiles, Se for mxfp4 ones), the grid
+// and the stream.
 struct WgLaunch {
   const bf16* X;
   int64_t ldx;
@@ -1132,6 +1166,10 @@ static void launch_wg_cfg(const WgLaunch& a, int wfmt, int pin) {
     const auto* st = static_cast<const float*>(a.scale);
     pin ? go(wstream_grouped_kernel<MT, KC, G, C, true, WF_FP8>, st)
         : go(wstream_grouped_kernel<MT, KC, G, C, false, WF_FP8>, st);
+  } else if (wfmt == WF_MXFP4) {
+    const auto* se = static_cast<const uint16_t*>(a.scale);
+    pin ? go(wstream_grouped_kernel<MT, KC, G, C, true, WF_MXFP4>, se)
+        : go(wstream_grouped_kernel<MT, KC, G, C, false, WF_MXFP4>, se);
   } else {
     pin ? go(wstream_grouped_kernel<MT, KC, G, C, true>, NoScales{})
         : go(wstream_grouped_kernel<MT, KC, G, C, false>, NoScales{});
@@ -1141,9 +1179,10 @@ static void launch_wg_cfg(const WgLaunch& a, int wfmt, int pin) {
 // Grouped streaming GEMM for the expert MLP (see wstream_grouped_kernel). max_rows bounds any expert's segment
 // (the token count T: a token picks an expert at most once); glu: gate_up with fused SwiGLU into Y [n_ent, N/2];
 // else combine into out_f32 [T, N].
-// wfmt: bf16 expert tiles Wt [E_local][N/32][K/16][64][8] without scales, or fp8 ones [E_local][N/32][K/32][64][16]
-// e4m3 bytes with St [E_local][N] fp32 row scales in tile order (ops.tile_experts_fp8); same grid, MT choice and
-// outputs.
+// wfmt: bf16 expert tiles Wt [E_local][N/32][K/16][64][8] without scales, fp8 ones [E_local][N/32][K/32][64][16]
+// e4m3 bytes with St [E_local][N] fp32 row scales in tile order (ops.tile_experts_fp8), or MXFP4 ones
+// [E_local][N/32][K/64][64][16] e2m1 bytes with Se [E_local][N/32][K/64][32][2] e8m0 block exponents
+// (ops.tile_experts_mxfp4); same grid, MT choice and outputs.
 extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, int wfmt, const void* Wt,
                                                   const void* scale, int e_local, int N, int K, const int* perm_tok,
                                                   const float* perm_w, const int* expert_off, int e_lo, int max_rows,
@@ -1156,9 +1195,10 @@ extern "C" hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, i
       if (scale != nullptr) return hipErrorInvalidValue;
       break;
     case WF_FP8:
+    case WF_MXFP4:  // (K % 256 == 0 above: whole 32- / 64-column weight vectors)
       if (Wt == nullptr || scale == nullptr) return hipErrorInvalidValue;
       break;
-    default: return hipErrorInvalidValue;  // (no MXFP4 expert tiles)
+    default: return hipErrorInvalidValue;
   }
   // MT = 4 (128-row tiles on 128-deep K chunks) for large steps: with 64-row tiles every
   // row tile of an expert re-streams its weights, and those tiles run far apart in dispatch order (blockIdx.z is the
