@@ -74,13 +74,14 @@ def main():
     scale = D ** -0.5
     out = torch.empty(B, Hq, D, device=dev, dtype=torch.bfloat16)
     kv_bytes_tok = Hkv * D * 2 * 2 if args.kv_dtype == "bf16" else Hkv * (2 * D + 2)
+    variants = (0, 3) if args.kv_dtype == "bf16" else (0,)  # tile variant 3 reads bf16 pages only
 
     # cascade prefix pass, several chunk sizes
     for chunk in [int(x) for x in args.chunks.split(",")]:
       nc = math.ceil(P / chunk)
       part = torch.empty(B, Hq, nc + 2, D, device=dev)
       lse = torch.empty(B, Hq, nc + 2, device=dev)
-      for var in (0, 3):
+      for var in variants:
         tile = ops.tile_rows(var) // G
         items = [(g0, min(tile, B - g0), 0, ci * chunk, min(P, (ci + 1) * chunk), ci, 0, 0)
                  for g0 in range(0, B, tile) for ci in range(nc)]
@@ -118,7 +119,7 @@ def main():
     qp = torch.randn(T, Hq, D, device=dev, dtype=torch.bfloat16)
     ctx = P + Ls - T
     ql = torch.arange(ctx, ctx + T, dtype=torch.int32, device=dev)
-    for var in (0, 3):
+    for var in variants:
         tile = ops.tile_rows(var) // G
         for ck in (1024, 2048, 4096, 0):
             if ck == 0:
@@ -146,7 +147,7 @@ def main():
     qp = torch.randn(T, Hq, D, device=dev, dtype=torch.bfloat16)
     ql = torch.arange(0, T, dtype=torch.int32, device=dev)
     o = torch.empty(T, Hq, D, device=dev, dtype=torch.bfloat16)
-    for var in (0, 3):
+    for var in variants:
         tile = ops.tile_rows(var) // G
         items = [(t0, min(tile, T - t0), 0, 0, t0 + tile, -1, 0, 0) for t0 in range(0, T, tile)]
         it = torch.tensor(items, dtype=torch.int32, device=dev)
@@ -157,7 +158,7 @@ def main():
     # the engine's plan (model_runner.plan_prefill_items): long tiles split into key pieces + per-range merges
     from kafka_llm_service_amd.engine.model_runner import plan_prefill_items
 
-    for var, T in [(v_, t_) for v_ in (0, 3) for t_ in (2048, 4096, 8192)]:
+    for var, T in [(v_, t_) for v_ in variants for t_ in (2048, 4096, 8192)]:
         qp = torch.randn(T, Hq, D, device=dev, dtype=torch.bfloat16)
         ql = torch.arange(0, T, dtype=torch.int32, device=dev)
         o = torch.empty(T, Hq, D, device=dev, dtype=torch.bfloat16)

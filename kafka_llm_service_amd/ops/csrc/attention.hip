@@ -14,9 +14,12 @@
 // Scores use the exp2 domain (scale * log2 e folded in); lse outputs are log2-domain.
 //
 // Kernels:
-//   attn_decode_kernel   grid (splits, Hkv, B): one query token per sequence, its G = Hq/Hkv heads packed in the
-//                        q columns, the sequence's keys split over `splits` workgroups and over the 4 waves of each
-//                        (flash-decoding); waves combine through LDS, splits through attn_merge_kernel.
+//   attn_decode_kernel   grid (Hkv, work items + merge workgroups): a work item is one piece of one sequence's keys
+//                        for its one query token, the G = Hq/Hkv heads packed in the q columns, the piece's keys
+//                        split over the 4 waves (flash-decoding); waves combine through LDS, the pieces of a row
+//                        through partial slots merged by the launch itself (one-piece rows directly, split rows by
+//                        the last piece to finish) or by attn_merge_kernel. A workgroup past the work items merges
+//                        the fp32 partials of other rows (FusedMerge) and streams no keys.
 //   attn_prefill_kernel  grid (Hkv, work items): a tile of up to 128 (token, head) query rows against a paged key
 //                        range; per-row causal limit; writes bf16 output directly or an (O, lse) partial. Used for
 //                        chunked prefill and for the cascade pass where the rows are the decode sequences of a
@@ -42,26 +45,10 @@ namespace kafka {
 
 // (PAGE, the fp8 page constants and the work-item records AttnWorkItem / DecodeItem: kafka_abi.h)
 
-// Reductions with the partner lane l ^ 32 on gfx950's v_permlane32_swap (one VALU op, no LDS crossbar round trip
-// through ds_bpermute — which also queued behind the K/V fragment reads): swapping a register with itself leaves
-// x[l] in one result and x[l ^ 32] in the other, so a symmetric op of the two is the xor-32 reduction on every lane.
-// max as llvm.maximum (gfx950 v_maximum3_f32, 3 inputs, no NaN-quieting v_max x, x of each MFMA result that fmaxf
-// costs in IEEE mode; attn_tile.hip t3_max)
-__device__ __forceinline__ float vmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
-__device__ __forceinline__ float xor32_max(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return vmax(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xor32_sum(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
+// (vmax, xor32_max / xor32_sum, wait_vmcnt and exp2i, the per-wave helpers shared with attn_tile.hip: common.h; so
+// are u32x4 and dq8, the e4m3 -> bf16x8 dequantisation shared with the fp8-weight decode GEMM)
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float exp2i(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
-
-// (u32x4 and dq8, the e4m3 -> bf16x8 dequantisation: common.h, shared with the fp8-weight decode GEMM)
 
 template <int D>
 struct WaveAcc {
@@ -142,6 +129,12 @@ template <typename BT>
 __device__ __forceinline__ void block_pages(const BT& bt, int key0, int end, int& p0, int& p1) {
   p0 = bt[key0 >> 4];
   p1 = (key0 + 16 < end) ? bt[(key0 >> 4) + 1] : p0;
+}
+
+// Does the block of keys [key0, key0 + 32) need the per-key range / causal test of softmax_pv? (wave-uniform; false
+// for interior blocks)
+__device__ __forceinline__ bool block_masked(int key0, int lo, int hi, int limit) {
+  return (key0 < lo) | (key0 + 32 > hi) | (key0 + 31 > limit);
 }
 
 // Online softmax of one 32-key S^T tile (raw scores, lane = query column) + the P.V MFMAs.
@@ -258,7 +251,7 @@ __device__ __forceinline__ void attn_blocks(const void* __restrict__ k_cache, co
   };
   auto compute = [&](const Frag& f, int b) {
     const int key0 = base + 32 * b;
-    const bool masked = (key0 < lo) | (key0 + 32 > hi) | (key0 + 31 > limit);
+    const bool masked = block_masked(key0, lo, hi, limit);
     if constexpr (FP8)
       attn_compute8<D>(f, key0, lo, hi, limit, qf, scale_log2, acc, lane, masked);
     else
@@ -303,7 +296,8 @@ __device__ __forceinline__ void init_acc(WaveAcc<D>& acc) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Decode: grid (work items, Hkv), 256 threads. Requires G <= 8.
+// Decode: grid (Hkv, work items + merge workgroups), 256 threads. Requires G <= 8. Workgroup (kvh, y) runs work item
+// y for kv head kvh (decode_piece); y >= n_items merges prefill rows instead (fused_merge_rows, below).
 // A work item is one decode row's key range [lo, hi) — the whole per-thread suffix, or one of `nsplit` pieces of a
 // long one (the host sizes pieces so every workgroup streams about the same bytes: one 3k-token history no longer
 // holds the whole launch while the short ones have finished). Row b's partials live at slots [0, npre) (cascade
@@ -328,99 +322,105 @@ struct DecodeSmem {
 static_assert(offsetof(DecodeSmem<128>, so) % 16 == 0 && offsetof(DecodeSmem<128>, qs) % 16 == 0,
               "DecodeSmem: qs / so must be 16-B aligned");
 
-// the workgroup's G final rows from sm.so to out (every thread of the workgroup calls it)
-template <int D>
-__device__ __forceinline__ void store_rows_sc1(DecodeSmem<D>& sm, bf16* __restrict__ out, int64_t out_stride, int b,
-                                               int kvh, int G) {
+// Parameters of a decode launch (by value, next to FusedMerge)
+struct DecodeArgs {
+  const bf16* q;  // row b at q + b * q_stride, [Hq, D]
+  int64_t q_stride;
+  const void* k_cache;
+  const void* v_cache;
+  int Hkv, G;
+  const int* block_tables;  // row b at block_tables + b * bt_stride
+  int bt_stride;
+  const DecodeItem* items;
+  int n_items;  // grid rows from n_items on are merge workgroups
+  int B;
+  float* out_part;  // [B, Hq, S_total, D]
+  float* lse_part;  // [B, Hq, S_total]
+  int S_total;
+  float scale_log2;
+  bf16* out;  // final rows (row b at out + b * out_stride), or nullptr: every piece leaves its partial
+  int64_t out_stride;
+  int* tickets;           // [B, Hkv]
+  const bf16* pre_bf16;   // the prefix partials (slots < npre) as bf16 in out_part's shape, or nullptr: in out_part
+};
+
+constexpr int DEC_MG = 32;  // MG: prefix partials per load round trip of the fused merges
+
+// The 32-key blocks and the pages covering a piece's keys [lo, hi)
+struct PieceBlocks {
+  int a0, nb, pg0, npg;  // first block's first key, blocks; first page, pages
+  __device__ __forceinline__ PieceBlocks(int lo, int hi)
+      : a0(lo & ~31), nb(hi > lo ? (hi - a0 + 31) >> 5 : 0), pg0(a0 >> 4), npg(nb > 0 ? ((hi - 1) >> 4) - pg0 + 1 : 0) {}
+  __device__ __forceinline__ bool in_lds() const { return npg <= DEC_MAXPG; }
+};
+
+// Stage 1: the piece's page ids (when they fit) and, at three workgroups per CU, the row's G query heads -> LDS
+template <int D, bool OCC3>
+__device__ __forceinline__ void stage_pages_q(DecodeSmem<D>& sm, const DecodeArgs& a, const int* __restrict__ bt,
+                                              const PieceBlocks& pb, int b, int kvh) {
+  if (pb.in_lds())
+    for (int i = threadIdx.x; i < pb.npg; i += 256) sm.pages[i] = bt[pb.pg0 + i];
+  if constexpr (OCC3) {
+    for (int i = threadIdx.x; i < a.G * (D / 8); i += 256) {
+      const int g = i / (D / 8), c = i % (D / 8);
+      *reinterpret_cast<bf16x8*>(&sm.qs[g][8 * c]) =
+          load_bf16x8(a.q + (int64_t)b * a.q_stride + (int64_t)(kvh * a.G + g) * D + 8 * c);
+    }
+  }
   __syncthreads();
-  const int t = threadIdx.x;
-  if (t < G * (D / 8)) {
-    const int g = t / (D / 8), c = (t % (D / 8)) * 8;
-    store16_slab(reinterpret_cast<float*>(out + (int64_t)b * out_stride + (int64_t)(kvh * G + g) * D + c),
-                 *reinterpret_cast<const f32x4*>(&sm.so[g][c]));
+}
+
+// Stage 2: wave w streams the piece's key blocks w, w + 4, ... into its accumulator; page ids from LDS, or from the
+// block-table row `bt` for a piece of more than DEC_MAXPG pages
+template <int D, bool FP8>
+__device__ __forceinline__ void stream_keys(const DecodeSmem<D>& sm, const DecodeArgs& a, const int* __restrict__ bt,
+                                            const PieceBlocks& pb, int b, int kvh, int lo, int hi, WaveAcc<D>& acc) {
+  const LdsPages lds_pages{sm.pages, pb.pg0};
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  if constexpr (!FP8) {
+    // Three waves per SIMD (VGPR budget 168): no Q fragments and no second K/V block in registers — each wave
+    // has its one block in flight at a time, and 12 waves per CU (3 workgroups) keep the memory system fed;
+    // more resident workgroups also cover each other's piece start / end. (Page source per block: one loop per
+    // source ran 1 - 1.6 % slower at 20k keys, profiles/attn_decode_stages/attn_bench_loop_per_source.jsonl.)
+    const bool qrow = r < a.G;
+    for (int bk = w; bk < pb.nb; bk += 4) {
+      const int key0 = pb.a0 + 32 * bk;
+      int p0, p1;
+      if (pb.in_lds())
+        block_pages(lds_pages, key0, hi, p0, p1);
+      else
+        block_pages(bt, key0, hi, p0, p1);
+      KVFrag<D> f;
+      load_kv<D>(f, static_cast<const bf16*>(a.k_cache), static_cast<const bf16*>(a.v_cache), a.Hkv, kvh, p0, p1,
+                 lane);
+      f32x16 sacc = {};
+#pragma unroll
+      for (int kk = 0; kk < D / 16; ++kk) {
+        bf16x8 qv = *reinterpret_cast<const bf16x8*>(&sm.qs[qrow ? r : 0][16 * kk + 8 * h]);
+        if (!qrow) qv = bf16x8{};
+        sacc = mfma32(f.k[kk], qv, sacc);
+      }
+      softmax_pv<D>(sacc, block_masked(key0, lo, hi, 0x7fffffff), key0, lo, hi, 0x7fffffff, a.scale_log2, f.v, acc,
+                    lane);
+    }
+  } else if (w < pb.nb) {
+    bf16x8 qf[D / 16];
+    load_q_frags<D>(qf, a.q + (int64_t)b * a.q_stride + (int64_t)(kvh * a.G + r) * D, r < a.G, h);
+    if (pb.in_lds())
+      attn_blocks<D, FP8>(a.k_cache, a.v_cache, a.Hkv, kvh, lds_pages, pb.a0, w, pb.nb, 4, hi, lo, hi, 0x7fffffff, qf,
+                          a.scale_log2, acc, lane);
+    else
+      attn_blocks<D, FP8>(a.k_cache, a.v_cache, a.Hkv, kvh, bt, pb.a0, w, pb.nb, 4, hi, lo, hi, 0x7fffffff, qf,
+                          a.scale_log2, acc, lane);
   }
 }
 
-// One decode piece: keys [lo, hi) of row b, kv head kvh, piece `split` of S, partial slots from split_offset. Every
-// thread of the workgroup calls it with the same arguments (it synchronises the workgroup); returns when the
-// piece's partial or final rows are written.
-// OST: the final bf16 rows leave through LDS as 16-B sc1 stores (one instruction per 16 B of a row instead of one
-// 8-B plain store per thread: the lines leave this XCD's L2, so the launch ends with no dirty output lines to write
-// back; the o GEMM reads them on every XCD). Needs 16-B aligned rows (host-checked).
-template <int D, bool FP8, bool OST = false>
-__device__ __forceinline__ void decode_piece(DecodeSmem<D>& sm, const bf16* __restrict__ q, int64_t q_stride,
-                                             const void* __restrict__ k_cache, const void* __restrict__ v_cache,
-                                             int Hkv, int G, const int* __restrict__ block_tables, int bt_stride,
-                                             int b, int kvh, int lo, int hi, int split, int S, int split_offset,
-                                             float* __restrict__ out_part, float* __restrict__ lse_part, int S_total,
-                                             float scale_log2, bf16* __restrict__ out, int64_t out_stride,
-                                             int* __restrict__ tickets, const bf16* __restrict__ pre_bf16) {
-  constexpr bool OCC3 = !FP8;  // bf16: three workgroups per CU, Q in LDS, one K/V block per wave in flight
-  constexpr int MG = 32;       // prefix partials per load round trip of the fused merge
-  auto& sO = sm.sO;
-  auto& sM = sm.sM;
-  auto& sL = sm.sL;
-  auto& sW = sm.sW;
-  auto& sWt = sm.sWt;
+// Stage 3: every wave's (O, m, l) of the G heads -> LDS
+template <int D>
+__device__ __forceinline__ void publish_wave_partials(DecodeSmem<D>& sm, const WaveAcc<D>& acc, int G) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const int Hq = Hkv * G;
-  const int a0 = lo & ~31;
-  const int nb = hi > lo ? (hi - a0 + 31) >> 5 : 0;
-  const int* bt = block_tables + (int64_t)b * bt_stride;
-
-  // the piece's page ids -> LDS (pages covering [a0, hi))
-  const int pg0 = a0 >> 4;
-  const int npg = nb > 0 ? ((hi - 1) >> 4) - pg0 + 1 : 0;
-  const bool lds_pt = npg <= DEC_MAXPG;
-  if (lds_pt)
-    for (int i = threadIdx.x; i < npg; i += 256) sm.pages[i] = bt[pg0 + i];
-  if constexpr (OCC3) {
-    for (int i = threadIdx.x; i < G * (D / 8); i += 256) {
-      const int g = i / (D / 8), c = i % (D / 8);
-      *reinterpret_cast<bf16x8*>(&sm.qs[g][8 * c]) = load_bf16x8(q + (int64_t)b * q_stride + (int64_t)(kvh * G + g) * D + 8 * c);
-    }
-  }
-  __syncthreads();
-  WaveAcc<D> acc;
-  init_acc<D>(acc);
-  if constexpr (OCC3) {
-    // Three waves per SIMD (VGPR budget 168): no Q fragments and no second K/V block in registers — each wave
-    // has its one block in flight at a time, and 12 waves per CU (3 workgroups) keep the memory system fed;
-    // more resident workgroups also cover each other's piece start / end.
-    if (w < nb && !FP8) {
-      const bool qrow = r < G;
-      for (int bk = w; bk < nb; bk += 4) {
-        const int key0 = a0 + 32 * bk;
-        int p0, p1;
-        if (lds_pt)
-          block_pages(LdsPages{sm.pages, pg0}, key0, hi, p0, p1);
-        else
-          block_pages(bt, key0, hi, p0, p1);
-        KVFrag<D> f;
-        load_kv<D>(f, static_cast<const bf16*>(k_cache), static_cast<const bf16*>(v_cache), Hkv, kvh, p0, p1, lane);
-        f32x16 sacc = {};
-#pragma unroll
-        for (int kk = 0; kk < D / 16; ++kk) {
-          bf16x8 qv = *reinterpret_cast<const bf16x8*>(&sm.qs[qrow ? r : 0][16 * kk + 8 * h]);
-          if (!qrow) qv = bf16x8{};
-          sacc = mfma32(f.k[kk], qv, sacc);
-        }
-        const bool masked = (key0 < lo) | (key0 + 32 > hi);
-        softmax_pv<D>(sacc, masked, key0, lo, hi, 0x7fffffff, scale_log2, f.v, acc, lane);
-      }
-    }
-  } else if (w < nb) {
-    bf16x8 qf[D / 16];
-    load_q_frags<D>(qf, q + (int64_t)b * q_stride + (int64_t)(kvh * G + r) * D, r < G, h);
-    if (lds_pt)
-      attn_blocks<D, FP8>(k_cache, v_cache, Hkv, kvh, LdsPages{sm.pages, pg0}, a0, w, nb, 4, hi, lo, hi, 0x7fffffff,
-                          qf, scale_log2, acc, lane);
-    else
-      attn_blocks<D, FP8>(k_cache, v_cache, Hkv, kvh, bt, a0, w, nb, 4, hi, lo, hi, 0x7fffffff, qf, scale_log2, acc,
-                          lane);
-  }
-  // cross-wave combine
   if (r < G) {
 #pragma unroll
     for (int t = 0; t < D / 32; ++t)
@@ -428,245 +428,270 @@ __device__ __forceinline__ void decode_piece(DecodeSmem<D>& sm, const bf16* __re
       for (int i4 = 0; i4 < 4; ++i4) {
         const int d = 32 * t + 8 * i4 + 4 * h;
         f32x4 v = {acc.o[t][4 * i4 + 0], acc.o[t][4 * i4 + 1], acc.o[t][4 * i4 + 2], acc.o[t][4 * i4 + 3]};
-        *reinterpret_cast<f32x4*>(&sO[w][r][d]) = v;
+        *reinterpret_cast<f32x4*>(&sm.sO[w][r][d]) = v;
       }
     if (h == 0) {
-      sM[w][r] = acc.m;
-      sL[w][r] = acc.l;
+      sm.sM[w][r] = acc.m;
+      sm.sL[w][r] = acc.l;
     }
   }
   __syncthreads();
-  if (out != nullptr && S == 1) {
-    // Fused merge (one split per sequence): fold in the cascade-prefix partials [0, split_offset) written earlier
-    // on the stream and write the final bf16 rows — no merge kernel, no partial round trip of this split.
-    // Phase 1: wave w owns heads w, w + 4: lanes load the prefix lse values in parallel, wave-reduce the max and
-    // the weight sum, and publish per-split weights in LDS. Phase 2: thread (g, 4 dims) sums weight x partial over
-    // the splits with all loads of a group of 8 in flight.
-    for (int g = w; g < G; g += 4) {
-      float Ms = -INFINITY;
+}
+
+// Cross-wave combine of head g: M = max_i sM[i][g], L = sum_i 2^(sM[i][g] - M) sL[i][g], and the return value, the
+// same weighted sum of sO[i][g][d ...] for V = float or f32x4 — unnormalised: each caller normalises in its own way.
+// (A caller that needs only M and L drops the result, and its LDS reads go with it.)
+template <typename V, int D>
+__device__ __forceinline__ V combine_waves(const DecodeSmem<D>& sm, int g, int d, float& M, float& L) {
+  M = -INFINITY;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) Ms = fmaxf(Ms, sM[i][g]);
-      float Ls = 0.f;
-      if (Ms != -INFINITY) {
+  for (int i = 0; i < 4; ++i) M = fmaxf(M, sm.sM[i][g]);
+  L = 0.f;
+  V O = {};
+  if (M != -INFINITY) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) Ls += exp2f(sM[i][g] - Ms) * sL[i][g];
-      }
-      const float ls = Ls > 0.f ? Ms + log2f(Ls) : -INFINITY;
-      const int64_t pbase = ((int64_t)b * Hq + kvh * G + g) * S_total;
-      float lp = -INFINITY;
-      if (lane < split_offset) lp = lse_part[pbase + lane];
-      const float lv = lane < split_offset ? lp : (lane == split_offset ? ls : -INFINITY);
-      float mx = lv;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-      const float wv = mx == -INFINITY ? 0.f : exp2f(lv - mx);
-      float ws = wv;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) ws += __shfl_xor(ws, o, 64);
-      if (lane <= split_offset) sW[g][lane] = wv;
-      if (lane == 0) sWt[g] = ws;
+    for (int i = 0; i < 4; ++i) {
+      const float f = exp2f(sm.sM[i][g] - M);
+      L += f * sm.sL[i][g];
+      O += *reinterpret_cast<const V*>(&sm.sO[i][g][d]) * f;
     }
-    __syncthreads();
-    const int g = threadIdx.x >> 5, c = (threadIdx.x & 31) * 4;
-    if (g < G) {
-      // this workgroup's own (normalised) result for dims c..c+3
-      float Ms = -INFINITY;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) Ms = fmaxf(Ms, sM[i][g]);
-      f32x4 os = {0.f, 0.f, 0.f, 0.f};
-      float Ls = 0.f;
-      if (Ms != -INFINITY) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float f = exp2f(sM[i][g] - Ms);
-          Ls += f * sL[i][g];
-          os += *reinterpret_cast<const f32x4*>(&sO[i][g][c]) * f;
-        }
-      }
-      f32x4 acc4 = Ls > 0.f ? os * (sW[g][split_offset] / Ls) : f32x4{0.f, 0.f, 0.f, 0.f};
-      const int64_t pbase = ((int64_t)b * Hq + kvh * G + g) * S_total * D + c;
-      int s2 = 0;
-      // MG prefix partials per round trip (the cascade writes 32 per row: 2 round trips at MG = 16, 4 at 8)
-      if (pre_bf16 != nullptr) {  // bf16 cascade partials (tile v3): half the bytes of the fp32 round trip
-        const bf16* pb = pre_bf16 + pbase;
-        for (; s2 + MG <= split_offset; s2 += MG) {
-          bf16x4 v[MG];
-#pragma unroll
-          for (int j = 0; j < MG; ++j) v[j] = *reinterpret_cast<const bf16x4*>(pb + (s2 + j) * D);
-#pragma unroll
-          for (int j = 0; j < MG; ++j) {
-            const float wj = sW[g][s2 + j];
-            acc4 += f32x4{(float)v[j][0], (float)v[j][1], (float)v[j][2], (float)v[j][3]} * wj;
-          }
-        }
-        for (; s2 < split_offset; ++s2) {
-          const bf16x4 v = *reinterpret_cast<const bf16x4*>(pb + s2 * D);
-          acc4 += f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]} * sW[g][s2];
-        }
-      } else {
-        const float* pp = out_part + pbase;
-        for (; s2 + MG <= split_offset; s2 += MG) {
-          f32x4 v[MG];
-#pragma unroll
-          for (int j = 0; j < MG; ++j) v[j] = *reinterpret_cast<const f32x4*>(pp + (s2 + j) * D);
-#pragma unroll
-          for (int j = 0; j < MG; ++j) acc4 += v[j] * sW[g][s2 + j];
-        }
-        for (; s2 < split_offset; ++s2) {
-          acc4 += *reinterpret_cast<const f32x4*>(pp + s2 * D) * sW[g][s2];
-        }
-      }
-      const float inv = sWt[g] > 0.f ? 1.f / sWt[g] : 0.f;
-      bf16x4 o4;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o4[j] = (bf16)(acc4[j] * inv);
-      if constexpr (OST)
-        *reinterpret_cast<bf16x4*>(&sm.so[g][c]) = o4;
-      else
-        *reinterpret_cast<bf16x4*>(out + (int64_t)b * out_stride + (int64_t)(kvh * G + g) * D + c) = o4;
-    }
-    if constexpr (OST) store_rows_sc1<D>(sm, out, out_stride, b, kvh, G);
-    return;
   }
-  if (out != nullptr) {
-    // ticket merge: each split's partial row leaves as 16-B write-through (sc1, agent-coherent) stores — 4-B ones
-    // cost several times more per byte — and the last workgroup reads it back with 16-B sc1 loads (ld4 below)
-    for (int idx4 = threadIdx.x; idx4 < G * D / 4; idx4 += 256) {
+  return O;
+}
+
+// The piece's normalised partial (O / L, lse) -> slot `slot` of head-rows row0 + g. TICKET: another workgroup of this
+// launch reads it (ticket_merge): 16-B write-through (sc1) stores — 4-B ones cost several times more per byte — and
+// an agent-scope lse store. It keeps its own element-wise combine: hipcc compiles that shape to a mix of fused and
+// unfused multiply-adds, combine_waves<f32x4> to fused ones, and a split row's partials stay bit for bit.
+template <int D, bool TICKET>
+__device__ __forceinline__ void write_partial(const DecodeSmem<D>& sm, const DecodeArgs& a, int64_t row0, int slot) {
+  if constexpr (TICKET) {
+    for (int idx4 = threadIdx.x; idx4 < a.G * D / 4; idx4 += 256) {
       const int g = idx4 / (D / 4), d0 = (idx4 % (D / 4)) * 4;
       float M = -INFINITY;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) M = fmaxf(M, sM[i][g]);
+      for (int i = 0; i < 4; ++i) M = fmaxf(M, sm.sM[i][g]);
       float L = 0.f;
       f32x4 O4 = {0.f, 0.f, 0.f, 0.f};
       if (M != -INFINITY) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float f = exp2f(sM[i][g] - M);
-          L += f * sL[i][g];
+          const float f = exp2f(sm.sM[i][g] - M);
+          L += f * sm.sL[i][g];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) O4[j] += f * sO[i][g][d0 + j];
+          for (int j = 0; j < 4; ++j) O4[j] += f * sm.sO[i][g][d0 + j];
         }
       }
-      const int64_t pidx = ((int64_t)b * Hq + kvh * G + g) * S_total + split_offset + split;
+      const int64_t pidx = (row0 + g) * a.S_total + slot;
       const float inv = L > 0.f ? 1.f / L : 0.f, lv = L > 0.f ? M + log2f(L) : -INFINITY;
       f32x4 ov4;
 #pragma unroll
       for (int j = 0; j < 4; ++j) ov4[j] = L > 0.f ? O4[j] * inv : 0.f;
-      store16_slab(out_part + pidx * D + d0, ov4);
-      if (d0 == 0) __hip_atomic_store(lse_part + pidx, lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      store16_slab(a.out_part + pidx * D + d0, ov4);
+      if (d0 == 0) __hip_atomic_store(a.lse_part + pidx, lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-  } else
-  for (int idx = threadIdx.x; idx < G * D; idx += 256) {
-    const int g = idx / D, d = idx % D;
-    float M = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) M = fmaxf(M, sM[i][g]);
-    float L = 0.f, O = 0.f;
-    if (M != -INFINITY) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float f = exp2f(sM[i][g] - M);
-        L += f * sL[i][g];
-        O += f * sO[i][g][d];
-      }
-    }
-    const int64_t pidx = ((int64_t)b * Hq + kvh * G + g) * S_total + split_offset + split;
-    const float ov = L > 0.f ? O / L : 0.f, lv = L > 0.f ? M + log2f(L) : -INFINITY;
-    if (out == nullptr) {
-      out_part[pidx * D + d] = ov;
-      if (d == 0) lse_part[pidx] = lv;
-    } else {  // ticket merge: write-through (agent-coherent) stores, no L2-wide write-back fence needed
-      __hip_atomic_store(out_part + pidx * D + d, ov, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (d == 0) __hip_atomic_store(lse_part + pidx, lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    for (int idx = threadIdx.x; idx < a.G * D; idx += 256) {
+      const int g = idx / D, d = idx % D;
+      float M, L;
+      const float O = combine_waves<float>(sm, g, d, M, L);
+      const int64_t pidx = (row0 + g) * a.S_total + slot;
+      a.out_part[pidx * D + d] = L > 0.f ? O / L : 0.f;
+      if (d == 0) a.lse_part[pidx] = L > 0.f ? M + log2f(L) : -INFINITY;
     }
   }
-  if (out == nullptr) return;
-  // Ticket merge (S > 1, e.g. one long sequence spread over many workgroups): every split publishes its partial
-  // with agent-coherent write-through stores (another XCD's workgroup may read it; a __threadfence release here
-  // would write back the whole L2 from every workgroup), waits for them, takes a ticket, and the LAST of the S
-  // workgroups of (b, kvh) merges all split_offset + S partials (agent-coherent loads) and writes the bf16 rows —
-  // no merge kernel launch. The last one also re-arms the counter for the next launch.
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int* tk = tickets + b * Hkv + kvh;
-    const int t = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sm.s_last = t == S - 1;
-    if (t == S - 1) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!sm.s_last) return;
-  auto ld = [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-  // 16-B agent-coherent loads (sc1: not served from this XCD's possibly stale L2) as compiler builtins over a buffer
-  // of out_part, so hipcc's waitcnt pass tracks them (out_part < 2 GiB: host-checked)
-  const auto prs = buf_rsrc(out_part);
-  auto ld4 = [&](const float* p) { return load16_sc1(prs, (int)((p - out_part) * 4)); };
-  const int n = split_offset + S;  // <= 64 (host-checked)
-  for (int g = w; g < G; g += 4) {
-    const int64_t pbase = ((int64_t)b * Hq + kvh * G + g) * S_total;
-    const float lv = lane < n ? ld(lse_part + pbase + lane) : -INFINITY;
-    float mx = lv;
+}
+
+// Merge weights of head g from one wave: lane s holds the lse of slot s (-inf from slot n on); 2^(lse - max) ->
+// sW[g][0, n), their sum -> sWt[g]
+template <int D>
+__device__ __forceinline__ void merge_weights(DecodeSmem<D>& sm, int g, int n, float lv) {
+  const int lane = threadIdx.x & 63;
+  const float mx = wave_max(lv);
+  const float wv = mx == -INFINITY ? 0.f : exp2f(lv - mx);
+  const float ws = wave_sum(wv);
+  if (lane < n) sm.sW[g][lane] = wv;
+  if (lane == 0) sm.sWt[g] = ws;
+}
+
+// acc4 += sum over the bf16 cascade-prefix slots [0, npre) of w[s] x slot s (pb: the thread's 4 dims of slot 0; tile
+// v3 writes them: half the bytes of the fp32 round trip), DEC_MG loads in flight per round trip
+template <int D>
+__device__ __forceinline__ void fold_prefix_bf16(f32x4& acc4, const bf16* __restrict__ pb, const float* w, int npre) {
+  int s = 0;
+  for (; s + DEC_MG <= npre; s += DEC_MG) {
+    bf16x4 v[DEC_MG];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    const float wv = mx == -INFINITY ? 0.f : exp2f(lv - mx);
-    float ws = wv;
+    for (int j = 0; j < DEC_MG; ++j) v[j] = *reinterpret_cast<const bf16x4*>(pb + (s + j) * D);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ws += __shfl_xor(ws, o, 64);
-    if (lane < n) sW[g][lane] = wv;
-    if (lane == 0) sWt[g] = ws;
-  }
-  __syncthreads();
-  const int g = threadIdx.x >> 5, c = (threadIdx.x & 31) * 4;
-  if (g < G) {
-    f32x4 acc4 = {0.f, 0.f, 0.f, 0.f};
-    const float* pp = out_part + ((int64_t)b * Hq + kvh * G + g) * S_total * D + c;
-    const int p0 = pre_bf16 != nullptr ? split_offset : 0;  // first fp32 slot (the pieces, or every slot)
-    // one round trip for the common row: the first PQ fp32 slots (agent-coherent loads) and MG bf16 prefix slots
-    // are all in flight before the first wait (was: the prefix batch, then the pieces batch — two tail latencies)
-    constexpr int PQ = 8;
-    f32x4 pv[PQ];
-#pragma unroll
-    for (int j = 0; j < PQ; ++j) pv[j] = ld4(pp + min(p0 + j, n - 1) * D);
-    int s0 = 0;
-    if (pre_bf16 != nullptr) {  // the cascade's bf16 prefix partials, MG loads per round trip (as the one-piece path)
-      const bf16* pb = pre_bf16 + ((int64_t)b * Hq + kvh * G + g) * S_total * D + c;
-      for (; s0 + MG <= split_offset; s0 += MG) {
-        bf16x4 v[MG];
-#pragma unroll
-        for (int j = 0; j < MG; ++j) v[j] = *reinterpret_cast<const bf16x4*>(pb + (s0 + j) * D);
-#pragma unroll
-        for (int j = 0; j < MG; ++j) {
-          const float wj = sW[g][s0 + j];
-          acc4 += f32x4{(float)v[j][0], (float)v[j][1], (float)v[j][2], (float)v[j][3]} * wj;
-        }
-      }
-      for (; s0 < split_offset; ++s0) {
-        const bf16x4 v = *reinterpret_cast<const bf16x4*>(pb + s0 * D);
-        acc4 += f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]} * sW[g][s0];
-      }
+    for (int j = 0; j < DEC_MG; ++j) {
+      const float wj = w[s + j];
+      acc4 += f32x4{(float)v[j][0], (float)v[j][1], (float)v[j][2], (float)v[j][3]} * wj;
     }
+  }
+  for (; s < npre; ++s) {
+    const bf16x4 v = *reinterpret_cast<const bf16x4*>(pb + s * D);
+    acc4 += f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]} * w[s];
+  }
+}
+
+// The same over fp32 slots written by an earlier kernel (plain loads; the cascade writes up to 32 per row: 2 round
+// trips at DEC_MG = 16, 4 at 8). The ticket merge reads slots of this launch and batches them its own way.
+template <int D>
+__device__ __forceinline__ void fold_prefix_f32(f32x4& acc4, const float* __restrict__ pp, const float* w, int npre) {
+  int s = 0;
+  for (; s + DEC_MG <= npre; s += DEC_MG) {
+    f32x4 v[DEC_MG];
 #pragma unroll
-    for (int j = 0; j < PQ; ++j)
-      if (p0 + j < n) acc4 += pv[j] * sW[g][p0 + j];
-    // rows with more pieces: groups of 16 with all loads in flight (the tail of the kernel: latency, not bandwidth)
-    for (int s2 = p0 + PQ; s2 < n; s2 += 16) {
-      f32x4 v[16];
+    for (int j = 0; j < DEC_MG; ++j) v[j] = *reinterpret_cast<const f32x4*>(pp + (s + j) * D);
 #pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = ld4(pp + min(s2 + j, n - 1) * D);
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if (s2 + j < n) acc4 += v[j] * sW[g][s2 + j];
-    }
-    const float inv = sWt[g] > 0.f ? 1.f / sWt[g] : 0.f;
+    for (int j = 0; j < DEC_MG; ++j) acc4 += v[j] * w[s + j];
+  }
+  for (; s < npre; ++s) acc4 += *reinterpret_cast<const f32x4*>(pp + s * D) * w[s];
+}
+
+// The merged rows, normalised by sWt, as bf16 to `out`: thread (g, 4 dims from c) holds acc4. Every thread of the
+// workgroup calls it.
+// OST: the rows leave through LDS as 16-B sc1 stores (one instruction per 16 B of a row instead of one 8-B plain
+// store per thread: the lines leave this XCD's L2, so the launch ends with no dirty output lines to write back; the
+// o GEMM reads them on every XCD). Needs 16-B aligned rows (host-checked).
+template <int D, bool OST>
+__device__ __forceinline__ void store_final_rows(DecodeSmem<D>& sm, const DecodeArgs& a, int b, int kvh, int g, int c,
+                                                 f32x4 acc4) {
+  bf16* orow = a.out + (int64_t)b * a.out_stride + (int64_t)(kvh * a.G) * D;
+  if (g < a.G) {
+    const float inv = sm.sWt[g] > 0.f ? 1.f / sm.sWt[g] : 0.f;
     bf16x4 o4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) o4[j] = (bf16)(acc4[j] * inv);
     if constexpr (OST)
       *reinterpret_cast<bf16x4*>(&sm.so[g][c]) = o4;
     else
-      *reinterpret_cast<bf16x4*>(out + (int64_t)b * out_stride + (int64_t)(kvh * G + g) * D + c) = o4;
+      *reinterpret_cast<bf16x4*>(orow + g * D + c) = o4;
   }
-  if constexpr (OST) store_rows_sc1<D>(sm, out, out_stride, b, kvh, G);
+  if constexpr (OST) {
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < a.G * (D / 8))  // 16 B of row t / (D / 8): the rows are contiguous in sm.so and in out
+      store16_slab(reinterpret_cast<float*>(orow + 8 * t), *reinterpret_cast<const f32x4*>(&sm.so[0][0] + 8 * t));
+  }
+}
+
+// Ending A, a one-piece row: fold in the cascade-prefix partials [0, npre) written earlier on the stream and write
+// the final bf16 rows — no merge kernel, no partial round trip of this piece.
+// Phase 1: wave w owns heads w, w + 4: lanes load the prefix lse values in parallel, wave-reduce the max and the
+// weight sum, and publish per-slot weights in LDS. Phase 2: thread (g, 4 dims) sums weight x partial over the slots.
+template <int D, bool OST>
+__device__ __forceinline__ void merge_one_piece(DecodeSmem<D>& sm, const DecodeArgs& a, int b, int kvh, int64_t row0,
+                                                int npre) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int g = w; g < a.G; g += 4) {
+    float Ms, Ls;
+    combine_waves<f32x4>(sm, g, 0, Ms, Ls);
+    const float ls = Ls > 0.f ? Ms + log2f(Ls) : -INFINITY;
+    float lp = -INFINITY;
+    if (lane < npre) lp = a.lse_part[(row0 + g) * a.S_total + lane];
+    merge_weights(sm, g, npre + 1, lane < npre ? lp : (lane == npre ? ls : -INFINITY));
+  }
+  __syncthreads();
+  const int g = threadIdx.x >> 5, c = (threadIdx.x & 31) * 4;
+  f32x4 acc4 = {0.f, 0.f, 0.f, 0.f};
+  if (g < a.G) {
+    // this workgroup's own (normalised) result for dims c..c+3
+    float Ms, Ls;
+    const f32x4 os = combine_waves<f32x4>(sm, g, c, Ms, Ls);
+    if (Ls > 0.f) acc4 = os * (sm.sW[g][npre] / Ls);
+    const int64_t pbase = (row0 + g) * a.S_total * D + c;
+    if (a.pre_bf16 != nullptr)
+      fold_prefix_bf16<D>(acc4, a.pre_bf16 + pbase, sm.sW[g], npre);
+    else
+      fold_prefix_f32<D>(acc4, a.out_part + pbase, sm.sW[g], npre);
+  }
+  store_final_rows<D, OST>(sm, a, b, kvh, g, c, acc4);
+}
+
+// Ending B, a piece of a split row (S > 1, e.g. one long sequence spread over many workgroups), after its
+// write_partial<TICKET>: every piece has published its partial with agent-coherent write-through stores (another
+// XCD's workgroup may read it; a __threadfence release here would write back the whole L2 from every workgroup),
+// waits for them, takes a ticket, and the LAST of the S workgroups of (b, kvh) merges all npre + S partials
+// (agent-coherent loads) and writes the bf16 rows — no merge kernel launch. The last one also re-arms the counter
+// for the next launch.
+template <int D, bool OST>
+__device__ __forceinline__ void ticket_merge(DecodeSmem<D>& sm, const DecodeArgs& a, int b, int kvh, int64_t row0,
+                                             int S, int npre) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int* tk = a.tickets + b * a.Hkv + kvh;
+    const int t = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sm.s_last = t == S - 1;
+    if (t == S - 1) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (!sm.s_last) return;
+  const int n = npre + S;  // <= 64 (host-checked)
+  for (int g = w; g < a.G; g += 4) {
+    const float* lp = a.lse_part + (row0 + g) * a.S_total + lane;
+    merge_weights(sm, g, n,
+                  lane < n ? __hip_atomic_load(lp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -INFINITY);
+  }
+  __syncthreads();
+  const int g = threadIdx.x >> 5, c = (threadIdx.x & 31) * 4;
+  f32x4 acc4 = {0.f, 0.f, 0.f, 0.f};
+  if (g < a.G) {
+    // 16-B agent-coherent loads (sc1: not served from this XCD's possibly stale L2) as compiler builtins over a
+    // buffer of out_part, so hipcc's waitcnt pass tracks them (out_part < 2 GiB: host-checked)
+    const auto prs = buf_rsrc(a.out_part);
+    const int64_t pbase = (row0 + g) * a.S_total * D + c;
+    auto ld4 = [&](int s) { return load16_sc1(prs, (int)((pbase + s * D) * 4)); };
+    const int p0 = a.pre_bf16 != nullptr ? npre : 0;  // first fp32 slot (the pieces, or every slot)
+    // one round trip for the common row: the first PQ fp32 slots (agent-coherent loads) and DEC_MG bf16 prefix
+    // slots are all in flight before the first wait (not the prefix batch, then the pieces: two tail latencies)
+    constexpr int PQ = 8;
+    f32x4 pv[PQ];
+#pragma unroll
+    for (int j = 0; j < PQ; ++j) pv[j] = ld4(min(p0 + j, n - 1));
+    if (a.pre_bf16 != nullptr) fold_prefix_bf16<D>(acc4, a.pre_bf16 + pbase, sm.sW[g], npre);
+#pragma unroll
+    for (int j = 0; j < PQ; ++j)
+      if (p0 + j < n) acc4 += pv[j] * sm.sW[g][p0 + j];
+    // rows with more pieces: groups of 16 with all loads in flight (the tail of the kernel: latency, not bandwidth)
+    for (int s2 = p0 + PQ; s2 < n; s2 += 16) {
+      f32x4 v[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = ld4(min(s2 + j, n - 1));
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (s2 + j < n) acc4 += v[j] * sm.sW[g][s2 + j];
+    }
+  }
+  store_final_rows<D, OST>(sm, a, b, kvh, g, c, acc4);
+}
+
+// One decode piece: item `it` (keys [lo, hi) of row b, piece `split` of `nsplit`, behind `npre` prefix partials) for
+// kv head kvh. Every thread of the workgroup calls it with the same arguments (the stages synchronise the
+// workgroup); returns when the piece's partial or final rows are written.
+// bf16 pages: three workgroups per CU, Q in LDS, one K/V block per wave in flight (stream_keys).
+template <int D, bool FP8, bool OST>
+__device__ __forceinline__ void decode_piece(DecodeSmem<D>& sm, const DecodeArgs& a, const DecodeItem& it, int kvh) {
+  const int b = it.b;
+  const int* bt = a.block_tables + (int64_t)b * a.bt_stride;
+  const PieceBlocks pb(it.lo, it.hi);
+  stage_pages_q<D, !FP8>(sm, a, bt, pb, b, kvh);
+  WaveAcc<D> acc;
+  init_acc<D>(acc);
+  stream_keys<D, FP8>(sm, a, bt, pb, b, kvh, it.lo, it.hi, acc);
+  publish_wave_partials<D>(sm, acc, a.G);
+  const int64_t row0 = (int64_t)b * (a.Hkv * a.G) + kvh * a.G;  // head-row of the unit's first head
+  if (a.out == nullptr) {
+    write_partial<D, false>(sm, a, row0, it.npre + it.split);
+  } else if (it.nsplit == 1) {
+    merge_one_piece<D, OST>(sm, a, b, kvh, row0, it.npre);
+  } else {
+    write_partial<D, true>(sm, a, row0, it.npre + it.split);
+    ticket_merge<D, OST>(sm, a, b, kvh, row0, it.nsplit, it.npre);
+  }
 }
 
 // Prefill rows merged by the decode launch (grid rows past the decode items): a step whose new-turn rows rode in the
@@ -712,33 +737,19 @@ __device__ __forceinline__ void fused_merge_rows(const FusedMerge& fm, int m, in
 // grid (Hkv, items [+ merge workgroups]): the Hkv heads of an item are consecutive workgroups, dealt to different
 // XCDs, reading one page row together (heads-fast: +7 % over items-fast, three workgroups per CU +5 % over two,
 // profiles/r04/bench_ab_decode_placement_occ.jsonl)
-template <int D, bool FP8, bool OST = false>
-__global__ __launch_bounds__(256, FP8 ? 2 : 3) void attn_decode_kernel(const bf16* __restrict__ q, int64_t q_stride,
-                                                                      const void* __restrict__ k_cache,
-                                                                      const void* __restrict__ v_cache, int Hkv, int G,
-                                                                      const int* __restrict__ block_tables,
-                                                                      int bt_stride,
-                                                                      const DecodeItem* __restrict__ items, int B,
-                                                                      float* __restrict__ out_part,
-                                                                      float* __restrict__ lse_part, int S_total,
-                                                                      float scale_log2, bf16* __restrict__ out,
-                                                                      int64_t out_stride, int* __restrict__ tickets,
-                                                                      const bf16* __restrict__ pre_bf16, int n_items,
-                                                                      FusedMerge fm) {
+template <int D, bool FP8, bool OST>
+__global__ __launch_bounds__(256, FP8 ? 2 : 3) void attn_decode_kernel(DecodeArgs a, FusedMerge fm) {
   __shared__ DecodeSmem<D> sm;
-  if ((int)blockIdx.y >= n_items) {  // (workgroup-uniform)
-    fused_merge_rows(fm, blockIdx.y - n_items, blockIdx.x, G, Hkv * G);
+  if ((int)blockIdx.y >= a.n_items) {  // (workgroup-uniform)
+    fused_merge_rows(fm, blockIdx.y - a.n_items, blockIdx.x, a.G, a.Hkv * a.G);
     return;
   }
-  const DecodeItem it = items[blockIdx.y];
-  const int b = it.b, kvh = blockIdx.x, split = it.split, S = it.nsplit, split_offset = it.npre;
+  const DecodeItem it = a.items[blockIdx.y];
   // a malformed item (host bug) is dropped instead of indexing out of bounds (workgroup-uniform)
-  if (b < 0 || b >= B || split < 0 || split >= S || split_offset < 0 || split_offset + S > S_total ||
-      (out != nullptr && split_offset + S > 64))
+  if (it.b < 0 || it.b >= a.B || it.split < 0 || it.split >= it.nsplit || it.npre < 0 ||
+      it.npre + it.nsplit > a.S_total || (a.out != nullptr && it.npre + it.nsplit > 64))
     return;
-  decode_piece<D, FP8, OST>(sm, q, q_stride, k_cache, v_cache, Hkv, G, block_tables, bt_stride, b, kvh, it.lo, it.hi,
-                       split, S, split_offset, out_part, lse_part, S_total, scale_log2, out, out_stride, tickets,
-                       pre_bf16);
+  decode_piece<D, FP8, OST>(sm, a, it, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -790,11 +801,6 @@ __device__ __forceinline__ void stage_load(StageRegs<NT>& sr, const bf16* __rest
     const int vp = (qd >> 8) ? p1 : p0;
     sr.v[i] = asm_load16(v_cache + ((int64_t)vp * Hkv + kvh) * (D * PAGE) + (qd & 255) * 8);
   }
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // s_waitcnt vmcnt(n * L) for a wave-uniform runtime n in [0, MAXN] (the count must be an immediate)
@@ -1240,28 +1246,19 @@ extern "C" hipError_t kafka_launch_attn_decode(const bf16* q, int64_t q_stride, 
   if (D != 128 || G > 8 || G < 1) return hipErrorInvalidValue;
   if (out != nullptr && tickets == nullptr) return hipErrorInvalidValue;
   if (m_rows > 0 && (m_part == nullptr || m_lse == nullptr || m_out == nullptr || m_S < 1)) return hipErrorInvalidValue;
-  const float scale_log2 = scale * 1.4426950408889634f;
-  const auto* di = reinterpret_cast<const DecodeItem*>(items);
   const int rpw = (8 % G == 0) ? 8 / G : 1;
   const int n_mwg = m_rows > 0 ? (m_rows + rpw - 1) / rpw : 0;
   if (n_items + n_mwg > 65535) return hipErrorInvalidValue;
+  const DecodeArgs a{q, q_stride, k_cache, v_cache, Hkv, G, block_tables, bt_stride,
+                     reinterpret_cast<const DecodeItem*>(items), n_items, B, out_part, lse_part, S_total,
+                     scale * 1.4426950408889634f, out, out_stride, tickets, pre_bf16};
   const FusedMerge fm{m_part, m_lse, m_S, m_rows, m_out, m_out_stride};
-  const dim3 grid(Hkv, n_items + n_mwg);
-  // the bf16 rows as 16-B sc1 stores through LDS (decode_piece OST) when they are 16-B aligned
+  // the bf16 rows as 16-B sc1 stores through LDS (store_final_rows OST) when they are 16-B aligned; fp8 pages have
+  // the plain-store instantiation only
   const bool ost = out != nullptr && out_stride % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
-  if (ost && !fp8)
-    attn_decode_kernel<128, false, true><<<grid, 256, 0, st>>>(q, q_stride, k_cache, v_cache, Hkv, G, block_tables,
-                                                                bt_stride, di, B, out_part, lse_part, S_total,
-                                                                scale_log2, out, out_stride, tickets, pre_bf16,
-                                                                n_items, fm);
-  else if (fp8)
-    attn_decode_kernel<128, true><<<grid, 256, 0, st>>>(q, q_stride, k_cache, v_cache, Hkv, G, block_tables, bt_stride,
-                                                         di, B, out_part, lse_part, S_total, scale_log2, out,
-                                                         out_stride, tickets, pre_bf16, n_items, fm);
-  else
-    attn_decode_kernel<128, false><<<grid, 256, 0, st>>>(q, q_stride, k_cache, v_cache, Hkv, G, block_tables,
-                                                          bt_stride, di, B, out_part, lse_part, S_total, scale_log2,
-                                                          out, out_stride, tickets, pre_bf16, n_items, fm);
+  const auto kernel = fp8 ? attn_decode_kernel<128, true, false>
+                          : ost ? attn_decode_kernel<128, false, true> : attn_decode_kernel<128, false, false>;
+  kernel<<<dim3(Hkv, n_items + n_mwg), 256, 0, st>>>(a, fm);
   return hipGetLastError();
 }
 

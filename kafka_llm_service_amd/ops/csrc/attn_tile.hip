@@ -57,23 +57,8 @@ __device__ __forceinline__ void dma16(const void* g, char* lds) {
   __builtin_amdgcn_global_load_lds(g, (lds_void_t*)lds, 16, 0, AUX);
 }
 
-// max without fmaxf's NaN-quieting: IEEE-mode v_max_f32 needs each MFMA result canonicalised first (a v_max x, x
-// per value: 3 VALU ops per pair of scores); llvm.maximum lowers to gfx950's v_maximum3_f32, 3 inputs per op, no
-// canonicalisation (it propagates NaN instead of dropping it: a NaN score poisons its row either way)
-__device__ __forceinline__ float t3_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
-__device__ __forceinline__ float t3_xor32_max(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return t3_max(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float t3_xor32_sum(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
+// (vmax, xor32_max / xor32_sum and wait_vmcnt<N>: common.h)
 
-template <int N>
-__device__ __forceinline__ void t3_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // raw barrier, opaque to the compiler's memory model: no vmcnt(0) drain of the DMAs in flight (a __syncthreads()
 // would emit one), and no LDS access is moved across it
 __device__ __forceinline__ void t3_barrier() { asm volatile("s_barrier" ::: "memory"); }
@@ -91,11 +76,11 @@ __device__ __forceinline__ uint64_t t3_rt() {
 template <int DPT>
 __device__ __forceinline__ void t3_wait_tiles(int n) {
   if (n >= 2)
-    t3_wait_vmcnt<2 * DPT>();
+    wait_vmcnt<2 * DPT>();
   else if (n == 1)
-    t3_wait_vmcnt<DPT>();
+    wait_vmcnt<DPT>();
   else
-    t3_wait_vmcnt<0>();
+    wait_vmcnt<0>();
 }
 
 // ABL = 8 (diagnostic build, KAFKA_TILE_ABL=8, benchmarks/attn_tile_stamps.py): workgroup phase stamps on the 100 MHz
@@ -308,13 +293,13 @@ __global__ __launch_bounds__(512, 2) void attn_tile_kernel(const AttnWorkItem* _
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
       // two chains of v_maximum3_f32 (m = max3(m, a, b)): 16 VALU ops for the 32 scores of a lane
-      float ma = t3_max(s[rb][0][0], s[rb][1][0]), mb = t3_max(s[rb][0][1], s[rb][1][1]);
+      float ma = vmax(s[rb][0][0], s[rb][1][0]), mb = vmax(s[rb][0][1], s[rb][1][1]);
 #pragma unroll
       for (int i = 2; i < 16; i += 2) {
-        ma = t3_max(t3_max(ma, s[rb][0][i]), s[rb][1][i]);
-        mb = t3_max(t3_max(mb, s[rb][0][i + 1]), s[rb][1][i + 1]);
+        ma = vmax(vmax(ma, s[rb][0][i]), s[rb][1][i]);
+        mb = vmax(vmax(mb, s[rb][0][i + 1]), s[rb][1][i + 1]);
       }
-      smax[rb] = t3_xor32_max(t3_max(ma, mb)) * scale_log2;
+      smax[rb] = xor32_max(vmax(ma, mb)) * scale_log2;
     }
     bool need = false;
 #pragma unroll

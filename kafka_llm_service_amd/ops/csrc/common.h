@@ -37,6 +37,30 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Per-wave helpers of the attention kernels (attention.hip, attn_tile.hip).
+// max without fmaxf's NaN-quieting: IEEE-mode v_max_f32 needs each MFMA result canonicalised first (a v_max x, x
+// per value: 3 VALU ops per pair of scores); llvm.maximum lowers to gfx950's v_maximum3_f32, 3 inputs per op, no
+// canonicalisation (it propagates NaN instead of dropping it: a NaN score poisons its row either way)
+__device__ __forceinline__ float vmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// Reductions with the partner lane l ^ 32 on gfx950's v_permlane32_swap (one VALU op, no LDS crossbar round trip
+// through ds_bpermute — which also queued behind the K/V fragment reads): swapping a register with itself leaves
+// x[l] in one result and x[l ^ 32] in the other, so a symmetric op of the two is the xor-32 reduction on every lane.
+__device__ __forceinline__ float xor32_max(float x) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return vmax(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float xor32_sum(float x) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+// counted wait for this wave's vector-memory operations (the count is an immediate)
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// 2^e for an integer e in [-126, 127] (the fp8 KV cache's per-token exponents)
+__device__ __forceinline__ float exp2i(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+
 // Block-wide sum for blockDim.x == NT (multiple of 64). `red` must hold NT/64 floats.
 template <int NT>
 __device__ __forceinline__ float block_sum(float v, float* red) {

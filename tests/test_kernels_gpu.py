@@ -189,6 +189,44 @@ def test_attn_decode_merges_prefill_rows(cuda, Hkv, G, rows, S2):
     assert torch.isnan(out[B].float()).all() and torch.isnan(out[-1].float()).all(), "rows outside the merge range"
 
 
+@pytest.mark.parametrize("n_pre,S,pre_bf16", [(33, 1, False), (33, 1, True), (33, 2, False), (33, 2, True),
+                                              (7, 5, False)])
+def test_attn_decode_many_prefix_slots(cuda, n_pre, S, pre_bf16):
+    """The fused merges with more prefix partials than one load batch (attention.hip DEC_MG = 32: 33 slots are one
+    full batch plus a remainder), fp32 and bf16, on a one-piece row and on a split row (35 slots: the ticket merge's
+    groups past 24), and a split row of 12 slots (its first group of 16 only). The prefix partials are synthesised:
+    random rows and lse, one slot unwritten (lse -inf) with large finite data — the kernel multiplies that slot by its
+    zero weight, so a NaN there would reach the output. Expected rows: ops.reference on the CPU."""
+    torch.manual_seed(12)
+    Hkv, G, D, P = 2, 4, 128, 32
+    Hq = Hkv * G
+    lens = [P + 5, P + 70]
+    B = len(lens)
+    k, v, bt = _random_paged(B, lens, Hkv, cuda, seed=12)
+    q = torch.randn(B, Hq, D, device=cuda, dtype=torch.bfloat16)
+    scale = 1 / math.sqrt(D)
+    St = n_pre + S
+    part = torch.zeros(B, Hq, St, D)
+    lse = torch.full((B, Hq, St), float("-inf"))
+    part[:, :, :n_pre] = torch.randn(B, Hq, n_pre, D)
+    lse[:, :, :n_pre] = torch.randn(B, Hq, n_pre) * 4
+    part[:, :, n_pre // 2], lse[:, :, n_pre // 2] = 1e30, float("-inf")
+    pre = None
+    if pre_bf16:
+        pre = part.to(torch.bfloat16)
+        part[:, :, :n_pre] = float("nan")  # the fp32 prefix slots are not read
+    items = ops.uniform_decode_items(torch.tensor(lens, dtype=torch.int32), torch.full((B,), P, dtype=torch.int32), S,
+                                     n_pre)
+    o_ref = torch.empty(B, Hq, D)
+    ref.attn_decode_items(q.cpu(), k.cpu(), v.cpu(), bt.cpu(), items, part.clone(), lse.clone(), scale, out=o_ref,
+                          pre_part=pre)
+    part, lse, pre = part.to(cuda), lse.to(cuda), None if pre is None else pre.to(cuda)
+    for launch in range(2):  # the second launch finds the ticket counters re-armed
+        out = torch.full((B, Hq, D), float("nan"), device=cuda, dtype=torch.bfloat16)
+        ops.attn_decode_items(q, k, v, bt, items.to(cuda), part, lse, scale, out=out, pre_part=pre)
+        _close(out, o_ref, atol=0.02, msg=f"n_pre={n_pre} S={S} bf16 prefix={pre_bf16} launch {launch}")
+
+
 def test_attn_decode_multi_group_cascade(cuda):
     """Three prefix groups (different shared prefixes of 208 / 320 / 96 tokens) + two ungrouped rows, planned by the
     engine's own planner (model_runner.prefix_groups / decode_items, long suffixes split into pieces), run as

@@ -148,7 +148,7 @@ def test_ticket_merge_partials_reused_buffer(cuda, S):
 def test_norm_rope_attn_outputs_reused_buffers(cuda, T):
     """The layer chain's small kernels with their default 16-B sc1 stores, on ONE set of buffers rewritten six times
     (the engine's layer after layer): fused_add_rmsnorm (normalised rows + the in-place residual), rope_kv_write (q rows
-    and the K cache rows) and the decode kernel's final bf16 rows (through LDS, decode_piece OST). Between rounds torch
+    and the K cache rows) and the decode kernel's final bf16 rows (through LDS, store_final_rows OST). Between rounds torch
     and our decode GEMM (every XCD) read each buffer; every round is checked against fp32 references."""
     g = torch.Generator(device=cuda).manual_seed(11)
     d, Hq, Hkv, D = 4096, 32, 8, 128
