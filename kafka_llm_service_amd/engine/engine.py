@@ -447,7 +447,7 @@ class LLMEngine:
                 # the real one, gathered on the device)
                 del s.output_ids[idx:]
                 s.num_computed = s.total_len - 1
-                if s.params.presence_penalty or s.params.frequency_penalty:
+                if s.params.presence_penalty or s.params.frequency_penalty or s.params.repetition_penalty != 1.0:
                     self.runner.lp.uncount(s, t)  # the sampler counted it on the device
                 self.stats["grammar_rollbacks"] = self.stats.get("grammar_rollbacks", 0) + 1
                 continue

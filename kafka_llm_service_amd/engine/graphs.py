@@ -22,6 +22,7 @@ relies on — a replay reads ONLY the static buffers (tests/test_graphs.py).
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import logging
 from collections import OrderedDict
@@ -64,7 +65,9 @@ class DecodeGraphs:
         # MoE layers, so it is part of the layout
         cap = self.runner.model.ep_t_cap if getattr(self.runner.model, "dp_attention", False) else 0
         return (h.B, h.n_dec_items, h.s_total, h.n_prefix_items, bool(h.cascade_prefix), h.i64.size, h.i32.size,
-                h.n_late, h.late_off, sp.greedy, sp.proc is not None, cap)
+                h.n_late, h.late_off, sp.greedy, sp.proc is not None,
+                # (the sampler launch inside the graph is the one with or without the repetition-penalty table)
+                sp.proc is not None and self.runner.lp.live_rep_table() is not None, cap)
 
     def eligible(self, h, sp) -> bool:
         if sp.lp_rows is not None and self.runner.model.tp == 1:
@@ -188,7 +191,13 @@ class DecodeGraphs:
             ok = True
             try:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self.pool):
+                with contextlib.ExitStack() as cap:
+                    # the first live graph of a process makes torch create the default generator's graph-state
+                    # tensors when its capture begins; created inside the step's inference mode they are inference
+                    # tensors, and every capture begun outside inference mode while this engine's graphs live then
+                    # fails on their in-place fill. So the capture BEGINS outside it; the step itself runs as before
+                    with torch.inference_mode(False):
+                        cap.enter_context(torch.cuda.graph(g, pool=self.pool))
                     step()
                 e.graph = g
             except Exception:  # noqa: BLE001 - never let capture problems take the engine down

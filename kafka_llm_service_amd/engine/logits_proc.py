@@ -8,12 +8,19 @@ Q7 of SURVEY.md §2.9: accepted but never forwarded) and its agent loop decodes 
 
 Per step the host builds one int32 row per sampled sequence (``proc``, 8 ints):
     [0] mode  0 none | 1 bitmask row [1] of ``mask_tab`` | 2 forced token [1] (the kernel writes it, no draw)
-    [2] penalty slot: row of ``counts`` holding the sequence's generated-token counts (-1: no penalty)
+    [2] penalty slot: row of ``counts`` holding the sequence's generated-token counts, and of ``rep_tab`` (-1: no
+        penalty)
     [3] presence, [4] frequency penalty (fp32 bits)
     [5] row of ``bias_tab`` holding the request's ``logit_bias``, [6] its entry count (0: no bias)
     [7] ``min_p``: the fp32 bits of ``float32(ln(min_p))`` (``min_p_bits``; 0: off, min_p = 1 travels as -0.0)
-The kernel computes ``(x - freq * c - (c > 0 ? pres : 0)) + b`` in fp32 and applies the grammar mask after it: a
+The kernel computes ``(y - freq * c - (c > 0 ? pres : 0)) + b`` in fp32 and applies the grammar mask after it: a
 masked-out token stays -inf whatever its bias. The bias is stateless (nothing to undo on a rollback or a re-prefill).
+``repetition_penalty`` r != 1 comes first (vLLM's order): ``y = x`` unless the sequence has SEEN the token — it is in
+``seq.prompt_ids``, or it was drawn and not rolled back — then ``y = x * inv_r`` for ``x > 0`` and ``y = x * r``
+otherwise, with ``r = float32(r)`` and ``inv_r = float32(1) / float32(r)`` computed once here: the kernel multiplies and
+never divides, so ``y`` is within one fp32 ulp of HF's ``x / r``. A slot's factors are its row of ``rep_tab``; prompt
+membership is the flag ``COUNT_SEEN_PROMPT`` in the slot's count words, set when the slot is assigned (the generated
+count is the word's low 30 bits, "seen" is a non-zero word). Forced rows ignore it; greedy rows honour it.
 ``min_p`` acts on the processed row under temperature: token i is kept iff ``x_i / T >= max(x / T) + ln(min_p)`` (one
 fp32 add of the host's logarithm, so the kernel, its replay and the CPU reference share one threshold bit for bit),
 intersected with top-k / top-p; greedy and forced rows ignore it.
@@ -26,7 +33,8 @@ addresses (hipGraph-capturable), and so does the bias table:
     ``counts[slot][token]`` with every token it draws, so the next step (stream-ordered) sees it without the host;
   * ``bias_tab`` int32 [BIAS_ROWS, 2 * LOGIT_BIAS_MAX]: one row per distinct ``logit_bias`` object — the ids in
     strictly ascending order, then the fp32 bits of their biases — keyed by content and LRU-managed like the mask
-    rows: a thread sends the same object every turn, so after one 2.4 KB row upload it is a row index.
+    rows: a thread sends the same object every turn, so after one 2.4 KB row upload it is a row index;
+  * ``rep_tab`` fp32 [slots, 2]: ``(r, inv_r)`` of the slot's sequence, ``(1, 1)`` for a slot without the penalty.
 Table writes (new mask rows, slot zeroing, count decrements of rolled-back tokens) are ``ProcUpdates`` applied on the stream before the step's sampler — on
 every TP rank, from the same plan, so every rank samples the same token.
 """
@@ -39,7 +47,7 @@ import numpy as np
 import torch
 
 # (the update record travels in a step's wire format)
-from kafka_llm_service_amd.engine.step_plan import BIAS_ROW_INTS, LOGIT_BIAS_MAX, ProcUpdates
+from kafka_llm_service_amd.engine.step_plan import BIAS_ROW_INTS, COUNT_SEEN_PROMPT, LOGIT_BIAS_MAX, ProcUpdates
 
 MASK_ROWS = 512
 BIAS_ROWS = 512
@@ -70,6 +78,15 @@ def min_p_bits(min_p: float) -> int:
     return int((-np.float32(0.0) if lmp == 0 else lmp).view(np.int32))
 
 
+def rep_factors(r: float) -> np.ndarray:
+    """A slot's ``rep_tab`` row ``(float32(r), float32(1) / float32(r))``: the reciprocal is one fp32 division on the
+    host, and the kernel, its replay and the CPU reference multiply by it — within one fp32 ulp of ``x / r``."""
+    if isinstance(r, bool) or not 0.1 <= r <= 10.0:  # (a NaN fails both comparisons)
+        raise ValueError("repetition_penalty must lie in [0.1, 10]")
+    r32 = np.float32(r)
+    return np.array([r32, np.float32(1.0) / r32], dtype=np.float32)
+
+
 class LogitsProcessor:
     def __init__(self, device: torch.device, vocab: int, max_slots: int = 256, mask_rows: int = MASK_ROWS,
                  bias_rows: int = BIAS_ROWS):
@@ -83,13 +100,17 @@ class LogitsProcessor:
         self.mask_tab: torch.Tensor | None = None
         self.counts: torch.Tensor | None = None
         self.bias_tab: torch.Tensor | None = None
+        self.rep_tab: torch.Tensor | None = None
         self._rows: OrderedDict = OrderedDict()  # key -> mask row (LRU order)
         self._brows: OrderedDict = OrderedDict()  # ("B", ((id, bias), ...)) -> bias row (LRU order)
         self._slots: dict[int, tuple[int, object]] = {}  # seq_id -> (slot, seq)
         self._free: list[int] = list(range(max_slots - 1, -1, -1))
+        # slots whose rep_tab row holds r != 1, as apply() has written them: the same on every TP rank
+        self._rep_slots: set[int] = set()
+        self._rep_seqs: dict[int, object] = {}  # seq_id -> seq of the sequences build() has seeded a slot for
         self._dec: list[tuple[int, int]] = []  # (slot, token) decrements queued by uncount()
         self.stats = {"mask_uploads": 0, "proc_steps": 0, "forced_rows": 0, "mask_rows_used": 0, "penalty_rows": 0,
-                      "bias_uploads": 0, "bias_rows_used": 0, "min_p_rows": 0}
+                      "bias_uploads": 0, "bias_rows_used": 0, "min_p_rows": 0, "rep_rows": 0, "seen_uploads": 0}
 
     # ---- tables (allocated together on first use: a captured graph sees every address) --------------------------
     def tables(self) -> tuple[torch.Tensor, torch.Tensor]:
@@ -97,12 +118,24 @@ class LogitsProcessor:
             self.mask_tab = torch.zeros(self.n_mask_rows, self.W, dtype=torch.int32, device=self.device)
             self.counts = torch.zeros(self.max_slots, self.cnt_ld, dtype=torch.int32, device=self.device)
             self.bias_tab = torch.zeros(self.n_bias_rows, BIAS_ROW_INTS, dtype=torch.int32, device=self.device)
+            self.rep_tab = torch.ones(self.max_slots, 2, dtype=torch.float32, device=self.device)
         return self.mask_tab, self.counts
 
     def bias_table(self) -> torch.Tensor:
         """The logit-bias table (allocated with the other two)."""
         self.tables()
         return self.bias_tab
+
+    def rep_table(self) -> torch.Tensor:
+        """The repetition-penalty table (allocated with the other three)."""
+        self.tables()
+        return self.rep_tab
+
+    def live_rep_table(self) -> torch.Tensor | None:
+        """The table while some slot holds a factor r != 1, else None: the sampler is then launched without it and
+        runs the kernel that knows no repetition penalty (a step's updates are applied before its sampler, so the
+        answer is the step's, and every TP rank gives the same one)."""
+        return self.rep_table() if self._rep_slots else None
 
     # ---- host side ----------------------------------------------------------------------------------------------
     def _table_row(self, lru: OrderedDict, n_rows: int, key, words_fn, upd_rows: list, upd_words: list, used: set,
@@ -143,10 +176,11 @@ class LogitsProcessor:
         return self._table_row(self._brows, self.n_bias_rows, ("B", pairs), words, upd_rows, upd_words, used,
                                "bias_uploads")
 
-    def _slot(self, seq, zero: list) -> int:
+    def _slot(self, seq, zero: list) -> tuple[int, bool]:
+        """(the sequence's count-table slot, whether this call assigned it — such a slot joins ``zero``)."""
         e = self._slots.get(seq.seq_id)
         if e is not None:
-            return e[0]
+            return e[0], False
         if not self._free:  # reclaim the slots of sequences that have finished since
             for sid in [sid for sid, (_, s) in self._slots.items() if s.finished]:
                 self._free.append(self._slots.pop(sid)[0])
@@ -154,8 +188,20 @@ class LogitsProcessor:
             raise RuntimeError(f"logits processor: more than {self.max_slots} live penalised sequences")
         slot = self._free.pop()
         self._slots[seq.seq_id] = (slot, seq)
-        zero.append(slot)
-        return slot
+        if slot not in zero:  # (a slot _release_finished_rep freed in this very step is already there)
+            zero.append(slot)
+        return slot, True
+
+    def _release_finished_rep(self, zero: list) -> None:
+        """Frees the slots of finished sequences that had a repetition penalty and clears them with this step's
+        updates, so that ``live_rep_table`` turns None — on every rank — as soon as no such request is left, not only
+        when the slot is needed again."""
+        for sid in [sid for sid, s in self._rep_seqs.items() if s.finished]:
+            del self._rep_seqs[sid]
+            e = self._slots.pop(sid, None)
+            if e is not None:
+                self._free.append(e[0])
+                zero.append(e[0])
 
     def uncount(self, seq, token: int) -> None:
         """A drawn token the engine discarded (grammar rollback, engine.py ``_finish_step``): the sampler already
@@ -176,6 +222,9 @@ class LogitsProcessor:
         proc[:, 2] = -1
         upd_rows, upd_words, zero, used = [], [], [], set()
         b_rows, b_words, b_used = [], [], set()
+        seen = []  # (slot, (r, inv_r), ascending distinct prompt ids) of the slots this step seeds
+        if self._rep_seqs:
+            self._release_finished_rep(zero)
         V, W = self.V, self.W
         for i, s, spec in rows:
             p = s.params
@@ -209,10 +258,20 @@ class LogitsProcessor:
                         return pack_bits(keep, W)
                     proc[i, 0], proc[i, 1] = 1, self._mask_row(("L",) + ids, bits, upd_rows, upd_words, used)
                     self.stats["mask_rows_used"] += 1
-            if p.presence_penalty or p.frequency_penalty:
-                proc[i, 2] = self._slot(s, zero)
-                proc[i, 3:5] = np.array([p.presence_penalty, p.frequency_penalty], dtype=np.float32).view(np.int32)
-                self.stats["penalty_rows"] += 1
+            rep = p.repetition_penalty
+            if p.presence_penalty or p.frequency_penalty or rep != 1.0:
+                proc[i, 2], new_slot = self._slot(s, zero)
+                if p.presence_penalty or p.frequency_penalty:
+                    proc[i, 3:5] = np.array([p.presence_penalty, p.frequency_penalty], dtype=np.float32).view(np.int32)
+                    self.stats["penalty_rows"] += 1
+                if rep != 1.0:
+                    self.stats["rep_rows"] += 1
+                    if new_slot:  # its factors and its prompt's flags (a preempted or re-prefilled sequence keeps
+                        # its slot and is not seeded again)
+                        ids = np.unique(np.asarray(s.prompt_ids, dtype=np.int64))
+                        seen.append((int(proc[i, 2]), rep_factors(rep), ids[(ids >= 0) & (ids < V)].astype(np.int32)))
+                        self.stats["seen_uploads"] += 1
+                        self._rep_seqs[s.seq_id] = s
             bias = getattr(p, "logit_bias", None)
             if bias:
                 pairs = tuple(sorted((int(t), float(b)) for t, b in bias if float(b) != 0.0))
@@ -241,6 +300,11 @@ class LogitsProcessor:
         if b_rows:
             upd.bias_rows = np.asarray(b_rows, dtype=np.int32)
             upd.bias_words = np.stack(b_words)
+        if seen:
+            upd.seen_slots = np.asarray([sl for sl, _, _ in seen], dtype=np.int32)
+            upd.rep_vals = np.stack([f for _, f, _ in seen])
+            upd.seen_off = np.concatenate([[0], np.cumsum([ids.size for _, _, ids in seen])]).astype(np.int32)
+            upd.seen_ids = np.concatenate([ids for _, _, ids in seen]).astype(np.int32)
         return proc, upd
 
     # ---- device side ----------------------------------------------------------------------------------------------
@@ -269,4 +333,21 @@ class LogitsProcessor:
         if upd.zero_slots.size:
             if int(upd.zero_slots.max()) >= counts.shape[0]:
                 raise ValueError("logits processor: penalty slot outside the count table")
-            counts.index_fill_(0, upload(upd.zero_slots.astype(np.int64)), 0)
+            slots = upload(upd.zero_slots.astype(np.int64))
+            counts.index_fill_(0, slots, 0)
+            self.rep_table().index_fill_(0, slots, 1.0)  # a recycled slot inherits no factor: (1, 1) until seeded
+            self._rep_slots.difference_update(upd.zero_slots.tolist())
+        if upd.seen_slots.size:  # after the zeroing: the prompt's flags, then the slot's (r, inv_r)
+            upd.check_seen()
+            rep_tab = self.rep_table()
+            sl = upd.seen_slots.astype(np.int64)
+            if int(sl.min()) < 0 or int(sl.max()) >= min(counts.shape[0], rep_tab.shape[0]) \
+                    or (upd.seen_ids.size and (int(upd.seen_ids.min()) < 0 or int(upd.seen_ids.max()) >= self.V)) \
+                    or not np.isfinite(upd.rep_vals).all() or (upd.rep_vals <= 0).any():
+                raise ValueError("logits processor: repetition-penalty update does not fit the tables")
+            if upd.seen_ids.size:
+                flat = np.repeat(sl, np.diff(upd.seen_off)) * counts.shape[1] + upd.seen_ids
+                counts.view(-1).index_fill_(0, upload(flat), COUNT_SEEN_PROMPT)
+            rep_tab.index_copy_(0, upload(sl), upload(np.ascontiguousarray(upd.rep_vals, dtype=np.float32)))
+            self._rep_slots.difference_update(sl.tolist())
+            self._rep_slots.update(int(s) for s, r in zip(sl, upd.rep_vals[:, 0]) if r != 1.0)

@@ -366,8 +366,8 @@ class ModelRunner:
         return self.sample_device(logits, self.sample_params(seqs))
 
     def sample_params(self, seqs: list[Sequence]) -> "SampleParams":
-        """Per-row sampling parameters of a step; rows with a token constraint, penalties, a logit bias or min_p get a
-        logits-processing row (engine/logits_proc.py) that the sampler kernel applies on the device. A constrained row's spec is
+        """Per-row sampling parameters of a step; rows with a token constraint, penalties (presence, frequency,
+        repetition), a logit bias or min_p get a logits-processing row (engine/logits_proc.py) that the sampler kernel applies on the device. A constrained row's spec is
         computed from its landed tokens, or past a pending one when the grammar can guess its successor state
         (engine/constrained.py: a wrong guess rolls the row back one token); a forced token is returned in
         ``known`` so the engine writes it at launch."""
@@ -399,7 +399,7 @@ class ModelRunner:
                     known[i] = f
             # (min_p acts under temperature only: a greedy row needs no processing row for it)
             if allowed is not None or p.presence_penalty or p.frequency_penalty or p.logit_bias \
-                    or (p.min_p and p.temperature > 0):
+                    or (p.min_p and p.temperature > 0) or p.repetition_penalty != 1.0:
                 rows.append((i, s, allowed))
         proc = upd = None
         if rows:
@@ -429,7 +429,8 @@ class ModelRunner:
         if sp.proc is None:
             return {}
         mask_tab, counts = self.lp.tables()
-        return {"mask_tab": mask_tab, "counts": counts, "bias_tab": self.lp.bias_table()}
+        return {"mask_tab": mask_tab, "counts": counts, "bias_tab": self.lp.bias_table(),
+                "rep_tab": self.lp.live_rep_table()}
 
     def sample_device(self, logits: torch.Tensor, sp: "SampleParams") -> torch.Tensor:
         n = logits.shape[0]

@@ -49,8 +49,16 @@ class SamplingParams:
     # keep the tokens with p_i >= min_p * p_max (0: off), intersected with top-k / top-p; the sampler kernel tests
     # x_i / T >= max + ln(min_p) per token (engine/logits_proc.py proc[7]). Greedy and forced rows ignore it.
     min_p: float = 0.0
+    # multiplicative penalty of HF ``generate`` / vLLM over every token the sequence has SEEN — its prompt and the
+    # tokens generated so far — in [0.1, 10] (1: off): a seen logit x becomes x / r if x > 0 and x * r otherwise, before
+    # the additive penalties (engine/logits_proc.py, the sampler kernel's rep_tab). Forced rows ignore it.
+    repetition_penalty: float = 1.0
 
     def __post_init__(self):
+        if isinstance(self.repetition_penalty, bool) or not isinstance(self.repetition_penalty, (int, float)) \
+                or not 0.1 <= self.repetition_penalty <= 10.0:  # (a NaN fails both comparisons)
+            raise ValueError("repetition_penalty must be a number in [0.1, 10]")
+        self.repetition_penalty = float(self.repetition_penalty)
         if isinstance(self.min_p, bool) or not isinstance(self.min_p, (int, float)) \
                 or not 0.0 <= self.min_p <= 1.0:  # (a NaN fails both comparisons)
             raise ValueError("min_p must be a number in [0, 1]")

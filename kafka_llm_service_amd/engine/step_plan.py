@@ -29,6 +29,7 @@ MAX_PARTIALS = 64           # partial slots per row that the decode kernel's fus
 MAX_PREFIX_CHUNKS = 32
 LOGIT_BIAS_MAX = 300                # entries of one request's logit_bias (kafka_abi.h LOGIT_BIAS_MAX)
 BIAS_ROW_INTS = 2 * LOGIT_BIAS_MAX  # one row of the sampler's bias table: ids, then the fp32 bits of their biases
+COUNT_SEEN_PROMPT = 1 << 30         # flag of a prompt token in the sampler's count table (kafka_abi.h)
 
 
 def cdiv(a, b):
@@ -174,10 +175,26 @@ class ProcUpdates:
     # logit-bias rows: [k] rows of bias_tab and [k, 2 * LOGIT_BIAS_MAX] their words (ascending ids, then fp32 bits)
     bias_rows: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     bias_words: np.ndarray = field(default_factory=lambda: np.zeros((0, BIAS_ROW_INTS), np.int32))
+    # repetition penalty: [k] penalty slots newly given to a sequence with repetition_penalty != 1, [k, 2] fp32 their
+    # (r, 1 / r) rows of rep_tab, and the ascending distinct prompt ids of each (CSR: slot j owns
+    # seen_ids[seen_off[j]:seen_off[j + 1]], seen_off int32 [k + 1]; [0] without slots) whose count words get
+    # COUNT_SEEN_PROMPT
+    seen_slots: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    seen_off: np.ndarray = field(default_factory=lambda: np.zeros(1, np.int32))
+    seen_ids: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    rep_vals: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.float32))
 
     @property
     def empty(self) -> bool:
-        return not (self.mask_rows.size or self.zero_slots.size or self.dec.size or self.bias_rows.size)
+        return not (self.mask_rows.size or self.zero_slots.size or self.dec.size or self.bias_rows.size
+                    or self.seen_slots.size)
+
+    def check_seen(self) -> None:
+        """The repetition-penalty sections agree with each other (a plan on the wire, a table update)."""
+        k, off = self.seen_slots.size, self.seen_off
+        if off.shape != (k + 1,) or self.rep_vals.shape != (k, 2) or int(off[0]) != 0 \
+                or (np.diff(off) < 0).any() or int(off[-1]) != self.seen_ids.size:
+            raise ValueError("plan: repetition-penalty slots, offsets, ids and factors disagree")
 
 
 @dataclass
@@ -235,6 +252,10 @@ def pack_plan(h: HostStep, sp: SampleParams) -> tuple[np.ndarray, np.ndarray]:
              upd.bias_words.astype(np.int32, copy=False)]
     if upd.bias_rows.size and upd.bias_words.shape != (upd.bias_rows.size, BIAS_ROW_INTS):
         raise ValueError("plan: logit-bias update rows and words disagree")
+    upd.check_seen()
+    if upd.seen_slots.size:  # behind the bias rows: slots [k], offsets [k + 1], factors [k, 2] fp32, ids
+        parts += [upd.seen_slots.astype(np.int32, copy=False), upd.seen_off.astype(np.int32, copy=False),
+                  upd.rep_vals.astype(np.float32, copy=False), upd.seen_ids.astype(np.int32, copy=False)]
     payload = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in parts])
     hdr = np.zeros(PLAN_HDR, dtype=np.int64)
     hdr[0] = 1
@@ -244,6 +265,7 @@ def pack_plan(h: HostStep, sp: SampleParams) -> tuple[np.ndarray, np.ndarray]:
     hdr[1 + k:1 + k + 10] = [h.i64.size, i32.size, n, int(sp.greedy), payload.size, proc.shape[0],
                              upd.mask_rows.size, W, upd.zero_slots.size, upd.dec.shape[0]]
     hdr[1 + k + 10] = upd.bias_rows.size  # (0 and no bytes behind ``dec`` for a step without new bias rows)
+    hdr[1 + k + 11] = upd.seen_slots.size  # (likewise: 0 and no bytes without newly seeded repetition-penalty slots)
     return hdr, payload
 
 
@@ -252,6 +274,7 @@ def unpack_plan(hdr: np.ndarray, payload: np.ndarray) -> tuple[HostStep, SampleP
     h = HostStep(**{f: int(v) for f, v in zip(_PLAN_SCALARS, hdr[1:1 + k])})
     n64, n32, n, greedy, _, n_proc, n_mask, W, n_zero, n_dec = (int(v) for v in hdr[1 + k:1 + k + 10])
     n_bias = int(hdr[1 + k + 10])
+    n_seen = int(hdr[1 + k + 11])
     o = 0
 
     def take(dt, cnt):
@@ -271,6 +294,11 @@ def unpack_plan(hdr: np.ndarray, payload: np.ndarray) -> tuple[HostStep, SampleP
     upd = ProcUpdates(take(np.int32, n_mask), take(np.int32, n_mask * W).reshape(n_mask, W),
                       take(np.int32, n_zero), take(np.int32, 2 * n_dec).reshape(n_dec, 2), take(np.int32, n_bias),
                       take(np.int32, n_bias * BIAS_ROW_INTS).reshape(n_bias, BIAS_ROW_INTS))
+    if n_seen:
+        upd.seen_slots, upd.seen_off = take(np.int32, n_seen), take(np.int32, n_seen + 1)
+        upd.rep_vals = take(np.float32, 2 * n_seen).reshape(n_seen, 2)
+        upd.seen_ids = take(np.int32, max(0, int(upd.seen_off[-1])))
+        upd.check_seen()
     sp.proc = proc if n_proc else None
     sp.upd = None if upd.empty else upd
     return h, sp

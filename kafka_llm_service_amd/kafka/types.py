@@ -6,7 +6,9 @@ final usage chunk like the OpenAI API; ``tool_choice`` / ``tools`` are accepted 
 ``tool_choice`` steers constrained decoding); ``logprobs`` / ``top_logprobs`` (0..20, only with ``logprobs: true``)
 return per-token log-probabilities of the model's raw logits; ``logit_bias`` maps token ids (JSON string keys) to
 biases in [-100, 100], at most 300 of them, added to the logits inside the sampler. Two fields go beyond the OpenAI
-schema: ``min_p`` in [0, 1] and ``top_k`` >= 0 (0 turns either off), the sampler's other two truncation rules.
+schema: ``min_p`` in [0, 1] and ``top_k`` >= 0 (0 turns either off), the sampler's other two truncation rules, and
+``repetition_penalty`` in [0.1, 10] (1 or absent: off), the multiplicative penalty of HF ``generate`` / vLLM over the
+tokens of the prompt and of the output so far.
 """
 from __future__ import annotations
 
@@ -54,6 +56,15 @@ class ChatCompletionRequest(BaseModel):
     # at least min_p times the most likely token's (0: off); ``top_k`` keeps the k most likely tokens (0: off)
     min_p: Optional[float] = Field(None, ge=0, le=1)
     top_k: Optional[int] = Field(None, ge=0)
+    # a logit x of a token the prompt or the output so far holds becomes x / r (x > 0) or x * r (x <= 0); 1: off
+    repetition_penalty: Optional[float] = Field(None, ge=0.1, le=10)
+
+    @field_validator("repetition_penalty", mode="before")
+    @classmethod
+    def _repetition_penalty_is_a_number(cls, v):
+        if isinstance(v, (bool, str)):  # (pydantic would read true as 1.0 and "2" as 2.0)
+            raise ValueError("repetition_penalty must be a number in [0.1, 10]")
+        return v
 
     @field_validator("logit_bias")
     @classmethod

@@ -153,6 +153,7 @@ class EngineLLMProvider(LLMProvider):
                                 tool_choice: Any = None, logprobs: bool | None = None,
                                 top_logprobs: int | None = None, logit_bias: dict | None = None,
                                 min_p: float | None = None, top_k: int | None = None,
+                                repetition_penalty: float | None = None,
                                 **kwargs: Any) -> AsyncGenerator[StreamChunk, None]:
         """``logprobs`` / ``top_logprobs``: every non-special token the provider consumes yields one OpenAI entry
         ({token, logprob, bytes, top_logprobs}) over the model's RAW logits; a content chunk carries the entries of
@@ -165,7 +166,10 @@ class EngineLLMProvider(LLMProvider):
         the model's vocabulary is refused before anything is submitted.
 
         ``min_p`` / ``top_k`` (extensions beyond the OpenAI schema; None or 0: off): the sampler's truncation rules
-        next to ``top_p`` — keep the tokens with p >= min_p * p_max, keep the k most likely — intersected."""
+        next to ``top_p`` — keep the tokens with p >= min_p * p_max, keep the k most likely — intersected.
+
+        ``repetition_penalty`` (an extension too; None or 1: off): in [0.1, 10], multiplies the logits of the tokens
+        the rendered prompt or the output so far holds (x / r if x > 0, else x * r) before the other penalties."""
         self.validate_messages(messages)
         bias = None
         if logit_bias:
@@ -190,6 +194,7 @@ class EngineLLMProvider(LLMProvider):
         params = SamplingParams(temperature=0.7 if temperature is None else float(temperature),
                                 top_p=1.0 if not top_p else float(top_p), max_tokens=max_new,
                                 min_p=float(min_p or 0.0), top_k=int(top_k or 0),
+                                repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
                                 frequency_penalty=float(frequency_penalty or 0.0),
                                 presence_penalty=float(presence_penalty or 0.0), seed=seed,
                                 ignore_eos=self.ignore_eos, logprobs=bool(logprobs),

@@ -65,6 +65,8 @@ class RemoteOpenAIProvider(LLMProvider):
         for k in ("min_p", "top_k"):  # extensions beyond the OpenAI schema: sent only when set (0 is "off")
             if kw.get(k):
                 body[k] = kw[k]
+        if kw.get("repetition_penalty") not in (None, 1, 1.0):  # (1 is "off")
+            body["repetition_penalty"] = kw["repetition_penalty"]
         return body
 
     async def stream_completion(self, messages: list[Message], *, temperature: Optional[float] = None,

@@ -203,11 +203,17 @@ LOGIT_BIAS_MAX = ref.LOGIT_BIAS_MAX  # entries of one request's logit_bias; a bi
 
 
 def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
-           mask_tab=None, counts=None, bias_tab=None) -> torch.Tensor:
+           mask_tab=None, counts=None, bias_tab=None, rep_tab=None) -> torch.Tensor:
     """Sampled ids [B] (int64). ``proc`` int32 [B, 8] turns on the per-row logits processing of the kernel (grammar
     bitmask rows of ``mask_tab``, forced ids, presence / frequency penalties from ``counts``, which the sampler
     updates with every drawn token, sparse logit biases from rows of ``bias_tab``; engine/logits_proc.py builds all
-    four). A ``proc`` row that names bias entries without a ``bias_tab`` is an error."""
+    four). A ``proc`` row that names bias entries without a ``bias_tab`` is an error. ``rep_tab`` fp32 [slots, 2] holds
+    the penalty slots' repetition penalties (r, 1 / r): a row whose slot has r != 1 multiplies the logits of its seen
+    tokens (count word != 0; a prompt token carries COUNT_SEEN_PROMPT) by 1 / r if positive, else by r, first of all.
+    Flags belong to slots whose ``rep_tab`` row has r != 1 and to no others: for a row without such a factor (or
+    without ``rep_tab``) the kernel reads the whole count word as a count, so a flagged word there is a count of 2^30
+    (engine/logits_proc.py sets and clears the two together). Passing ``rep_tab`` selects the kernel instantiation
+    that knows the penalty; the engine passes it only while some slot holds a factor."""
     B = logits.shape[0]
     if out is None:
         out = torch.empty(B, dtype=torch.long, device=logits.device)
@@ -218,9 +224,9 @@ def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=No
         nsplit = _SAMPLE_SPLIT if V >= 16384 else 1  # a row over 8 workgroups (greedy / plain temperature)
         ws = _sample_ws(logits.device, 65536 + 2 * B * nsplit) if nsplit > 1 else None
         ext().sample(logits, temperature, top_p, top_k, seeds, step, out, ws, nsplit, proc, mask_tab, counts,
-                     bias_tab)
+                     bias_tab, rep_tab)
     else:
-        ref.sample(logits, temperature, top_p, top_k, seeds, step, out, proc, mask_tab, counts, bias_tab)
+        ref.sample(logits, temperature, top_p, top_k, seeds, step, out, proc, mask_tab, counts, bias_tab, rep_tab)
     return out
 
 

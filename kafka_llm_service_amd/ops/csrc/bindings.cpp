@@ -319,7 +319,7 @@ static void sample(at::Tensor logits, c10::optional<at::Tensor> temperature, c10
                    c10::optional<at::Tensor> top_k, c10::optional<at::Tensor> seeds, c10::optional<at::Tensor> step,
                    at::Tensor out, c10::optional<at::Tensor> ws, int64_t nsplit, c10::optional<at::Tensor> proc,
                    c10::optional<at::Tensor> mask_tab, c10::optional<at::Tensor> counts,
-                   c10::optional<at::Tensor> bias_tab) {
+                   c10::optional<at::Tensor> bias_tab, c10::optional<at::Tensor> rep_tab) {
   CHECK_CUDA(logits); CHECK_DT(out, at::kLong);
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [B, V]");
   const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
@@ -352,6 +352,7 @@ static void sample(at::Tensor logits, c10::optional<at::Tensor> temperature, c10
   const uint32_t* mt = nullptr;
   int* cp = nullptr;
   const int* bt = nullptr;
+  const float* rt = nullptr;
   int64_t mld = 0, cld = 0, bld = 0;
   if (proc.has_value()) {
     TORCH_CHECK(proc->is_cuda() && proc->scalar_type() == at::kInt && proc->is_contiguous() && proc->dim() == 2 &&
@@ -377,12 +378,20 @@ static void sample(at::Tensor logits, c10::optional<at::Tensor> temperature, c10
       bt = bias_tab->data_ptr<int>();
       bld = bias_tab->size(1);
     }
+    // repetition penalties (r, 1 / r) per penalty slot: the kernel reads row proc[2], so one row per row of counts
+    if (rep_tab.has_value()) {
+      TORCH_CHECK(counts.has_value() && rep_tab->is_cuda() && rep_tab->scalar_type() == at::kFloat &&
+                      rep_tab->is_contiguous() && rep_tab->dim() == 2 && rep_tab->size(1) == 2 &&
+                      rep_tab->size(0) >= counts->size(0),
+                  "sample: rep_tab must be fp32 [>= slots of counts, 2] on the GPU, given with counts");
+      rt = rep_tab->data_ptr<float>();
+    }
   }
   CHECK_HIP(kafka_launch_sample(logits.data_ptr(), is_bf16, logits.stride(0), B, V,
                                  (const float*)fp(temperature, at::kFloat), (const float*)fp(top_p, at::kFloat),
                                  (const int*)fp(top_k, at::kInt), (const int64_t*)fp(seeds, at::kLong),
                                  (const int64_t*)st, out.data_ptr<int64_t>(), wp, wp ? (int)nsplit : 1, pp, mt, mld,
-                                 cp, cld, bt, bld, cur_stream()));
+                                 cp, cld, bt, bld, rt, cur_stream()));
 }
 
 // Per-token logprobs (logprobs.hip). rows: int32 [R] or none (rows 0..R-1); tok_lp f32 [R], top_lp f32 [R, K] and
@@ -1010,7 +1019,7 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"), py::arg("top_p"), py::arg("top_k"),
         py::arg("seeds"), py::arg("step"), py::arg("out"), py::arg("ws") = py::none(), py::arg("nsplit") = 1,
         py::arg("proc") = py::none(), py::arg("mask_tab") = py::none(), py::arg("counts") = py::none(),
-        py::arg("bias_tab") = py::none());
+        py::arg("bias_tab") = py::none(), py::arg("rep_tab") = py::none());
   m.def("token_logprobs", &token_logprobs, py::arg("logits"), py::arg("tokens"), py::arg("rows"), py::arg("k"),
         py::arg("tok_lp"), py::arg("top_lp"), py::arg("top_id"), py::arg("ws") = py::none(), py::arg("nsplit") = 1);
   m.def("wstream_plan", &wstream_plan);

@@ -55,6 +55,12 @@ static_assert(sizeof(DecodeItem) == ITEM_INTS * sizeof(int), "DecodeItem is one 
 // bits of their biases at [LOGIT_BIAS_MAX, LOGIT_BIAS_MAX + n); proc[5] names the row, proc[6] is n (0: no bias)
 constexpr int LOGIT_BIAS_MAX = 300;  // OpenAI's bound on the entries of one request's logit_bias
 
+// ---- sampler count table (sampling.hip RowProc; engine/logits_proc.py) --------------------------------------------
+// counts[slot][token]: the generated-token count in the low 30 bits (presence / frequency penalties) and this flag
+// where the slot's sequence holds the token in its prompt (seeded by the host for repetition-penalty slots only). A
+// token is "seen" by the repetition penalty when the word is non-zero.
+constexpr int COUNT_SEEN_PROMPT = 1 << 30;
+
 // ---- weight tile formats of the streaming GEMMs (wstream_gemm.hip WFMT; ops.WEIGHT_FORMATS) ----------------------
 // bf16 tiles [N/32][K/16][64 lanes][8]; fp8: e4m3 bytes [N/32][K/32][64][16] + fp32 row scales [N]; MXFP4: e2m1 bytes
 // [N/32][K/64][64][16] + e8m0 block exponents [N/32][K/64][32][2]
@@ -153,11 +159,13 @@ hipError_t kafka_launch_attn_tile(const void* items, int n_items, const bf16* q,
 // [rows, bias_ld], bias_ld >= 2 * LOGIT_BIAS_MAX and a multiple of 4) likewise — without it no row is biased.
 // proc[7] carries min_p as the fp32 bits of float32(ln(min_p)) (0: off, min_p = 1 is -0.0): a row under temperature
 // keeps the tokens with x / T >= max(x / T) + that value. The same workspace serves min_p rows (two ints per split).
+// rep_tab (optional, fp32 [slots, 2] with the rows of counts): (r, 1 / r) of each penalty slot's repetition penalty;
+// a row with r != 1 multiplies its seen tokens' logits (counts word != 0) before the other penalties.
 hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int64_t stride, int B, int V, const float* temperature,
                                const float* top_p, const int* top_k, const int64_t* seeds, const int64_t* step,
                                int64_t* out_tokens, int* ws, int nsplit, const int* proc, const uint32_t* mask_tab,
                                int64_t mask_ld, int* counts, int64_t cnt_ld, const int* bias_tab, int64_t bias_ld,
-                               hipStream_t st);
+                               const float* rep_tab, hipStream_t st);
 
 // ---- logprobs.hip
 // Log softmax of the RAW logits (no temperature / penalties / mask) at each scored row's sampled token, and the row's

@@ -98,17 +98,25 @@ __device__ __forceinline__ float gumbel_fast(uint64_t key, uint32_t idx) {
 
 // Per-row logits processing on the device (PROC instantiation; VERDICT r03 "Next round" #3): proc[row] = int32 x 8
 //   [0] mode: 0 = none, 1 = vocab bitmask (row [1] of mask_tab), 2 = forced token ([1] is the id: no draw at all)
-//   [2] penalty slot: row of counts[slot][V] (the row's generated-token counts, -1 = none)
+//   [2] penalty slot: row of counts[slot][V] (the row's generated-token counts, -1 = none) and of rep_tab
 //   [3] presence penalty, [4] frequency penalty (fp32 bits)
 //   [5] logit-bias row of bias_tab, [6] its entry count (0 = no bias; clamped to LOGIT_BIAS_MAX)
 //   [7] min_p: the fp32 bits of lmp = float32(ln(min_p)), the host's logarithm (0 = off; min_p = 1 is -0.0). Under
 //       temperature token i is kept iff x_i / T >= max(x / T) + lmp — one fp32 add, so every token is tested on its own
 //       once the maximum is known — intersected with top-k / top-p; greedy and forced rows ignore it.
-// The logit of token i becomes  (x_i - freq * c_i - (c_i > 0 ? pres : 0)) + b_i  (OpenAI presence / frequency
+// The logit of token i becomes  (y_i - freq * c_i - (c_i > 0 ? pres : 0)) + b_i  (OpenAI presence / frequency
 // penalties, then the request's logit_bias, before temperature), or -inf where the grammar mask has a zero bit; the
 // sampler then runs unchanged over it, and the thread that writes the row's token also bumps counts[slot][token] —
 // the next step (stream-ordered) sees it, so penalties need no landed tokens on the host and no per-row torch ops
 // over the [B, V] logits.
+// Repetition penalty (rep_tab fp32 [slots, 2] = (r, 1 / r), both rounded on the host; a null table or r == 1: none):
+// y_i = x_i unless token i is SEEN by the row's sequence, then x_i * (1 / r) for x_i > 0 and x_i * r otherwise — one
+// fp32 multiply rounded on its own (__fmul_rn: no fma with the subtraction that follows), never a division. Seen is
+// counts[slot][i] != 0: the word holds the generated count in its low 30 bits (c_i above, what presence and frequency
+// use) and COUNT_SEEN_PROMPT where the host seeded a prompt token of the slot's sequence, so the multiply rides on the
+// load the penalties already make. emit_token's += 1 leaves the flag alone. The host sets flags and a factor r != 1
+// together and clears both when a slot is recycled, so a row without a factor holds plain counts and runs the code it
+// ran before the flag existed.
 // The bias is sparse: a row of bias_tab holds n <= LOGIT_BIAS_MAX ascending ids and their biases (kafka_abi.h). A
 // workgroup stages its row's pairs in LDS once; every 16-byte logit load then finds the first id >= its index by
 // binary search there (<= 9 LDS reads) and adds the few biases that fall into its 8 indices: no dense [slots, V]
@@ -122,12 +130,15 @@ struct RowProc {
   const int* bias;  // the row of bias_tab they come from
   bool minp;        // proc[7] != 0
   float lmp;        // ln(min_p) <= 0 (0 when off)
+  bool rep;         // the slot's rep_tab row holds r != 1
+  float r, inv_r;   // repetition penalty and its host-rounded reciprocal
 };
 
 template <bool PROC>
 __device__ __forceinline__ RowProc row_proc(const int* proc, const uint32_t* mask_tab, int64_t mask_ld, int* counts,
-                                            int64_t cnt_ld, const int* bias_tab, int64_t bias_ld, int row) {
-  RowProc r{0, -1, -1, 0.f, 0.f, nullptr, nullptr, 0, nullptr, false, 0.f};
+                                            int64_t cnt_ld, const int* bias_tab, int64_t bias_ld,
+                                            const float* rep_tab, int row) {
+  RowProc r{0, -1, -1, 0.f, 0.f, nullptr, nullptr, 0, nullptr, false, 0.f, false, 1.f, 1.f};
   if constexpr (PROC) {
     const int* p = proc + (int64_t)row * 8;
     r.minp = p[7] != 0;
@@ -139,6 +150,11 @@ __device__ __forceinline__ RowProc row_proc(const int* proc, const uint32_t* mas
     r.freq = __int_as_float(p[4]);
     if (r.mode == 1) r.mask = mask_tab + (int64_t)r.arg * mask_ld;
     if (r.slot >= 0) r.cnt = counts + (int64_t)r.slot * cnt_ld;
+    if (rep_tab != nullptr && r.cnt != nullptr) {
+      r.r = rep_tab[2 * r.slot];
+      r.inv_r = rep_tab[2 * r.slot + 1];
+      r.rep = r.r != 1.f;
+    }
     if (bias_tab != nullptr && p[6] > 0) {
       r.nb = min(p[6], LOGIT_BIAS_MAX);
       r.bias = bias_tab + (int64_t)p[5] * bias_ld;
@@ -167,7 +183,7 @@ __device__ __forceinline__ int bias_lower_bound(const int* sb, int nb, int i) {
 }
 
 // 8 logits starting at index i0 (a multiple of 8), processed
-template <typename T, bool PROC>
+template <typename T, bool PROC, bool REP = false>
 __device__ __forceinline__ void load8p(const T* x, int i0, const RowProc& rp, float (&v)[8]) {
   Vec8<T>::load(x + i0, v);
   if constexpr (PROC) {
@@ -175,8 +191,17 @@ __device__ __forceinline__ void load8p(const T* x, int i0, const RowProc& rp, fl
       const int4 c0 = *reinterpret_cast<const int4*>(rp.cnt + i0);
       const int4 c1 = *reinterpret_cast<const int4*>(rp.cnt + i0 + 4);
       const int c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+      if constexpr (REP) {  // (only such a slot holds flags: the other rows keep the code they had)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] -= rp.freq * (float)c[j] + (c[j] > 0 ? rp.pres : 0.f);
+        for (int j = 0; j < 8; ++j) {
+          const int g = c[j] & (COUNT_SEEN_PROMPT - 1);
+          if (c[j] != 0) v[j] = __fmul_rn(v[j], v[j] > 0.f ? rp.inv_r : rp.r);
+          v[j] -= rp.freq * (float)g + (g > 0 ? rp.pres : 0.f);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] -= rp.freq * (float)c[j] + (c[j] > 0 ? rp.pres : 0.f);
+      }
     }
     if (rp.nb > 0) {
       const int* sb = bias_lds<PROC>();
@@ -198,13 +223,19 @@ __device__ __forceinline__ void load8p(const T* x, int i0, const RowProc& rp, fl
   }
 }
 
-template <typename T, bool PROC>
+template <typename T, bool PROC, bool REP = false>
 __device__ __forceinline__ float load1p(const T* x, int i, const RowProc& rp) {
   float v = (float)x[i];
   if constexpr (PROC) {
     if (rp.cnt != nullptr) {
       const int c = rp.cnt[i];
-      v -= rp.freq * (float)c + (c > 0 ? rp.pres : 0.f);
+      if constexpr (REP) {
+        const int g = c & (COUNT_SEEN_PROMPT - 1);
+        if (c != 0) v = __fmul_rn(v, v > 0.f ? rp.inv_r : rp.r);
+        v -= rp.freq * (float)g + (g > 0 ? rp.pres : 0.f);
+      } else {
+        v -= rp.freq * (float)c + (c > 0 ? rp.pres : 0.f);
+      }
     }
     if (rp.nb > 0) {
       const int* sb = bias_lds<PROC>();
@@ -225,6 +256,19 @@ __device__ __forceinline__ void emit_token(int64_t* out_tokens, int row, int tok
   }
 }
 
+// the split's LDS, outside the template so that a kernel with two row bodies holds it once
+struct MinPLds {
+  float* pm;
+  int *pw, *pflag, *last;
+};
+__device__ __forceinline__ MinPLds min_p_lds() {
+  __shared__ float pm[64];
+  __shared__ int pw[64];
+  __shared__ int pflag[64];
+  __shared__ int s_last;
+  return MinPLds{pm, pw, pflag, &s_last};
+}
+
 // min_p alone (T > 0, no effective top-k / top-p; PROC rows only): the kept set {xv >= max + lmp} needs the row maximum
 // and nothing else, so the row stays on the plain stream (gumbel_fast, the plain rows' key: the token does not depend
 // on nsplit) and stays split. A split reads its slice twice: the slice maximum m_s, then the argmax of xv + noise over
@@ -234,14 +278,14 @@ __device__ __forceinline__ void emit_token(int64_t* out_tokens, int row, int tok
 // (key, index, logit), recomputed here). A slice below thr gives nothing; a slice at or above thr whose winner fell
 // below it is rescanned with thr by the whole workgroup (one slice of V / nsplit; rare on a peaked row, common on flat
 // random logits, where most of a slice's mass lies between the two thresholds).
-template <typename T>
+template <typename T, bool REP>
 __device__ __forceinline__ void sample_min_p_split(const T* x, int V, const RowProc& rp, float inv_t, uint64_t key,
                                                    int row, int sp, int nsplit, int* ws, int64_t* out_tokens,
                                                    float* sv, int* si, float* red) {
-  __shared__ float pm[64];  // per slice (nsplit <= 64): maximum, winner, "rescan"
-  __shared__ int pw[64];
-  __shared__ int pflag[64];
-  __shared__ int s_last;
+  const MinPLds lds = min_p_lds();  // per slice (nsplit <= 64): maximum, winner, "rescan"
+  float* pm = lds.pm;
+  int *pw = lds.pw, *pflag = lds.pflag;
+  int& s_last = *lds.last;
   const int nvec = V >> 3, tail0 = nvec << 3;
   const int per = (nvec + nsplit - 1) / nsplit;
   // best of xv + noise over slice k's tokens with xv >= thr (the last slice owns the scalar tail)
@@ -249,7 +293,7 @@ __device__ __forceinline__ void sample_min_p_split(const T* x, int V, const RowP
     const int v0 = k * per, v1 = min(nvec, v0 + per);
     for (int vi = v0 + threadIdx.x; vi < v1; vi += SNT) {
       float v[8];
-      load8p<T, true>(x, vi * 8, rp, v);
+      load8p<T, true, REP>(x, vi * 8, rp, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float xv = v[j] * inv_t;
@@ -258,7 +302,7 @@ __device__ __forceinline__ void sample_min_p_split(const T* x, int V, const RowP
     }
     if (k == nsplit - 1)
       for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
-        const float xv = load1p<T, true>(x, i, rp) * inv_t;
+        const float xv = load1p<T, true, REP>(x, i, rp) * inv_t;
         if (xv >= thr) a = better(a, ArgMax{xv + gumbel_fast(key, i), i});
       }
     return a;
@@ -268,12 +312,12 @@ __device__ __forceinline__ void sample_min_p_split(const T* x, int V, const RowP
     const int v0 = sp * per, v1 = min(nvec, v0 + per);
     for (int vi = v0 + threadIdx.x; vi < v1; vi += SNT) {
       float v[8];
-      load8p<T, true>(x, vi * 8, rp, v);
+      load8p<T, true, REP>(x, vi * 8, rp, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) m = fmaxf(m, v[j] * inv_t);
     }
     if (sp == nsplit - 1)
-      for (int i = tail0 + threadIdx.x; i < V; i += SNT) m = fmaxf(m, load1p<T, true>(x, i, rp) * inv_t);
+      for (int i = tail0 + threadIdx.x; i < V; i += SNT) m = fmaxf(m, load1p<T, true, REP>(x, i, rp) * inv_t);
   }
   m = block_max<SNT>(m, red);
   ArgMax a = block_argmax(scan(sp, m + rp.lmp, ArgMax{-INFINITY, 0x7fffffff}), sv, si);
@@ -309,7 +353,7 @@ __device__ __forceinline__ void sample_min_p_split(const T* x, int V, const RowP
     const int w = pw[threadIdx.x];
     int flag = 0;
     if (pm[threadIdx.x] >= thr && w >= 0 && w < V) {
-      const float xv = load1p<T, true>(x, w, rp) * inv_t;
+      const float xv = load1p<T, true, REP>(x, w, rp) * inv_t;
       if (xv >= thr) r = ArgMax{xv + gumbel_fast(key, w), w}; else flag = 1;
     }
     pflag[threadIdx.x] = flag;
@@ -321,36 +365,14 @@ __device__ __forceinline__ void sample_min_p_split(const T* x, int V, const RowP
   if (threadIdx.x == 0) emit_token<true>(out_tokens, row, r.i, V, rp);
 }
 
-template <typename T, bool PROC>
-__global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logits, int64_t stride, int V,
-                                                      const float* __restrict__ temperature,
-                                                      const float* __restrict__ top_p, const int* __restrict__ top_k,
-                                                      const int64_t* __restrict__ seeds, const int64_t* __restrict__ step_ptr,
-                                                      int64_t* __restrict__ out_tokens, int max_rounds,
-                                                      int* __restrict__ ws, const int* __restrict__ proc,
-                                                      const uint32_t* __restrict__ mask_tab, int64_t mask_ld,
-                                                      int* __restrict__ counts, int64_t cnt_ld,
-                                                      const int* __restrict__ bias_tab, int64_t bias_ld) {
-  __shared__ float sv[SNT / 64];
-  __shared__ int si[SNT / 64];
-  __shared__ float red[SNT / 64];
-  const int row = blockIdx.x, sp = blockIdx.y, nsplit = gridDim.y;
-  const T* x = logits + (int64_t)row * stride;
-  const RowProc rp = row_proc<PROC>(proc, mask_tab, mask_ld, counts, cnt_ld, bias_tab, bias_ld, row);
-  if (PROC && rp.mode == 2) {  // forced token (a fixed piece of a tool-call grammar): every split returns, no ticket
-    if (sp == 0 && threadIdx.x == 0) emit_token<PROC>(out_tokens, row, rp.arg, V, rp);
-    return;
-  }
-  if constexpr (PROC) {
-    if (rp.nb > 0) {  // rp is the row's, so the branch and its barrier are uniform; every split stages the same pairs
-      int* sb = bias_lds<PROC>();
-      if ((int)threadIdx.x < rp.nb) {
-        sb[threadIdx.x] = rp.bias[threadIdx.x];
-        sb[LOGIT_BIAS_MAX + threadIdx.x] = rp.bias[LOGIT_BIAS_MAX + threadIdx.x];
-      }
-      __syncthreads();
-    }
-  }
+// One row's draw (the kernel below has read its RowProc, written a forced row and staged the bias pairs). REP: the
+// row's slot has a repetition penalty; a uniform branch in the kernel picks the instantiation once per workgroup, so
+// the loops of rows without it are the loops they were.
+template <typename T, bool PROC, bool REP>
+__device__ __forceinline__ void sample_row(const T* x, int V, const float* temperature, const float* top_p,
+                                           const int* top_k, const int64_t* seeds, const int64_t* step_ptr,
+                                           int64_t* out_tokens, int max_rounds, int* ws, const RowProc& rp, int row,
+                                           int sp, int nsplit, float* sv, int* si, float* red) {
   const float temp = temperature ? temperature[row] : 0.f;
   const int nvec = V >> 3;
   const int tail0 = nvec << 3;
@@ -367,7 +389,7 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
     const uint64_t key = mix64(seed ^ mix64(stream * 0x632BE59BD9B4E019ull));
     if constexpr (PROC) {
       if (rp.minp && !greedy) {  // the row's proc[7]: uniform over its workgroups; every other row runs what it ran
-        sample_min_p_split<T>(x, V, rp, inv_t, key, row, sp, nsplit, ws, out_tokens, sv, si, red);
+        sample_min_p_split<T, REP>(x, V, rp, inv_t, key, row, sp, nsplit, ws, out_tokens, sv, si, red);
         return;
       }
     }
@@ -376,7 +398,7 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
     ArgMax a{-INFINITY, 0x7fffffff};
     for (int vi = v0 + threadIdx.x; vi < v1; vi += SNT) {
       float v[8];
-      load8p<T, PROC>(x, vi * 8, rp, v);
+      load8p<T, PROC, REP>(x, vi * 8, rp, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float xv = v[j] * inv_t;
@@ -385,7 +407,7 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
     }
     if (sp == nsplit - 1)
       for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
-        const float xv = load1p<T, PROC>(x, i, rp) * inv_t;
+        const float xv = load1p<T, PROC, REP>(x, i, rp) * inv_t;
         a = better(a, ArgMax{greedy ? xv : xv + gumbel_fast(key, i), i});
       }
     a = block_argmax(a, sv, si);
@@ -425,19 +447,19 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
   float z = 0.f;
   for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
     float v[8];
-    load8p<T, PROC>(x, vi * 8, rp, v);
+    load8p<T, PROC, REP>(x, vi * 8, rp, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) mx = fmaxf(mx, v[j] * inv_t);
   }
-  for (int i = tail0 + threadIdx.x; i < V; i += SNT) mx = fmaxf(mx, load1p<T, PROC>(x, i, rp) * inv_t);
+  for (int i = tail0 + threadIdx.x; i < V; i += SNT) mx = fmaxf(mx, load1p<T, PROC, REP>(x, i, rp) * inv_t);
   mx = block_max<SNT>(mx, red);
   for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
     float v[8];
-    load8p<T, PROC>(x, vi * 8, rp, v);
+    load8p<T, PROC, REP>(x, vi * 8, rp, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) z += __expf(v[j] * inv_t - mx);
   }
-  for (int i = tail0 + threadIdx.x; i < V; i += SNT) z += __expf(load1p<T, PROC>(x, i, rp) * inv_t - mx);
+  for (int i = tail0 + threadIdx.x; i < V; i += SNT) z += __expf(load1p<T, PROC, REP>(x, i, rp) * inv_t - mx);
   z = block_sum<SNT>(z, red);
   // min_p: a candidate also passes the row's threshold (z and the mass stay the whole row's: the ratio to the maximum
   // does not change under renormalisation). The maximum passes its own threshold, so round 0 has a candidate.
@@ -450,7 +472,7 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
     ArgMax a{-INFINITY, 0x7fffffff};
     for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
       float v[8];
-      load8p<T, PROC>(x, vi * 8, rp, v);
+      load8p<T, PROC, REP>(x, vi * 8, rp, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float xv = v[j] * inv_t;
@@ -459,16 +481,16 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
       }
     }
     for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
-      const float xv = load1p<T, PROC>(x, i, rp) * inv_t;
+      const float xv = load1p<T, PROC, REP>(x, i, rp) * inv_t;
       if (PROC ? (xv > pivot && xv >= thr) : xv > pivot) a = better(a, ArgMax{xv + gumbel(seed, stream, i), i});
     }
     a = block_argmax(a, sv, si);
     if (a.i == 0x7fffffff) break;
-    const float xc = load1p<T, PROC>(x, a.i, rp) * inv_t;
+    const float xc = load1p<T, PROC, REP>(x, a.i, rp) * inv_t;
     float mass = 0.f, cnt = 0.f;
     for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
       float v[8];
-      load8p<T, PROC>(x, vi * 8, rp, v);
+      load8p<T, PROC, REP>(x, vi * 8, rp, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float xv = v[j] * inv_t;
@@ -479,7 +501,7 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
       }
     }
     for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
-      const float xv = load1p<T, PROC>(x, i, rp) * inv_t;
+      const float xv = load1p<T, PROC, REP>(x, i, rp) * inv_t;
       if (xv > xc) {
         mass += __expf(xv - mx);
         cnt += 1.f;
@@ -499,27 +521,73 @@ __global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logit
     ArgMax a{-INFINITY, 0x7fffffff};
     for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
       float v[8];
-      load8p<T, PROC>(x, vi * 8, rp, v);
+      load8p<T, PROC, REP>(x, vi * 8, rp, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) a = better(a, ArgMax{v[j], vi * 8 + j});
     }
-    for (int i = tail0 + threadIdx.x; i < V; i += SNT) a = better(a, ArgMax{load1p<T, PROC>(x, i, rp), i});
+    for (int i = tail0 + threadIdx.x; i < V; i += SNT) a = better(a, ArgMax{load1p<T, PROC, REP>(x, i, rp), i});
     a = block_argmax(a, sv, si);
     result = a.i;
   }
   if (threadIdx.x == 0) emit_token<PROC>(out_tokens, row, result, V, rp);
 }
 
+// REP: the launch has a rep_tab (some live slot has a repetition penalty). Without one the PROC kernel neither reads the
+// table nor carries the penalised row body: it is the kernel it was before the penalty existed.
+template <typename T, bool PROC, bool REP>
+__global__ __launch_bounds__(SNT) void sample_kernel(const T* __restrict__ logits, int64_t stride, int V,
+                                                      const float* __restrict__ temperature,
+                                                      const float* __restrict__ top_p, const int* __restrict__ top_k,
+                                                      const int64_t* __restrict__ seeds, const int64_t* __restrict__ step_ptr,
+                                                      int64_t* __restrict__ out_tokens, int max_rounds,
+                                                      int* __restrict__ ws, const int* __restrict__ proc,
+                                                      const uint32_t* __restrict__ mask_tab, int64_t mask_ld,
+                                                      int* __restrict__ counts, int64_t cnt_ld,
+                                                      const int* __restrict__ bias_tab, int64_t bias_ld,
+                                                      const float* __restrict__ rep_tab) {
+  __shared__ float sv[SNT / 64];
+  __shared__ int si[SNT / 64];
+  __shared__ float red[SNT / 64];
+  const int row = blockIdx.x, sp = blockIdx.y, nsplit = gridDim.y;
+  const T* x = logits + (int64_t)row * stride;
+  const RowProc rp = row_proc<PROC>(proc, mask_tab, mask_ld, counts, cnt_ld, bias_tab, bias_ld,
+                                    REP ? rep_tab : nullptr, row);
+  if (PROC && rp.mode == 2) {  // forced token (a fixed piece of a tool-call grammar): every split returns, no ticket
+    if (sp == 0 && threadIdx.x == 0) emit_token<PROC>(out_tokens, row, rp.arg, V, rp);
+    return;
+  }
+  if constexpr (PROC) {
+    if (rp.nb > 0) {  // rp is the row's, so the branch and its barrier are uniform; every split stages the same pairs
+      int* sb = bias_lds<PROC>();
+      if ((int)threadIdx.x < rp.nb) {
+        sb[threadIdx.x] = rp.bias[threadIdx.x];
+        sb[LOGIT_BIAS_MAX + threadIdx.x] = rp.bias[LOGIT_BIAS_MAX + threadIdx.x];
+      }
+      __syncthreads();
+    }
+  }
+  if constexpr (PROC && REP) {
+    if (rp.rep) {  // (uniform: the row's)
+      sample_row<T, true, true>(x, V, temperature, top_p, top_k, seeds, step_ptr, out_tokens, max_rounds, ws, rp, row,
+                                sp, nsplit, sv, si, red);
+      return;
+    }
+  }
+  sample_row<T, PROC, false>(x, V, temperature, top_p, top_k, seeds, step_ptr, out_tokens, max_rounds, ws, rp, row, sp,
+                             nsplit, sv, si, red);
+}
+
 // ws (optional): int32 workspace of >= SAMPLE_MAX_ROWS + 2 * B * nsplit entries whose first SAMPLE_MAX_ROWS are zero
 // (tickets, re-armed by the kernel); without it every row is one workgroup. proc (optional, int32 [B, 8], see
 // RowProc) selects the logits-processing instantiation; mask_tab uint32 [rows, mask_ld] and counts int32
 // [slots, cnt_ld] (cnt_ld >= V rounded up to 8) are only read for rows that name them; bias_tab int32 [rows, bias_ld]
-// (kafka_abi.h) likewise — without it the kernel biases no row, whatever proc[6] says.
+// (kafka_abi.h) likewise — without it the kernel biases no row, whatever proc[6] says. rep_tab (optional, fp32
+// [slots, 2], as many rows as counts): the slots' repetition penalties (r, 1 / r); without it no row is multiplied.
 extern "C" hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int64_t stride, int B, int V, const float* temperature,
                          const float* top_p, const int* top_k, const int64_t* seeds, const int64_t* step,
                          int64_t* out_tokens, int* ws, int nsplit, const int* proc, const uint32_t* mask_tab,
                          int64_t mask_ld, int* counts, int64_t cnt_ld, const int* bias_tab, int64_t bias_ld,
-                         hipStream_t st) {
+                         const float* rep_tab, hipStream_t st) {
   if (B == 0) return hipSuccess;
   if (ws == nullptr || nsplit < 1) nsplit = 1;
   if (B > SAMPLE_MAX_ROWS || nsplit > 64) return hipErrorInvalidValue;
@@ -527,14 +595,19 @@ extern "C" hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int6
     return hipErrorInvalidValue;
   if (proc != nullptr && bias_tab != nullptr && bias_ld < 2 * LOGIT_BIAS_MAX) return hipErrorInvalidValue;
   const dim3 grid(B, nsplit);
-#define KAFKA_SAMPLE(T_, P_)                                                                                       \
-  sample_kernel<T_, P_><<<grid, SNT, 0, st>>>(reinterpret_cast<const T_*>(logits), stride, V, temperature, top_p, \
-                                              top_k, seeds, step, out_tokens, 32, ws, proc, mask_tab, mask_ld,     \
-                                              counts, cnt_ld, bias_tab, bias_ld)
+#define KAFKA_SAMPLE(T_, P_, R_)                                                                                     \
+  sample_kernel<T_, P_, R_><<<grid, SNT, 0, st>>>(reinterpret_cast<const T_*>(logits), stride, V, temperature, top_p, \
+                                                  top_k, seeds, step, out_tokens, 32, ws, proc, mask_tab, mask_ld,   \
+                                                  counts, cnt_ld, bias_tab, bias_ld, rep_tab)
+  const bool rep = proc != nullptr && counts != nullptr && rep_tab != nullptr;
   if (is_bf16) {
-    if (proc) KAFKA_SAMPLE(bf16, true); else KAFKA_SAMPLE(bf16, false);
+    if (rep) KAFKA_SAMPLE(bf16, true, true);
+    else if (proc) KAFKA_SAMPLE(bf16, true, false);
+    else KAFKA_SAMPLE(bf16, false, false);
   } else {
-    if (proc) KAFKA_SAMPLE(float, true); else KAFKA_SAMPLE(float, false);
+    if (rep) KAFKA_SAMPLE(float, true, true);
+    else if (proc) KAFKA_SAMPLE(float, true, false);
+    else KAFKA_SAMPLE(float, false, false);
   }
 #undef KAFKA_SAMPLE
   return hipGetLastError();

@@ -448,13 +448,20 @@ def attn_merge(part, lse, out, lse_out=None, pre=None, npre=0):
 
 
 LOGIT_BIAS_MAX = 300  # entries of one bias_tab row (csrc/kafka_abi.h): ids at [0, n), fp32 bits at [LOGIT_BIAS_MAX, ..)
+COUNT_SEEN_PROMPT = 1 << 30  # flag of a prompt token in a count word (csrc/kafka_abi.h); the count is the bits below
 
 
-def process_logits(logits, proc, mask_tab, counts, bias_tab=None):
+def process_logits(logits, proc, mask_tab, counts, bias_tab=None, rep_tab=None):
     """The sampler's per-row logits processing (csrc/sampling.hip RowProc) in fp32: penalties from the row's token
-    counts, then the row's sparse logit bias — ``(x - freq * c - (c > 0 ? pres : 0)) + b``, one fp32 add after the
+    counts, then the row's sparse logit bias — ``(y - freq * c - (c > 0 ? pres : 0)) + b``, one fp32 add after the
     penalty arithmetic — then the grammar bitmask (-inf where a bit is 0, whatever the bias). Returns (processed fp32
-    logits, forced ids or -1)."""
+    logits, forced ids or -1).
+
+    ``rep_tab`` (fp32 [slots, 2] = (r, inv_r), inv_r = float32(1) / float32(r) from the host; None or r == 1: off) is
+    the repetition penalty: ``y = x`` unless the row's count word of the token is non-zero (a prompt token carries
+    COUNT_SEEN_PROMPT, a generated one its count), then ``y = x * inv_r`` for ``x > 0`` and ``y = x * r`` otherwise —
+    one fp32 multiply rounded on its own, never a division, so ``y`` is within one fp32 ulp of ``x / r``. ``c`` is the
+    generated count, the word without the flag. Forced rows ignore it."""
     B, V = logits.shape
     x = logits.float().clone()
     forced = torch.full((B,), -1, dtype=torch.long)
@@ -466,7 +473,11 @@ def process_logits(logits, proc, mask_tab, counts, bias_tab=None):
             forced[b] = arg
             continue
         if slot >= 0:
-            c = counts[slot, :V].to(x.device).float()
+            word = counts[slot, :V].to(x.device)
+            if rep_tab is not None and float(rep_tab[slot, 0]) != 1.0:
+                r, inv_r = (rep_tab[slot, j].to(device=x.device, dtype=torch.float32) for j in (0, 1))
+                x[b] = torch.where(word != 0, torch.where(x[b] > 0, x[b] * inv_r, x[b] * r), x[b])
+            c = (word & (COUNT_SEEN_PROMPT - 1)).float()
             x[b] -= freq * c + pres * (c > 0).float()
         nb = min(int(pr[b, 6]), LOGIT_BIAS_MAX)  # (the kernel's clamp)
         if nb > 0:
@@ -484,15 +495,17 @@ def process_logits(logits, proc, mask_tab, counts, bias_tab=None):
 
 
 def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
-           mask_tab=None, counts=None, bias_tab=None):
+           mask_tab=None, counts=None, bias_tab=None, rep_tab=None):
     """CPU sampler with the same semantics (not the same random stream) as the HIP kernel: the sort-based definition
     of top-k / top-p and the CPU engine path. ``proc[:, 7]`` (the fp32 bits of ln(min_p), 0 = off) adds the min_p
     set ``x / T >= max(x / T) + ln(min_p)`` with the kernel's fp32 threshold, intersected with the other two; greedy
-    and forced rows ignore it. ``sample_replay`` below reproduces the kernel's own stream and decisions draw by draw."""
+    and forced rows ignore it. ``rep_tab``: the repetition penalty of ``process_logits`` (one fp32 multiply by the
+    host's reciprocal, within one fp32 ulp of x / r) over the row's seen tokens. ``sample_replay`` below reproduces
+    the kernel's own stream and decisions draw by draw."""
     B, V = logits.shape
     forced = None
     if proc is not None:
-        x, forced = process_logits(logits, proc, mask_tab, counts, bias_tab)
+        x, forced = process_logits(logits, proc, mask_tab, counts, bias_tab, rep_tab)
     else:
         x = logits.float()
     res = torch.empty(B, dtype=torch.long, device=logits.device)
@@ -722,19 +735,20 @@ def _replay_filtered(x, xv, tp, tk, seeds, steps, lmp=None):
 
 
 def sample_replay(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=None, out=None, proc=None,
-                  mask_tab=None, counts=None, nsplit: int = 1, bias_tab=None) -> SampleReplay:
+                  mask_tab=None, counts=None, nsplit: int = 1, bias_tab=None, rep_tab=None) -> SampleReplay:
     """CPU replay of csrc/sampling.hip with the kernel's own random stream: the arguments of ``ops.sample`` plus
     ``nsplit`` (the workgroups a greedy / plain-temperature row is split over; it must not change the result). Every
     row whose ``ambiguous`` flag is clear has exactly one right token and the kernel must return it. Logits are finite
     or -inf. ``step`` holds one value as for the kernel, or (replay only) one per row. ``counts`` is bumped with every
     token like the kernel bumps it. min_p (``proc[:, 7]``) is a threshold max + ln(min_p) formed and compared in fp32
     exactly as the kernel does, so it adds no ambiguity band; ``rescans`` counts, per min_p-only row, the slices the
-    kernel's last workgroup reads again."""
+    kernel's last workgroup reads again. ``rep_tab``: the repetition penalty, formed by ``process_logits`` in one fp32
+    multiply by the host's reciprocal as the kernel forms it (within one fp32 ulp of x / r): no band either."""
     B, V = logits.shape
     assert 1 <= nsplit <= 64
     forced = None
     if proc is not None:
-        x, forced = process_logits(logits, proc, mask_tab, counts, bias_tab)
+        x, forced = process_logits(logits, proc, mask_tab, counts, bias_tab, rep_tab)
     else:
         x = logits.float()
     x = x.cpu().contiguous().numpy()

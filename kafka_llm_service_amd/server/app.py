@@ -118,6 +118,8 @@ def _sampling_kwargs(req: ChatCompletionRequest) -> dict[str, Any]:
         kw["min_p"] = float(req.min_p)
     if req.top_k:
         kw["top_k"] = int(req.top_k)
+    if req.repetition_penalty is not None and req.repetition_penalty != 1:  # (absent or 1 is "off")
+        kw["repetition_penalty"] = float(req.repetition_penalty)
     return kw
 
 
