@@ -206,6 +206,7 @@ class LLMEngine:
         self.runner = ModelRunner(self.model, kc, vc, self.kvm, cfg.max_num_seqs, max_blocks,
                                   cascade_min_prefix=cfg.cascade_min_prefix, use_cascade=cfg.use_cascade,
                                   target_wgs=cfg.target_wgs, prefill_kv_chunk=cfg.prefill_kv_chunk)
+        self.runner.lp.json_table_fn = self._json_table  # (built by the first JSON-mode step, on every TP rank)
         if cfg.use_graphs is None:  # env KAFKA_GRAPHS=0/1 overrides the default (on for TP > 1 on GPUs)
             env = os.environ.get("KAFKA_GRAPHS")
             cfg.use_graphs = (env == "1") if env in ("0", "1") else (cfg.tp > 1 and self.device.type == "cuda")
@@ -247,6 +248,13 @@ class LLMEngine:
         # long new turn costs less (Llama-3-70B TP = 1: 1,516 vs 1,422 tok/s, TTFT 140 vs 119 ms,
         # profiles/r02/bench_70b_tp1_rowfit256_ab.jsonl)
         return ops.STREAM_MAX_M if self.model.tiled_only else 0
+
+    def _json_table(self):
+        """The JSON-mode token table of this model: its tokenizer's bytes per id and the engine's EOS ids."""
+        from kafka_llm_service_amd.engine.json_mode import table_for
+        from kafka_llm_service_amd.engine.tokenizer import tokenizer_for_model
+
+        return table_for(tokenizer_for_model(self.model_cfg), self.eos, self.model_cfg.vocab_size)
 
     def add_request(self, request_id: str, prompt_ids: list[int], params: SamplingParams | None = None,
                     meta: dict | None = None) -> Sequence:

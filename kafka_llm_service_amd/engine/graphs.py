@@ -75,6 +75,10 @@ class DecodeGraphs:
             # runs eagerly. Under TP the graph ends at the logit shard and the sampler is eager anyway, so the
             # decision stays what every rank takes from the broadcast plan (followers never see lp_rows)
             return False
+        if sp.json_rows is not None:
+            # a step with JSON-mode rows runs eagerly: the mask and advance kernels (ops/csrc/json_mask.hip) take a
+            # row count that changes from step to step. The rows ride in the plan, so every TP rank decides alike
+            return False
         return not self.disabled and h.B > 0 and h.T == h.B and h.n_items == 0
 
     # ------------------------------------------------------------------------------------------------------------

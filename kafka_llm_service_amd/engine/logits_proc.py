@@ -35,6 +35,14 @@ addresses (hipGraph-capturable), and so does the bias table:
     strictly ascending order, then the fp32 bits of their biases — keyed by content and LRU-managed like the mask
     rows: a thread sends the same object every turn, so after one 2.4 KB row upload it is a row index;
   * ``rep_tab`` fp32 [slots, 2]: ``(r, inv_r)`` of the slot's sequence, ``(1, 1)`` for a slot without the penalty.
+JSON mode (``SamplingParams.json_mode``; engine/json_mode.py, ops/csrc/json_mask.hip) adds rows the LRU never hands
+out: a processor built with ``json_slots`` appends that many rows to ``mask_tab`` and owns ``jstate`` int32
+[json_slots, 4], one automaton state record per live JSON sequence. A JSON row is a mode-1 row naming mask row
+``n_mask_rows + slot``; the mask kernel fills that row from ``jstate[slot]`` right before the sampler and the advance
+kernel moves ``jstate[slot]`` over the drawn token right behind it, so the state never visits the host: such rows
+carry no guard and never roll back, and two steps can be in flight. The host seeds a slot's record only when the row
+is sampled from a prefill — admission, or the re-prefill after a preemption or an eviction — by walking the output ids
+so far (all landed by then) through ``ref.json_advance_ref``.
 Table writes (new mask rows, slot zeroing, count decrements of rolled-back tokens) are ``ProcUpdates`` applied on the stream before the step's sampler — on
 every TP rank, from the same plan, so every rank samples the same token.
 """
@@ -47,7 +55,8 @@ import numpy as np
 import torch
 
 # (the update record travels in a step's wire format)
-from kafka_llm_service_amd.engine.step_plan import BIAS_ROW_INTS, COUNT_SEEN_PROMPT, LOGIT_BIAS_MAX, ProcUpdates
+from kafka_llm_service_amd.engine.step_plan import (BIAS_ROW_INTS, COUNT_SEEN_PROMPT, JSON_STATE_INTS, LOGIT_BIAS_MAX,
+                                                    ProcUpdates)
 
 MASK_ROWS = 512
 BIAS_ROWS = 512
@@ -89,7 +98,7 @@ def rep_factors(r: float) -> np.ndarray:
 
 class LogitsProcessor:
     def __init__(self, device: torch.device, vocab: int, max_slots: int = 256, mask_rows: int = MASK_ROWS,
-                 bias_rows: int = BIAS_ROWS):
+                 bias_rows: int = BIAS_ROWS, json_slots: int = 0):
         self.device = torch.device(device)
         self.V = vocab
         self.W = -(-vocab // 32)
@@ -109,13 +118,25 @@ class LogitsProcessor:
         self._rep_slots: set[int] = set()
         self._rep_seqs: dict[int, object] = {}  # seq_id -> seq of the sequences build() has seeded a slot for
         self._dec: list[tuple[int, int]] = []  # (slot, token) decrements queued by uncount()
+        # JSON mode: state-table slots (mask rows n_mask_rows + slot), the token table and its device copy
+        self.n_json_slots = json_slots
+        self.jstate: torch.Tensor | None = None
+        self._jslots: dict[int, tuple[int, object]] = {}  # seq_id -> (slot, seq)
+        self._jfree: list[int] = list(range(json_slots - 1, -1, -1))
+        self.json_table_fn = None  # () -> engine/json_mode.JsonTable of the model's tokenizer (set by the engine)
+        self._json_table = None
+        self._json_dev = None
         self.stats = {"mask_uploads": 0, "proc_steps": 0, "forced_rows": 0, "mask_rows_used": 0, "penalty_rows": 0,
-                      "bias_uploads": 0, "bias_rows_used": 0, "min_p_rows": 0, "rep_rows": 0, "seen_uploads": 0}
+                      "bias_uploads": 0, "bias_rows_used": 0, "min_p_rows": 0, "rep_rows": 0, "seen_uploads": 0,
+                      "json_rows": 0, "json_seeds": 0}
 
     # ---- tables (allocated together on first use: a captured graph sees every address) --------------------------
     def tables(self) -> tuple[torch.Tensor, torch.Tensor]:
         if self.mask_tab is None:
-            self.mask_tab = torch.zeros(self.n_mask_rows, self.W, dtype=torch.int32, device=self.device)
+            self.mask_tab = torch.zeros(self.n_mask_rows + self.n_json_slots, self.W, dtype=torch.int32,
+                                        device=self.device)
+            self.jstate = torch.zeros(max(1, self.n_json_slots), JSON_STATE_INTS, dtype=torch.int32,
+                                      device=self.device)
             self.counts = torch.zeros(self.max_slots, self.cnt_ld, dtype=torch.int32, device=self.device)
             self.bias_tab = torch.zeros(self.n_bias_rows, BIAS_ROW_INTS, dtype=torch.int32, device=self.device)
             self.rep_tab = torch.ones(self.max_slots, 2, dtype=torch.float32, device=self.device)
@@ -136,6 +157,64 @@ class LogitsProcessor:
         runs the kernel that knows no repetition penalty (a step's updates are applied before its sampler, so the
         answer is the step's, and every TP rank gives the same one)."""
         return self.rep_table() if self._rep_slots else None
+
+    # ---- JSON mode ----------------------------------------------------------------------------------------------
+    def set_json_table(self, table) -> None:
+        """The token table (engine/json_mode.JsonTable) the JSON rows of this processor are walked over."""
+        if table.V != self.V:
+            raise ValueError(f"JSON token table holds {table.V} ids, the vocabulary {self.V}")
+        if table is not self._json_table:
+            self._json_table, self._json_dev = table, None
+
+    def json_table(self):
+        if self._json_table is None:
+            if self.json_table_fn is None:
+                raise RuntimeError("JSON mode needs a token table (LogitsProcessor.set_json_table)")
+            self.set_json_table(self.json_table_fn())
+        return self._json_table
+
+    def json_tables(self):
+        """The device copy of the token table and the automaton (ops.JsonTables), made once."""
+        if self._json_dev is None:
+            from kafka_llm_service_amd import ops
+
+            self._json_dev = ops.JsonTables(self.json_table(), self.device)
+        return self._json_dev
+
+    def json_rows(self, proc: np.ndarray | None) -> np.ndarray | None:
+        """int32 [k, 2] (sampled row, state slot) of the JSON rows of ``proc`` (mode-1 rows naming a mask row behind
+        the LRU-managed ones), or None."""
+        if proc is None or not self.n_json_slots:
+            return None
+        idx = np.flatnonzero((proc[:, 0] == 1) & (proc[:, 1] >= self.n_mask_rows))
+        if not idx.size:
+            return None
+        return np.stack([idx, proc[idx, 1] - self.n_mask_rows], axis=1).astype(np.int32)
+
+    def _json_slot(self, seq) -> tuple[int, bool]:
+        e = self._jslots.get(seq.seq_id)
+        if e is not None:
+            return e[0], False
+        if not self._jfree:  # reclaim the slots of sequences that have finished since
+            for sid in [sid for sid, (_, s) in self._jslots.items() if s.finished]:
+                self._jfree.append(self._jslots.pop(sid)[0])
+        if not self._jfree:
+            raise RuntimeError(f"logits processor: more than {self.n_json_slots} live JSON-mode sequences")
+        slot = self._jfree.pop()
+        self._jslots[seq.seq_id] = (slot, seq)
+        return slot, True
+
+    def json_seed(self, seq) -> np.ndarray:
+        """The state record after the sequence's output ids so far — the only place the host computes a state."""
+        from kafka_llm_service_amd.engine import json_mode as jm
+        from kafka_llm_service_amd.ops import reference as ref
+
+        table, st = self.json_table(), jm.START_STATE
+        for t in seq.output_ids:
+            if t < 0:
+                raise RuntimeError("JSON mode: a state is seeded from landed tokens only")
+            st = ref.json_advance_ref(st, t, table)
+        return jm.state_record(st)
 
     # ---- host side ----------------------------------------------------------------------------------------------
     def _table_row(self, lru: OrderedDict, n_rows: int, key, words_fn, upd_rows: list, upd_words: list, used: set,
@@ -212,9 +291,12 @@ class LogitsProcessor:
         if e is not None and 0 <= int(token) < self.V:
             self._dec.append((e[0], int(token)))
 
-    def build(self, rows: list[tuple[int, object, object]], n: int) -> tuple[np.ndarray, ProcUpdates]:
+    def build(self, rows: list[tuple[int, object, object]], n: int,
+              n_decode: int | None = None) -> tuple[np.ndarray, ProcUpdates]:
         """``rows``: (row, seq, constraint spec) for every sampled row that needs processing (spec None, a list of
-        allowed ids, or a constrained.Mask); ``n`` rows in the step. Returns (proc int32 [n, 8], table updates)."""
+        allowed ids, or a constrained.Mask); ``n`` rows in the step, the first ``n_decode`` of them decode rows (None:
+        all — only JSON rows care: one sampled from a prefill has its state seeded). Returns (proc int32 [n, 8], table
+        updates)."""
         from kafka_llm_service_amd.engine.constrained import Mask
 
         self.tables()
@@ -223,6 +305,7 @@ class LogitsProcessor:
         upd_rows, upd_words, zero, used = [], [], [], set()
         b_rows, b_words, b_used = [], [], set()
         seen = []  # (slot, (r, inv_r), ascending distinct prompt ids) of the slots this step seeds
+        j_slots, j_states = [], []
         if self._rep_seqs:
             self._release_finished_rep(zero)
         V, W = self.V, self.W
@@ -258,6 +341,16 @@ class LogitsProcessor:
                         return pack_bits(keep, W)
                     proc[i, 0], proc[i, 1] = 1, self._mask_row(("L",) + ids, bits, upd_rows, upd_words, used)
                     self.stats["mask_rows_used"] += 1
+            if getattr(p, "json_mode", False):
+                if spec is not None:
+                    raise ValueError("JSON mode and a token constraint on one row: the masks are not intersected")
+                slot, new_slot = self._json_slot(s)
+                if new_slot or (n_decode is not None and i >= n_decode):
+                    j_slots.append(slot)
+                    j_states.append(self.json_seed(s))
+                    self.stats["json_seeds"] += 1
+                proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
+                self.stats["json_rows"] += 1
             rep = p.repetition_penalty
             if p.presence_penalty or p.frequency_penalty or rep != 1.0:
                 proc[i, 2], new_slot = self._slot(s, zero)
@@ -305,6 +398,9 @@ class LogitsProcessor:
             upd.rep_vals = np.stack([f for _, f, _ in seen])
             upd.seen_off = np.concatenate([[0], np.cumsum([ids.size for _, _, ids in seen])]).astype(np.int32)
             upd.seen_ids = np.concatenate([ids for _, _, ids in seen]).astype(np.int32)
+        if j_slots:
+            upd.json_slots = np.asarray(j_slots, dtype=np.int32)
+            upd.json_states = np.stack(j_states).astype(np.int32)
         return proc, upd
 
     # ---- device side ----------------------------------------------------------------------------------------------
@@ -313,8 +409,16 @@ class LogitsProcessor:
         if upd is None or upd.empty:
             return
         mask_tab, counts = self.tables()
+        if upd.json_slots.size:
+            st = upd.json_states
+            if st.shape != (upd.json_slots.size, JSON_STATE_INTS) or int(upd.json_slots.min()) < 0 \
+                    or int(upd.json_slots.max()) >= self.n_json_slots or (st[:, 0] < 0).any() \
+                    or (st[:, 0] > 63).any() or (st[:, 1] < 0).any() or (st[:, 1] > 32).any():
+                raise ValueError("logits processor: JSON state update does not fit the state table")
+            self.jstate.index_copy_(0, upload(upd.json_slots.astype(np.int64)),
+                                    upload(np.ascontiguousarray(st, dtype=np.int32)))
         if upd.mask_rows.size:
-            if int(upd.mask_rows.max()) >= mask_tab.shape[0] or upd.mask_words.shape[1] != mask_tab.shape[1]:
+            if int(upd.mask_rows.max()) >= self.n_mask_rows or upd.mask_words.shape[1] != mask_tab.shape[1]:
                 raise ValueError("logits processor: mask update does not fit the table")
             rows = upload(upd.mask_rows.astype(np.int64))
             mask_tab.index_copy_(0, rows, upload(upd.mask_words))

@@ -209,7 +209,9 @@ class ModelRunner:
         self.join_suffix = os.environ.get("KAFKA_JOIN_SUFFIX", "1") == "1"
         self.step_events: list | None = None  # (start, end) timing events per launched step when a list is set
         # grammar masks / forced tokens / penalties inside the sampler kernel (tables allocated on first use)
-        self.lp = LogitsProcessor(self.device, self.vocab, max_slots=max(256, max_num_seqs))
+        # (and the JSON-mode rows: a state slot and a device-written mask row per live JSON sequence)
+        self.lp = LogitsProcessor(self.device, self.vocab, max_slots=max(256, max_num_seqs),
+                                  json_slots=max(256, max_num_seqs))
 
     # ------------------------------------------------------------------------------------------------------------
     def prepare(self, batch: ScheduledBatch) -> tuple[StepInput, list[Sequence]]:
@@ -309,10 +311,15 @@ class ModelRunner:
             arrays += [np.concatenate([sp.temp, sp.topp]), sp.topk, sp.seeds]
         if sp is not None and sp.proc is not None:
             arrays.append(sp.proc)
+            if sp.json_rows is not None:  # (JSON rows are proc rows: behind them)
+                arrays.append(sp.json_rows)
         dev = self.stager.upload_many(arrays)
         if len(dev) > 2:
             has_t = not sp.greedy and sp.temp.shape[0]
-            self._sp_dev = (sp, *(dev[2:5] if has_t else (None, None, None)), dev[-1] if sp.proc is not None else None)
+            i_proc = 5 if has_t else 2
+            self._sp_dev = (sp, *(dev[2:5] if has_t else (None, None, None)),
+                            dev[i_proc] if sp.proc is not None else None)
+            self._json_dev = (sp, dev[i_proc + 1]) if sp.proc is not None and sp.json_rows is not None else None
         return self.views(dev[0], dev[1], h)
 
     def views(self, d64: torch.Tensor, d32: torch.Tensor, h: HostStep) -> StepInput:
@@ -365,12 +372,15 @@ class ModelRunner:
     def sample(self, logits: torch.Tensor, seqs: list[Sequence]) -> torch.Tensor:
         return self.sample_device(logits, self.sample_params(seqs))
 
-    def sample_params(self, seqs: list[Sequence]) -> "SampleParams":
+    def sample_params(self, seqs: list[Sequence], n_decode: int | None = None) -> "SampleParams":
         """Per-row sampling parameters of a step; rows with a token constraint, penalties (presence, frequency,
         repetition), a logit bias or min_p get a logits-processing row (engine/logits_proc.py) that the sampler kernel applies on the device. A constrained row's spec is
         computed from its landed tokens, or past a pending one when the grammar can guess its successor state
         (engine/constrained.py: a wrong guess rolls the row back one token); a forced token is returned in
-        ``known`` so the engine writes it at launch."""
+        ``known`` so the engine writes it at launch. A JSON-mode row (``json_mode``) is a processing row too: its mask
+        row is written on the device from its device-resident automaton state (engine/json_mode.py), so it needs no
+        landed token; the rows at and behind ``n_decode`` are sampled from a prefill, where such a row's state is
+        seeded."""
         n = len(seqs)
         temp = np.empty(n, dtype=np.float32)
         topp = np.empty(n, dtype=np.float32)
@@ -399,13 +409,14 @@ class ModelRunner:
                     known[i] = f
             # (min_p acts under temperature only: a greedy row needs no processing row for it)
             if allowed is not None or p.presence_penalty or p.frequency_penalty or p.logit_bias \
-                    or (p.min_p and p.temperature > 0) or p.repetition_penalty != 1.0:
+                    or (p.min_p and p.temperature > 0) or p.repetition_penalty != 1.0 or p.json_mode:
                 rows.append((i, s, allowed))
         proc = upd = None
         if rows:
-            proc, upd = self.lp.build(rows, n)
+            proc, upd = self.lp.build(rows, n, n_decode)
             upd = None if upd.empty else upd
         sp = SampleParams(temp, topp, topk, seeds, proc, not temp.any(), upd, known)
+        sp.json_rows = self.lp.json_rows(proc)
         if lp_rows:
             sp.lp_rows, sp.lp_k = np.asarray(lp_rows, dtype=np.int32), lp_k
         return sp
@@ -433,6 +444,20 @@ class ModelRunner:
                 "rep_tab": self.lp.live_rep_table()}
 
     def sample_device(self, logits: torch.Tensor, sp: "SampleParams") -> torch.Tensor:
+        """The step's sampler launch. A step with JSON rows launches the mask kernel in front of it (the rows' mask
+        rows from their device states) and the advance kernel behind it (the states over the drawn ids); a step
+        without them launches exactly what it always did."""
+        jpre, self._json_dev = getattr(self, "_json_dev", None), None
+        if sp.json_rows is None:
+            return self._sample_device(logits, sp)
+        jrows = jpre[1] if jpre is not None and jpre[0] is sp else self._h2d(sp.json_rows)
+        tabs, mask_tab = self.lp.json_tables(), self.lp.tables()[0]
+        ops.json_mask(tabs, jrows, self.lp.jstate, mask_tab, self.lp.n_mask_rows)
+        toks = self._sample_device(logits, sp)
+        ops.json_advance(tabs, jrows, toks, self.lp.jstate)
+        return toks
+
+    def _sample_device(self, logits: torch.Tensor, sp: "SampleParams") -> torch.Tensor:
         n = logits.shape[0]
         dev = logits.device
         pre, self._sp_dev = getattr(self, "_sp_dev", None), None
@@ -482,7 +507,7 @@ class ModelRunner:
         self.last_stats = host.stats
         self.recent_stats.append(host.stats)
         self.rows_hist[bisect.bisect_left(ROWS_BUCKETS, host.T)] += 1
-        sp = self.sample_params(sample_seqs)
+        sp = self.sample_params(sample_seqs, host.B)
         self.stager.begin()
         if self.broadcast is not None:  # TP leader: followers run the same step on their shards
             self.broadcast(host, sp)

@@ -53,8 +53,17 @@ class SamplingParams:
     # tokens generated so far — in [0.1, 10] (1: off): a seen logit x becomes x / r if x > 0 and x * r otherwise, before
     # the additive penalties (engine/logits_proc.py, the sampler kernel's rep_tab). Forced rows ignore it.
     repetition_penalty: float = 1.0
+    # OpenAI ``response_format: {"type": "json_object"}``: every sampled token keeps the output a prefix of one JSON
+    # object (RFC 8259, at most 32 levels deep; engine/json_mode.py), and once the object has closed only an EOS id
+    # is allowed. The mask is built on the device from a device-resident automaton state (ops/csrc/json_mask.hip) and
+    # applies last, like a tool-call mask; it is not combined with ``allowed_tokens_fn`` / ``tool_grammar``.
+    json_mode: bool = False
 
     def __post_init__(self):
+        if not isinstance(self.json_mode, bool):
+            raise ValueError("json_mode must be a bool")
+        if self.json_mode and (self.allowed_tokens_fn is not None or self.tool_grammar is not None):
+            raise ValueError("json_mode cannot be combined with a token constraint or a tool grammar")
         if isinstance(self.repetition_penalty, bool) or not isinstance(self.repetition_penalty, (int, float)) \
                 or not 0.1 <= self.repetition_penalty <= 10.0:  # (a NaN fails both comparisons)
             raise ValueError("repetition_penalty must be a number in [0.1, 10]")

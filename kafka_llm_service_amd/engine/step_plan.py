@@ -30,6 +30,7 @@ MAX_PREFIX_CHUNKS = 32
 LOGIT_BIAS_MAX = 300                # entries of one request's logit_bias (kafka_abi.h LOGIT_BIAS_MAX)
 BIAS_ROW_INTS = 2 * LOGIT_BIAS_MAX  # one row of the sampler's bias table: ids, then the fp32 bits of their biases
 COUNT_SEEN_PROMPT = 1 << 30         # flag of a prompt token in the sampler's count table (kafka_abi.h)
+JSON_STATE_INTS = 4                 # a JSON-mode row's device state record (kafka_abi.h; engine/json_mode.py)
 
 
 def cdiv(a, b):
@@ -183,11 +184,15 @@ class ProcUpdates:
     seen_off: np.ndarray = field(default_factory=lambda: np.zeros(1, np.int32))
     seen_ids: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     rep_vals: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.float32))
+    # JSON mode: [k] slots of the device state table the host (re)seeds — on admission and on a re-prefill — and
+    # [k, JSON_STATE_INTS] their records (state id, depth, stack bits, 0); every other state change happens on the device
+    json_slots: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    json_states: np.ndarray = field(default_factory=lambda: np.zeros((0, JSON_STATE_INTS), np.int32))
 
     @property
     def empty(self) -> bool:
         return not (self.mask_rows.size or self.zero_slots.size or self.dec.size or self.bias_rows.size
-                    or self.seen_slots.size)
+                    or self.seen_slots.size or self.json_slots.size)
 
     def check_seen(self) -> None:
         """The repetition-penalty sections agree with each other (a plan on the wire, a table update)."""
@@ -212,6 +217,9 @@ class SampleParams:
     # largest top_logprobs. NOT part of pack_plan / unpack_plan: only the rank that returns tokens computes them
     lp_rows: np.ndarray | None = None
     lp_k: int = 0
+    # JSON mode: int32 [k, 2] (sampled row, state-table slot) of the step's JSON rows, or None. The mask kernel runs
+    # over them before the sampler and the advance kernel behind it (ops/csrc/json_mask.hip); part of the plan
+    json_rows: np.ndarray | None = None
 
 
 _PLAN_SCALARS = ("B", "T", "nbt", "bt_w", "n_rows", "s_total", "n_dec_items", "n_prefix_items", "cascade_prefix",
@@ -256,6 +264,14 @@ def pack_plan(h: HostStep, sp: SampleParams) -> tuple[np.ndarray, np.ndarray]:
     if upd.seen_slots.size:  # behind the bias rows: slots [k], offsets [k + 1], factors [k, 2] fp32, ids
         parts += [upd.seen_slots.astype(np.int32, copy=False), upd.seen_off.astype(np.int32, copy=False),
                   upd.rep_vals.astype(np.float32, copy=False), upd.seen_ids.astype(np.int32, copy=False)]
+    if upd.json_states.shape != (upd.json_slots.size, JSON_STATE_INTS):
+        raise ValueError("plan: JSON state slots and records disagree")
+    jrows = sp.json_rows if sp.json_rows is not None else np.zeros((0, 2), np.int32)
+    if jrows.ndim != 2 or jrows.shape[1] != 2:
+        raise ValueError("plan: JSON rows must be (sampled row, slot) pairs")
+    if upd.json_slots.size or jrows.size:  # last: seeded slots [k], their records [k, 4], the step's JSON rows [j, 2]
+        parts += [upd.json_slots.astype(np.int32, copy=False), upd.json_states.astype(np.int32, copy=False),
+                  jrows.astype(np.int32, copy=False)]
     payload = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in parts])
     hdr = np.zeros(PLAN_HDR, dtype=np.int64)
     hdr[0] = 1
@@ -266,6 +282,7 @@ def pack_plan(h: HostStep, sp: SampleParams) -> tuple[np.ndarray, np.ndarray]:
                              upd.mask_rows.size, W, upd.zero_slots.size, upd.dec.shape[0]]
     hdr[1 + k + 10] = upd.bias_rows.size  # (0 and no bytes behind ``dec`` for a step without new bias rows)
     hdr[1 + k + 11] = upd.seen_slots.size  # (likewise: 0 and no bytes without newly seeded repetition-penalty slots)
+    hdr[1 + k + 12], hdr[1 + k + 13] = upd.json_slots.size, jrows.shape[0]  # (likewise without JSON rows)
     return hdr, payload
 
 
@@ -275,6 +292,7 @@ def unpack_plan(hdr: np.ndarray, payload: np.ndarray) -> tuple[HostStep, SampleP
     n64, n32, n, greedy, _, n_proc, n_mask, W, n_zero, n_dec = (int(v) for v in hdr[1 + k:1 + k + 10])
     n_bias = int(hdr[1 + k + 10])
     n_seen = int(hdr[1 + k + 11])
+    n_jseed, n_jrows = int(hdr[1 + k + 12]), int(hdr[1 + k + 13])
     o = 0
 
     def take(dt, cnt):
@@ -299,6 +317,11 @@ def unpack_plan(hdr: np.ndarray, payload: np.ndarray) -> tuple[HostStep, SampleP
         upd.rep_vals = take(np.float32, 2 * n_seen).reshape(n_seen, 2)
         upd.seen_ids = take(np.int32, max(0, int(upd.seen_off[-1])))
         upd.check_seen()
+    if n_jseed or n_jrows:
+        upd.json_slots = take(np.int32, n_jseed)
+        upd.json_states = take(np.int32, n_jseed * JSON_STATE_INTS).reshape(n_jseed, JSON_STATE_INTS)
+        jrows = take(np.int32, 2 * n_jrows).reshape(n_jrows, 2)
+        sp.json_rows = jrows if n_jrows else None
     sp.proc = proc if n_proc else None
     sp.upd = None if upd.empty else upd
     return h, sp

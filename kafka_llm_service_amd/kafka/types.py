@@ -8,7 +8,10 @@ return per-token log-probabilities of the model's raw logits; ``logit_bias`` map
 biases in [-100, 100], at most 300 of them, added to the logits inside the sampler. Two fields go beyond the OpenAI
 schema: ``min_p`` in [0, 1] and ``top_k`` >= 0 (0 turns either off), the sampler's other two truncation rules, and
 ``repetition_penalty`` in [0.1, 10] (1 or absent: off), the multiplicative penalty of HF ``generate`` / vLLM over the
-tokens of the prompt and of the output so far.
+tokens of the prompt and of the output so far. ``response_format``: ``{"type": "text"}`` (or absent) changes nothing;
+``{"type": "json_object"}`` is JSON mode — the reply is one JSON object (the sampler masks every token that would
+break RFC 8259, the mask built on the GPU: engine/json_mode.py); ``json_schema`` and any other type are refused, and so
+is JSON mode together with ``tools`` unless ``tool_choice`` is ``"none"``.
 """
 from __future__ import annotations
 
@@ -58,6 +61,21 @@ class ChatCompletionRequest(BaseModel):
     top_k: Optional[int] = Field(None, ge=0)
     # a logit x of a token the prompt or the output so far holds becomes x / r (x > 0) or x * r (x <= 0); 1: off
     repetition_penalty: Optional[float] = Field(None, ge=0.1, le=10)
+    # {"type": "text"} | {"type": "json_object"} (JSON mode: the reply is one JSON object)
+    response_format: Optional[dict[str, Any]] = None
+
+    @field_validator("response_format")
+    @classmethod
+    def _response_format_type(cls, v):
+        if v is None:
+            return v
+        t = v.get("type")
+        if t == "json_schema":
+            raise ValueError('response_format type "json_schema" is not supported; the supported structured type is '
+                             '"json_object"')
+        if t not in ("text", "json_object"):
+            raise ValueError(f'response_format type must be "text" or "json_object", not {t!r}')
+        return v
 
     @field_validator("repetition_penalty", mode="before")
     @classmethod
@@ -89,7 +107,14 @@ class ChatCompletionRequest(BaseModel):
     def _top_logprobs_needs_logprobs(self):
         if self.top_logprobs is not None and not self.logprobs:
             raise ValueError("top_logprobs requires logprobs to be true")
+        if self.json_mode and self.tools and self.tool_choice != "none":
+            raise ValueError('response_format "json_object" cannot be combined with tools unless tool_choice is '
+                             '"none" (the JSON mask and the tool-call mask are not intersected)')
         return self
+
+    @property
+    def json_mode(self) -> bool:
+        return bool(self.response_format) and self.response_format.get("type") == "json_object"
 
 
 class AgentRunRequest(BaseModel):

@@ -153,7 +153,7 @@ class EngineLLMProvider(LLMProvider):
                                 tool_choice: Any = None, logprobs: bool | None = None,
                                 top_logprobs: int | None = None, logit_bias: dict | None = None,
                                 min_p: float | None = None, top_k: int | None = None,
-                                repetition_penalty: float | None = None,
+                                repetition_penalty: float | None = None, response_format: dict | None = None,
                                 **kwargs: Any) -> AsyncGenerator[StreamChunk, None]:
         """``logprobs`` / ``top_logprobs``: every non-special token the provider consumes yields one OpenAI entry
         ({token, logprob, bytes, top_logprobs}) over the model's RAW logits; a content chunk carries the entries of
@@ -169,7 +169,16 @@ class EngineLLMProvider(LLMProvider):
         next to ``top_p`` — keep the tokens with p >= min_p * p_max, keep the k most likely — intersected.
 
         ``repetition_penalty`` (an extension too; None or 1: off): in [0.1, 10], multiplies the logits of the tokens
-        the rendered prompt or the output so far holds (x / r if x > 0, else x * r) before the other penalties."""
+        the rendered prompt or the output so far holds (x / r if x > 0, else x * r) before the other penalties.
+
+        ``response_format`` ``{"type": "json_object"}``: JSON mode — the engine masks every token that would keep the
+        reply from being one JSON object, and once the object has closed allows only an end-of-sequence id, so the
+        reply finishes with "stop" when the document closed and with "length" when ``max_tokens`` cut it. The mask
+        applies last, like a tool-call mask, and replaces it: a JSON-mode request decodes no tool call."""
+        json_mode = (response_format or {}).get("type") == "json_object"
+        if response_format and not json_mode and response_format.get("type") != "text":
+            raise LLMProviderError('response_format type must be "text" or "json_object"', provider="engine",
+                                   status_code=400)
         self.validate_messages(messages)
         bias = None
         if logit_bias:
@@ -199,8 +208,9 @@ class EngineLLMProvider(LLMProvider):
                                 presence_penalty=float(presence_penalty or 0.0), seed=seed,
                                 ignore_eos=self.ignore_eos, logprobs=bool(logprobs),
                                 top_logprobs=int(top_logprobs or 0) if logprobs else 0, logit_bias=bias,
+                                json_mode=json_mode,
                                 tool_grammar=({"tools": tools, "tool_choice": self._choice(tool_choice, messages)}
-                                              if tools and self.constrain_tools else None))
+                                              if tools and self.constrain_tools and not json_mode else None))
         stops = [s for s in (stop or []) if s]
         hold = max((len(s) for s in stops), default=1) - 1
         rid = f"req-{uuid.uuid4().hex}"

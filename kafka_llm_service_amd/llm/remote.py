@@ -67,6 +67,8 @@ class RemoteOpenAIProvider(LLMProvider):
                 body[k] = kw[k]
         if kw.get("repetition_penalty") not in (None, 1, 1.0):  # (1 is "off")
             body["repetition_penalty"] = kw["repetition_penalty"]
+        if (kw.get("response_format") or {}).get("type") == "json_object":  # (absent or "text" sends nothing)
+            body["response_format"] = {"type": "json_object"}
         return body
 
     async def stream_completion(self, messages: list[Message], *, temperature: Optional[float] = None,

@@ -7,6 +7,7 @@ Kernel inventory:
   attn_decode / attn_prefill / attn_merge       csrc/attention.hip   (MFMA 32x32x16 bf16, paged, split-K, cascade)
   sample (greedy / temperature / top-k / top-p) csrc/sampling.hip
   token_logprobs (logprob + top-k alternatives) csrc/logprobs.hip
+  json_mask / json_advance (JSON-mode masks)    csrc/json_mask.hip
   moe_* / grouped GEMM                          csrc/moe.hip
   custom all-reduce                             csrc/allreduce.hip
 """
@@ -228,6 +229,69 @@ def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, step=No
     else:
         ref.sample(logits, temperature, top_p, top_k, seeds, step, out, proc, mask_tab, counts, bias_tab, rep_tab)
     return out
+
+
+class JsonTables:
+    """What the JSON-mode ops read, on one device: the automaton's transition table, the tokens' bytes (CSR) and the
+    EOS ids of ``table`` (engine/json_mode.JsonTable, kept for the CPU path). Built once per (table, device)."""
+
+    def __init__(self, table, device):
+        from kafka_llm_service_amd.engine import json_mode as jm
+
+        self.table = table
+        self.device = torch.device(device)
+        self.V = table.V
+        self.trans = torch.from_numpy(jm.TRANS.copy()).to(self.device)
+        self.tok_off = torch.from_numpy(table.tok_off).to(self.device)
+        # (padded: a table whose tokens are all empty still has an address)
+        self.tok_bytes = torch.from_numpy(np.concatenate([table.tok_bytes, np.zeros(16, np.uint8)])).to(self.device)
+        self.eos = torch.from_numpy(table.eos_ids).to(self.device)
+
+
+def _json_check(tabs: JsonTables, rows, state, n_sampled: int | None = None) -> None:
+    """The device-side values the kernels trust (CPU tensors only: the kernels skip a row that names a slot outside
+    the state table)."""
+    r = rows.reshape(-1, 2)
+    if r.numel() and (int(r[:, 1].min()) < 0 or int(r[:, 1].max()) >= state.shape[0]
+                      or (n_sampled is not None and (int(r[:, 0].min()) < 0 or int(r[:, 0].max()) >= n_sampled))):
+        raise ValueError("json: a row names a slot outside the state table or a row outside the sampled ids")
+
+
+def json_mask(tabs: JsonTables, rows, state, mask_tab, json_row0: int) -> None:
+    """For every (sampled row, slot) pair of ``rows`` (int32 [k, 2]): row ``json_row0 + slot`` of ``mask_tab`` (int32
+    [rows, >= ceil(V / 32)]) becomes the vocabulary mask of the slot's JSON automaton state ``state[slot]`` (int32
+    [slots, 4]: state id, depth, stack bits, 0) — ``ref.json_mask_ref`` word for word. Launches and allocates nothing
+    for k = 0."""
+    if rows.shape[0] == 0:
+        return
+    if _gpu(mask_tab):
+        ext().json_mask(tabs.trans, tabs.tok_off, tabs.tok_bytes, tabs.eos, rows, state, mask_tab, int(json_row0))
+        return
+    from kafka_llm_service_amd.engine import json_mode as jm
+
+    _json_check(tabs, rows, state)
+    W = tabs.table.W
+    if json_row0 < 0 or json_row0 + state.shape[0] > mask_tab.shape[0] or mask_tab.shape[1] < W:
+        raise ValueError("json_mask: the mask table does not hold the slots' rows")
+    for slot in rows[:, 1].tolist():
+        words = ref.json_mask_ref(jm.record_state(state[slot].numpy()), tabs.table)
+        mask_tab[json_row0 + slot, :W] = torch.from_numpy(words.view(np.int32).copy())
+
+
+def json_advance(tabs: JsonTables, rows, sampled, state) -> None:
+    """Behind the sampler: ``state[slot]`` of every (sampled row, slot) pair advances over the bytes of the id
+    ``sampled[row]`` (int64) — ``ref.json_advance_ref``. Launches nothing for k = 0."""
+    if rows.shape[0] == 0:
+        return
+    if _gpu(state):
+        ext().json_advance(tabs.trans, tabs.tok_off, tabs.tok_bytes, rows, sampled, state)
+        return
+    from kafka_llm_service_amd.engine import json_mode as jm
+
+    _json_check(tabs, rows, state, sampled.shape[0])
+    for r, slot in rows.tolist():
+        st = ref.json_advance_ref(jm.record_state(state[slot].numpy()), int(sampled[r]), tabs.table)
+        state[slot] = torch.from_numpy(jm.state_record(st))
 
 
 LOGPROBS_MAX_K = 20      # OpenAI's top_logprobs bound; the kernel's register / LDS budget (csrc/logprobs.hip)

@@ -394,6 +394,53 @@ static void sample(at::Tensor logits, c10::optional<at::Tensor> temperature, c10
                                  cp, cld, bt, bld, rt, cur_stream()));
 }
 
+// JSON mode (json_mask.hip): the shared checks of the automaton's table and the token bytes, then the two launches.
+static int json_check_tables(const at::Tensor& trans, const at::Tensor& tok_off, const at::Tensor& tok_bytes,
+                             const at::Tensor& jrows, const at::Tensor& jstate) {
+  TORCH_CHECK(trans.is_cuda() && trans.scalar_type() == at::kByte && trans.is_contiguous() && trans.numel() == 64 * 256,
+              "json: trans must be uint8 [64, 256] on the GPU");
+  TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.dim() == 1 &&
+                  tok_off.numel() >= 2,
+              "json: tok_off must be int32 [V + 1] on the GPU");
+  TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous(),
+              "json: tok_bytes must be uint8 on the GPU");
+  TORCH_CHECK(jrows.is_cuda() && jrows.scalar_type() == at::kInt && jrows.is_contiguous() && jrows.dim() == 2 &&
+                  jrows.size(1) == 2,
+              "json: rows must be int32 [k, 2] (sampled row, slot) on the GPU");
+  TORCH_CHECK(jstate.is_cuda() && jstate.scalar_type() == at::kInt && jstate.is_contiguous() && jstate.dim() == 2 &&
+                  jstate.size(1) == kafka::JSON_STATE_INTS,
+              "json: the state table must be int32 [slots, 4] on the GPU");
+  return (int)(tok_off.numel() - 1);
+}
+
+static void json_mask(at::Tensor trans, at::Tensor tok_off, at::Tensor tok_bytes, at::Tensor eos, at::Tensor jrows,
+                      at::Tensor jstate, at::Tensor mask_tab, int64_t json_row0) {
+  const int V = json_check_tables(trans, tok_off, tok_bytes, jrows, jstate);
+  TORCH_CHECK(eos.is_cuda() && eos.scalar_type() == at::kInt && eos.is_contiguous() &&
+                  eos.numel() <= kafka::JSON_MAX_EOS,
+              "json_mask: eos must be int32 [<= 8] on the GPU");
+  TORCH_CHECK(mask_tab.is_cuda() && mask_tab.scalar_type() == at::kInt && mask_tab.is_contiguous() &&
+                  mask_tab.dim() == 2 && mask_tab.size(1) * 32 >= V && json_row0 >= 0 &&
+                  json_row0 + jstate.size(0) <= mask_tab.size(0),
+              "json_mask: mask_tab must be int32 [>= json_row0 + slots, >= V / 32] on the GPU");
+  CHECK_HIP(kafka_launch_json_mask(trans.data_ptr<uint8_t>(), tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V,
+                                   eos.data_ptr<int>(), (int)eos.numel(), jrows.data_ptr<int>(), (int)jrows.size(0),
+                                   jstate.data_ptr<int>(), (int)jstate.size(0),
+                                   reinterpret_cast<uint32_t*>(mask_tab.data_ptr<int>()), mask_tab.size(1),
+                                   mask_tab.size(0), (int)json_row0, cur_stream()));
+}
+
+static void json_advance(at::Tensor trans, at::Tensor tok_off, at::Tensor tok_bytes, at::Tensor jrows,
+                         at::Tensor sampled, at::Tensor jstate) {
+  const int V = json_check_tables(trans, tok_off, tok_bytes, jrows, jstate);
+  TORCH_CHECK(sampled.is_cuda() && sampled.scalar_type() == at::kLong && sampled.is_contiguous() && sampled.dim() == 1,
+              "json_advance: the sampled ids must be int64 [n] on the GPU");
+  CHECK_HIP(kafka_launch_json_advance(trans.data_ptr<uint8_t>(), tok_off.data_ptr<int>(),
+                                      tok_bytes.data_ptr<uint8_t>(), V, jrows.data_ptr<int>(), (int)jrows.size(0),
+                                      sampled.data_ptr<int64_t>(), (int)sampled.numel(), jstate.data_ptr<int>(),
+                                      (int)jstate.size(0), cur_stream()));
+}
+
 // Per-token logprobs (logprobs.hip). rows: int32 [R] or none (rows 0..R-1); tok_lp f32 [R], top_lp f32 [R, K] and
 // top_id int32 [R, K] share one row stride (views of one packed record buffer). The row ids are trusted (the Python
 // op range-checks a host list before uploading it); everything the kernel indexes by them is sized for every row.
@@ -1020,6 +1067,10 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("seeds"), py::arg("step"), py::arg("out"), py::arg("ws") = py::none(), py::arg("nsplit") = 1,
         py::arg("proc") = py::none(), py::arg("mask_tab") = py::none(), py::arg("counts") = py::none(),
         py::arg("bias_tab") = py::none(), py::arg("rep_tab") = py::none());
+  m.def("json_mask", &json_mask, py::arg("trans"), py::arg("tok_off"), py::arg("tok_bytes"), py::arg("eos"),
+        py::arg("rows"), py::arg("state"), py::arg("mask_tab"), py::arg("json_row0"));
+  m.def("json_advance", &json_advance, py::arg("trans"), py::arg("tok_off"), py::arg("tok_bytes"), py::arg("rows"),
+        py::arg("sampled"), py::arg("state"));
   m.def("token_logprobs", &token_logprobs, py::arg("logits"), py::arg("tokens"), py::arg("rows"), py::arg("k"),
         py::arg("tok_lp"), py::arg("top_lp"), py::arg("top_id"), py::arg("ws") = py::none(), py::arg("nsplit") = 1);
   m.def("wstream_plan", &wstream_plan);

@@ -61,6 +61,14 @@ constexpr int LOGIT_BIAS_MAX = 300;  // OpenAI's bound on the entries of one req
 // token is "seen" by the repetition penalty when the word is non-zero.
 constexpr int COUNT_SEEN_PROMPT = 1 << 30;
 
+// ---- JSON mode (json_mask.hip; engine/json_mode.py holds the automaton and its transition table) ---------------------
+// A row's state record in the device state table is int32 [JSON_STATE_INTS]: (state id, depth, stack bits, 0). The
+// kernels name the few states the walk itself assigns; every other id only ever comes out of the table.
+constexpr int JSON_STATE_INTS = 4;
+constexpr int JSON_MAX_DEPTH = 32;  // open containers; the stack is one bit per level (1 = object) in one word
+constexpr int JSON_MAX_EOS = 8;     // EOS ids the mask kernel compares a token with in DONE
+constexpr int JSON_EXPECT_KEY = 2, JSON_EXPECT_VALUE = 4, JSON_DONE = 7;
+
 // ---- weight tile formats of the streaming GEMMs (wstream_gemm.hip WFMT; ops.WEIGHT_FORMATS) ----------------------
 // bf16 tiles [N/32][K/16][64 lanes][8]; fp8: e4m3 bytes [N/32][K/32][64][16] + fp32 row scales [N]; MXFP4: e2m1 bytes
 // [N/32][K/64][64][16] + e8m0 block exponents [N/32][K/64][32][2]
@@ -166,6 +174,20 @@ hipError_t kafka_launch_sample(const void* logits, bool is_bf16, int64_t stride,
                                int64_t* out_tokens, int* ws, int nsplit, const int* proc, const uint32_t* mask_tab,
                                int64_t mask_ld, int* counts, int64_t cnt_ld, const int* bias_tab, int64_t bias_ld,
                                const float* rep_tab, hipStream_t st);
+
+// ---- json_mask.hip
+// The vocabulary masks of the step's JSON rows, written into rows json_row0 + slot of mask_tab from the slots' state
+// records, and (behind the sampler) the records' advance over the sampled ids. trans: uint8 [64 * 256]; tok_off int32
+// [V + 1] / tok_bytes: the tokens' bytes (CSR); eos: n_eos <= JSON_MAX_EOS ids; jrows int32 [n_rows, 2]: (sampled row,
+// slot) pairs; jstate int32 [n_slots, JSON_STATE_INTS]; mask_tab uint32 [mask_rows, mask_ld] with mask_ld * 32 >= V
+// and json_row0 + n_slots <= mask_rows; sampled int64 [n_sampled]. Nothing is launched for n_rows == 0.
+hipError_t kafka_launch_json_mask(const uint8_t* trans, const int* tok_off, const uint8_t* tok_bytes, int V,
+                                  const int* eos, int n_eos, const int* jrows, int n_rows, const int* jstate,
+                                  int n_slots, uint32_t* mask_tab, int64_t mask_ld, int64_t mask_rows, int json_row0,
+                                  hipStream_t st);
+hipError_t kafka_launch_json_advance(const uint8_t* trans, const int* tok_off, const uint8_t* tok_bytes, int V,
+                                     const int* jrows, int n_rows, const int64_t* sampled, int n_sampled, int* jstate,
+                                     int n_slots, hipStream_t st);
 
 // ---- logprobs.hip
 // Log softmax of the RAW logits (no temperature / penalties / mask) at each scored row's sampled token, and the row's

@@ -950,3 +950,99 @@ def ep_combine(back, slot_map, topk_w, lo, n_own, out):
         for j in range(k):
             acc += float(topk_w[lo + i, j]) * back[int(slot_map[i * k + j])].float()
         out[i] = acc.to(out.dtype)
+
+
+# ---- JSON mode: the byte walk of engine/json_mode.py's automaton, token masks and state advance -------------------
+# A state is (state id, depth, stack bits). These three functions are the definition csrc/json_mask.hip is held to,
+# bit for bit: all of it is integer work, so there is no tolerance anywhere.
+def json_walk(state, data: bytes):
+    """The state after reading ``data`` from ``state``; (DEAD, depth, stack) as soon as a byte is rejected (depth and
+    stack as they stood). DONE and DEAD accept no byte."""
+    from kafka_llm_service_amd.engine import json_mode as jm
+
+    s, d, stk = (int(v) for v in state)
+    for b in data:
+        if s == jm.DEAD:
+            break
+        e = int(jm.TRANS[s, b])
+        op, nxt = e >> 6, e & 63
+        if nxt == jm.DEAD:
+            s = jm.DEAD
+        elif op == 0:
+            s = nxt
+        elif op == jm.OP_OPEN:
+            if d >= jm.JSON_MAX_DEPTH:
+                s = jm.DEAD
+            else:
+                if b == 0x7B:
+                    stk |= 1 << d
+                d += 1
+                s = nxt
+        else:
+            top = (stk >> (d - 1)) & 1 if d > 0 else -1
+            if op == jm.OP_COMMA:
+                s = jm.DEAD if top < 0 else (jm.EXPECT_KEY if top else jm.EXPECT_VALUE)
+            elif top != (1 if b == 0x7D else 0):
+                s = jm.DEAD
+            else:
+                d -= 1
+                stk &= ~(1 << d)
+                s = jm.DONE if d == 0 else nxt
+    return s, d, stk
+
+
+def json_advance_ref(state, token: int, table):
+    """The row's state after ``token`` (``table``: engine/json_mode.JsonTable). In DONE every id — the EOS the mask
+    allows, a forced id — leaves the state at DONE; elsewhere an id without bytes or outside the table is a rejected
+    byte."""
+    from kafka_llm_service_amd.engine import json_mode as jm
+
+    s, d, stk = (int(v) for v in state)
+    if s == jm.DONE:
+        return s, d, stk
+    token = int(token)
+    if not 0 <= token < table.V or table.lens[token] == 0:
+        return jm.DEAD, d, stk
+    return json_walk((s, d, stk), table.bytes_of(token))
+
+
+def json_mask_ref(state, table) -> np.ndarray:
+    """uint32 [ceil(V / 32)]: bit i (bit ``i % 32`` of word ``i // 32``) is set iff token i is allowed in ``state`` —
+    in DONE: iff it is one of the table's EOS ids; elsewhere: iff it has at least one byte and every byte is accepted
+    in sequence from ``state``. All tokens are walked together, one byte position at a time."""
+    from kafka_llm_service_amd.engine import json_mode as jm
+
+    V = table.V
+    s0, d0, k0 = (int(v) for v in state)
+    keep = np.zeros(table.W * 32, dtype=bool)
+    if s0 == jm.DONE:
+        keep[table.eos_ids] = True
+    elif s0 != jm.DEAD:
+        s = np.full(V, s0, dtype=np.int64)
+        d = np.full(V, d0, dtype=np.int64)
+        stk = np.full(V, k0, dtype=np.int64)
+        off = table.tok_off[:-1].astype(np.int64)
+        live = np.flatnonzero(table.lens > 0)
+        trans = jm.TRANS.astype(np.int64)
+        for j in range(int(table.lens.max())):
+            live = live[(table.lens[live] > j) & (s[live] != jm.DEAD)]
+            if not live.size:
+                break
+            b = table.tok_bytes[off[live] + j].astype(np.int64)
+            e = trans[s[live], b]
+            op, nxt = e >> 6, e & 63
+            dl, kl = d[live], stk[live]
+            top = np.where(dl > 0, (kl >> np.maximum(dl - 1, 0)) & 1, -1)
+            opening, closing, comma = op == jm.OP_OPEN, op == jm.OP_CLOSE, op == jm.OP_COMMA
+            dead = (nxt == jm.DEAD) | (opening & (dl >= jm.JSON_MAX_DEPTH)) | (comma & (top < 0)) \
+                | (closing & (top != (b == 0x7D)))
+            nd = dl + opening - closing
+            nk = np.where(opening & (b == 0x7B), kl | (1 << np.minimum(dl, 31)), kl)
+            nk = np.where(closing, kl & ~(1 << np.maximum(dl - 1, 0)), nk)
+            ns = np.where(comma, np.where(top == 1, jm.EXPECT_KEY, jm.EXPECT_VALUE), nxt)
+            ns = np.where(closing & (nd == 0), jm.DONE, ns)
+            s[live] = np.where(dead, jm.DEAD, ns)
+            d[live] = np.where(dead, dl, nd)
+            stk[live] = np.where(dead, kl, nk)
+        keep[:V] = (table.lens > 0) & (s != jm.DEAD)
+    return np.packbits(keep, bitorder="little").view("<u4")

@@ -120,6 +120,8 @@ def _sampling_kwargs(req: ChatCompletionRequest) -> dict[str, Any]:
         kw["top_k"] = int(req.top_k)
     if req.repetition_penalty is not None and req.repetition_penalty != 1:  # (absent or 1 is "off")
         kw["repetition_penalty"] = float(req.repetition_penalty)
+    if req.json_mode:  # ({"type": "text"} or absent: nothing new goes down)
+        kw["response_format"] = {"type": "json_object"}
     return kw
 
 
