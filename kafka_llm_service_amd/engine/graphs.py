@@ -79,6 +79,10 @@ class DecodeGraphs:
             # a step with JSON-mode rows runs eagerly: the mask and advance kernels (ops/csrc/json_mask.hip) take a
             # row count that changes from step to step. The rows ride in the plan, so every TP rank decides alike
             return False
+        if sp.schema_rows is not None:
+            # likewise a step with json_schema rows (ops/csrc/json_schema.hip): its row count changes, and so may the
+            # tables its launches read
+            return False
         return not self.disabled and h.B > 0 and h.T == h.B and h.n_items == 0
 
     # ------------------------------------------------------------------------------------------------------------

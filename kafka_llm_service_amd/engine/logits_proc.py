@@ -43,6 +43,13 @@ kernel moves ``jstate[slot]`` over the drawn token right behind it, so the state
 carry no guard and never roll back, and two steps can be in flight. The host seeds a slot's record only when the row
 is sampled from a prefill — admission, or the re-prefill after a preemption or an eviction — by walking the output ids
 so far (all landed by then) through ``ref.json_advance_ref``.
+Structured outputs (``SamplingParams.json_schema``; engine/json_schema.py, ops/csrc/json_schema.hip) share those slots
+and mask rows: a schema row's record is ``(state, 0, 0, table index + 1)``, and its kernels walk the request's own
+transition table out of a device pool of ``json_slots`` buffers (``ops.SchemaTables``: 64 MiB at 256 slots, allocated
+by the first schema request — schema steps never run inside a graph, so no captured graph needs the address). Tables
+are keyed by the schema's canonical text and refcounted by live sequences; unreferenced ones stay resident in LRU
+order, so a thread that sends the same schema every turn uploads it once. With as many buffers as state slots a live
+sequence always finds one. A new table travels in ``ProcUpdates.schema_tabs`` and is loaded on every TP rank.
 Table writes (new mask rows, slot zeroing, count decrements of rolled-back tokens) are ``ProcUpdates`` applied on the stream before the step's sampler — on
 every TP rank, from the same plan, so every rank samples the same token.
 """
@@ -57,6 +64,7 @@ import torch
 # (the update record travels in a step's wire format)
 from kafka_llm_service_amd.engine.step_plan import (BIAS_ROW_INTS, COUNT_SEEN_PROMPT, JSON_STATE_INTS, LOGIT_BIAS_MAX,
                                                     ProcUpdates)
+from kafka_llm_service_amd.engine.json_schema import DEAD as SCHEMA_DEAD, SCHEMA_MAX_STATES
 
 MASK_ROWS = 512
 BIAS_ROWS = 512
@@ -126,9 +134,18 @@ class LogitsProcessor:
         self.json_table_fn = None  # () -> engine/json_mode.JsonTable of the model's tokenizer (set by the engine)
         self._json_table = None
         self._json_dev = None
+        # json_schema: the table pool (device side: apply(); host side: build()). _stabs: schema text -> buffer, in
+        # LRU order of last use; a buffer with _stab_refs 0 may be given to another schema
+        self.spool = None
+        self._stabs: OrderedDict = OrderedDict()
+        self._stab_refs: dict[int, int] = {}
+        self._stab_free: list[int] = list(range(json_slots - 1, -1, -1))
+        self._sseq: dict[int, int] = {}  # seq_id -> buffer of the sequences that hold a reference
+        self._slot_tab = np.full(max(1, json_slots), -1, dtype=np.int32)  # slot -> buffer (-1: a JSON-mode slot)
         self.stats = {"mask_uploads": 0, "proc_steps": 0, "forced_rows": 0, "mask_rows_used": 0, "penalty_rows": 0,
                       "bias_uploads": 0, "bias_rows_used": 0, "min_p_rows": 0, "rep_rows": 0, "seen_uploads": 0,
-                      "json_rows": 0, "json_seeds": 0}
+                      "json_rows": 0, "json_seeds": 0, "schema_rows": 0, "schema_seeds": 0,
+                      "schema_table_uploads": 0}
 
     # ---- tables (allocated together on first use: a captured graph sees every address) --------------------------
     def tables(self) -> tuple[torch.Tensor, torch.Tensor]:
@@ -187,17 +204,85 @@ class LogitsProcessor:
         if proc is None or not self.n_json_slots:
             return None
         idx = np.flatnonzero((proc[:, 0] == 1) & (proc[:, 1] >= self.n_mask_rows))
+        idx = idx[self._slot_tab[proc[idx, 1] - self.n_mask_rows] < 0]  # (a schema row is not a JSON-mode row)
         if not idx.size:
             return None
         return np.stack([idx, proc[idx, 1] - self.n_mask_rows], axis=1).astype(np.int32)
+
+    def schema_rows(self, proc: np.ndarray | None) -> np.ndarray | None:
+        """int32 [k, 3] (sampled row, state slot, table buffer) of the json_schema rows of ``proc``, or None."""
+        if proc is None or not self.n_json_slots:
+            return None
+        idx = np.flatnonzero((proc[:, 0] == 1) & (proc[:, 1] >= self.n_mask_rows))
+        idx = idx[self._slot_tab[proc[idx, 1] - self.n_mask_rows] >= 0]
+        if not idx.size:
+            return None
+        slots = proc[idx, 1] - self.n_mask_rows
+        return np.stack([idx, slots, self._slot_tab[slots]], axis=1).astype(np.int32)
+
+    def _json_reclaim(self) -> None:
+        """The slots, and the table references, of sequences that have finished since."""
+        for sid in [sid for sid, (_, s) in self._jslots.items() if s.finished]:
+            slot = self._jslots.pop(sid)[0]
+            self._jfree.append(slot)
+            self._slot_tab[slot] = -1
+            buf = self._sseq.pop(sid, None)
+            if buf is not None:
+                self._stab_refs[buf] -= 1
+
+    def _schema_table(self, seq, new_tabs: list) -> int:
+        """The pool buffer of the sequence's schema; a schema the pool does not hold takes a free buffer or the least
+        recently used unreferenced one, and its table joins ``new_tabs``."""
+        from kafka_llm_service_amd.engine.json_schema import compile_text
+
+        buf = self._sseq.get(seq.seq_id)
+        if buf is not None:
+            return buf
+        text = seq.params.json_schema
+        buf = self._stabs.get(text)
+        if buf is None:
+            if not self._stab_free:
+                self._json_reclaim()
+                victim = next((t for t, b in self._stabs.items() if not self._stab_refs.get(b)), None)
+                if victim is None:  # (as many buffers as slots, a slot holder references one: cannot happen)
+                    raise RuntimeError("logits processor: every schema table buffer is referenced")
+                self._stab_free.append(self._stabs.pop(victim))
+            buf = self._stab_free.pop()
+            dfa = compile_text(text)
+            self._stabs[text] = buf
+            new_tabs.append((buf, dfa.cls, dfa.trans))
+            self.stats["schema_table_uploads"] += 1
+        self._stabs.move_to_end(text)
+        self._stab_refs[buf] = self._stab_refs.get(buf, 0) + 1
+        self._sseq[seq.seq_id] = buf
+        return buf
+
+    def schema_seed(self, seq, buf: int) -> np.ndarray:
+        """The schema row's record after the sequence's output ids so far (as ``json_seed``)."""
+        from kafka_llm_service_amd.engine import json_schema as js
+        from kafka_llm_service_amd.ops import reference as ref
+
+        table, dfa, st = self.json_table(), js.compile_text(seq.params.json_schema), js.START
+        for t in seq.output_ids:
+            if t < 0:
+                raise RuntimeError("json_schema: a state is seeded from landed tokens only")
+            st = ref.schema_advance_ref(st, t, dfa, table)
+        return js.state_record(st, buf)
+
+    def schema_pool(self):
+        """The device pool of schema tables (ops.SchemaTables), allocated by the first schema step."""
+        if self.spool is None:
+            from kafka_llm_service_amd import ops
+
+            self.spool = ops.SchemaTables(max(1, self.n_json_slots), self.device)
+        return self.spool
 
     def _json_slot(self, seq) -> tuple[int, bool]:
         e = self._jslots.get(seq.seq_id)
         if e is not None:
             return e[0], False
         if not self._jfree:  # reclaim the slots of sequences that have finished since
-            for sid in [sid for sid, (_, s) in self._jslots.items() if s.finished]:
-                self._jfree.append(self._jslots.pop(sid)[0])
+            self._json_reclaim()
         if not self._jfree:
             raise RuntimeError(f"logits processor: more than {self.n_json_slots} live JSON-mode sequences")
         slot = self._jfree.pop()
@@ -305,7 +390,7 @@ class LogitsProcessor:
         upd_rows, upd_words, zero, used = [], [], [], set()
         b_rows, b_words, b_used = [], [], set()
         seen = []  # (slot, (r, inv_r), ascending distinct prompt ids) of the slots this step seeds
-        j_slots, j_states = [], []
+        j_slots, j_states, s_tabs = [], [], []
         if self._rep_seqs:
             self._release_finished_rep(zero)
         V, W = self.V, self.W
@@ -351,6 +436,18 @@ class LogitsProcessor:
                     self.stats["json_seeds"] += 1
                 proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
                 self.stats["json_rows"] += 1
+            if getattr(p, "json_schema", None) is not None:
+                if spec is not None or getattr(p, "json_mode", False):
+                    raise ValueError("json_schema and another token mask on one row: the masks are not intersected")
+                slot, new_slot = self._json_slot(s)
+                buf = self._schema_table(s, s_tabs)
+                self._slot_tab[slot] = buf
+                if new_slot or (n_decode is not None and i >= n_decode):
+                    j_slots.append(slot)
+                    j_states.append(self.schema_seed(s, buf))
+                    self.stats["schema_seeds"] += 1
+                proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
+                self.stats["schema_rows"] += 1
             rep = p.repetition_penalty
             if p.presence_penalty or p.frequency_penalty or rep != 1.0:
                 proc[i, 2], new_slot = self._slot(s, zero)
@@ -401,6 +498,7 @@ class LogitsProcessor:
         if j_slots:
             upd.json_slots = np.asarray(j_slots, dtype=np.int32)
             upd.json_states = np.stack(j_states).astype(np.int32)
+        upd.schema_tabs = s_tabs
         return proc, upd
 
     # ---- device side ----------------------------------------------------------------------------------------------
@@ -409,11 +507,17 @@ class LogitsProcessor:
         if upd is None or upd.empty:
             return
         mask_tab, counts = self.tables()
+        for buf, cls, trans in upd.schema_tabs:  # (checked by the pool: the kernels trust a table's entries)
+            self.schema_pool().load(int(buf), cls, trans, upload)
         if upd.json_slots.size:
             st = upd.json_states
+            sch = st[:, 3] != 0 if st.ndim == 2 and st.shape[1] == JSON_STATE_INTS else np.zeros(0, bool)
+            jm_st, sc_st = st[~sch] if sch.size else st, st[sch] if sch.size else st[:0]
             if st.shape != (upd.json_slots.size, JSON_STATE_INTS) or int(upd.json_slots.min()) < 0 \
-                    or int(upd.json_slots.max()) >= self.n_json_slots or (st[:, 0] < 0).any() \
-                    or (st[:, 0] > 63).any() or (st[:, 1] < 0).any() or (st[:, 1] > 32).any():
+                    or int(upd.json_slots.max()) >= self.n_json_slots or (jm_st[:, 0] < 0).any() \
+                    or (jm_st[:, 0] > 63).any() or (jm_st[:, 1] < 0).any() or (jm_st[:, 1] > 32).any() \
+                    or ((sc_st[:, 0] < 0) | ((sc_st[:, 0] >= SCHEMA_MAX_STATES) & (sc_st[:, 0] != SCHEMA_DEAD))).any() \
+                    or sc_st[:, 1:3].any() or (sc_st[:, 3] < 1).any() or (sc_st[:, 3] > self.n_json_slots).any():
                 raise ValueError("logits processor: JSON state update does not fit the state table")
             self.jstate.index_copy_(0, upload(upd.json_slots.astype(np.int64)),
                                     upload(np.ascontiguousarray(st, dtype=np.int32)))

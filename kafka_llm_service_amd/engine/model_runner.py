@@ -313,6 +313,8 @@ class ModelRunner:
             arrays.append(sp.proc)
             if sp.json_rows is not None:  # (JSON rows are proc rows: behind them)
                 arrays.append(sp.json_rows)
+            if sp.schema_rows is not None:  # (and the json_schema rows: last)
+                arrays.append(sp.schema_rows)
         dev = self.stager.upload_many(arrays)
         if len(dev) > 2:
             has_t = not sp.greedy and sp.temp.shape[0]
@@ -320,6 +322,7 @@ class ModelRunner:
             self._sp_dev = (sp, *(dev[2:5] if has_t else (None, None, None)),
                             dev[i_proc] if sp.proc is not None else None)
             self._json_dev = (sp, dev[i_proc + 1]) if sp.proc is not None and sp.json_rows is not None else None
+            self._schema_dev = (sp, dev[-1]) if sp.proc is not None and sp.schema_rows is not None else None
         return self.views(dev[0], dev[1], h)
 
     def views(self, d64: torch.Tensor, d32: torch.Tensor, h: HostStep) -> StepInput:
@@ -409,7 +412,8 @@ class ModelRunner:
                     known[i] = f
             # (min_p acts under temperature only: a greedy row needs no processing row for it)
             if allowed is not None or p.presence_penalty or p.frequency_penalty or p.logit_bias \
-                    or (p.min_p and p.temperature > 0) or p.repetition_penalty != 1.0 or p.json_mode:
+                    or (p.min_p and p.temperature > 0) or p.repetition_penalty != 1.0 or p.json_mode \
+                    or p.json_schema is not None:
                 rows.append((i, s, allowed))
         proc = upd = None
         if rows:
@@ -417,6 +421,7 @@ class ModelRunner:
             upd = None if upd.empty else upd
         sp = SampleParams(temp, topp, topk, seeds, proc, not temp.any(), upd, known)
         sp.json_rows = self.lp.json_rows(proc)
+        sp.schema_rows = self.lp.schema_rows(proc)
         if lp_rows:
             sp.lp_rows, sp.lp_k = np.asarray(lp_rows, dtype=np.int32), lp_k
         return sp
@@ -446,15 +451,27 @@ class ModelRunner:
     def sample_device(self, logits: torch.Tensor, sp: "SampleParams") -> torch.Tensor:
         """The step's sampler launch. A step with JSON rows launches the mask kernel in front of it (the rows' mask
         rows from their device states) and the advance kernel behind it (the states over the drawn ids); a step
-        without them launches exactly what it always did."""
+        with json_schema rows does the same with the kernels of ops/csrc/json_schema.hip over the requests' own tables
+        (JSON-mode mask, schema mask, sampler, then the two advances); a step without either launches exactly what it
+        always did."""
         jpre, self._json_dev = getattr(self, "_json_dev", None), None
-        if sp.json_rows is None:
+        spre, self._schema_dev = getattr(self, "_schema_dev", None), None
+        if sp.json_rows is None and sp.schema_rows is None:
             return self._sample_device(logits, sp)
-        jrows = jpre[1] if jpre is not None and jpre[0] is sp else self._h2d(sp.json_rows)
         tabs, mask_tab = self.lp.json_tables(), self.lp.tables()[0]
-        ops.json_mask(tabs, jrows, self.lp.jstate, mask_tab, self.lp.n_mask_rows)
+        jrows = srows = None
+        if sp.json_rows is not None:
+            jrows = jpre[1] if jpre is not None and jpre[0] is sp else self._h2d(sp.json_rows)
+            ops.json_mask(tabs, jrows, self.lp.jstate, mask_tab, self.lp.n_mask_rows)
+        if sp.schema_rows is not None:
+            srows = spre[1] if spre is not None and spre[0] is sp else self._h2d(sp.schema_rows)
+            ops.schema_mask(tabs, self.lp.schema_pool(), srows, logits.shape[0], self.lp.jstate, mask_tab,
+                            self.lp.n_mask_rows, used=np.unique(sp.schema_rows[:, 2]))
         toks = self._sample_device(logits, sp)
-        ops.json_advance(tabs, jrows, toks, self.lp.jstate)
+        if jrows is not None:
+            ops.json_advance(tabs, jrows, toks, self.lp.jstate)
+        if srows is not None:
+            ops.schema_advance(tabs, self.lp.schema_pool(), srows, toks, self.lp.jstate)
         return toks
 
     def _sample_device(self, logits: torch.Tensor, sp: "SampleParams") -> torch.Tensor:

@@ -58,8 +58,21 @@ class SamplingParams:
     # is allowed. The mask is built on the device from a device-resident automaton state (ops/csrc/json_mask.hip) and
     # applies last, like a tool-call mask; it is not combined with ``allowed_tokens_fn`` / ``tool_grammar``.
     json_mode: bool = False
+    # OpenAI ``response_format: {"type": "json_schema", ...}``: the canonical text of a schema of the supported subset
+    # (engine/json_schema.py), or None. Every sampled token keeps the output a prefix of one document that conforms to
+    # it; after the document only an EOS id is allowed. The schema compiles to a transition table of its own that the
+    # device kernels walk (ops/csrc/json_schema.hip); excludes ``json_mode`` and the token constraints.
+    json_schema: str | None = None
 
     def __post_init__(self):
+        if self.json_schema is not None:
+            if not isinstance(self.json_schema, str):
+                raise ValueError("json_schema must be the canonical text of a schema, or None")
+            if self.json_mode or self.allowed_tokens_fn is not None or self.tool_grammar is not None:
+                raise ValueError("json_schema cannot be combined with json_mode, a token constraint or a tool grammar")
+            from kafka_llm_service_amd.engine.json_schema import compile_text
+
+            compile_text(self.json_schema)  # (SchemaError is a ValueError; the automaton stays cached for the engine)
         if not isinstance(self.json_mode, bool):
             raise ValueError("json_mode must be a bool")
         if self.json_mode and (self.allowed_tokens_fn is not None or self.tool_grammar is not None):

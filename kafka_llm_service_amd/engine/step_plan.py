@@ -188,11 +188,15 @@ class ProcUpdates:
     # [k, JSON_STATE_INTS] their records (state id, depth, stack bits, 0); every other state change happens on the device
     json_slots: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     json_states: np.ndarray = field(default_factory=lambda: np.zeros((0, JSON_STATE_INTS), np.int32))
+    # json_schema: the tables this step loads into the device pool before its mask kernel runs, as (table index, cls
+    # uint8 [256], trans uint16 [S, C]) — a schema the pool does not hold yet (engine/json_schema.py). A schema row's
+    # seeded record rides in json_slots / json_states above as (state, 0, 0, table index + 1)
+    schema_tabs: list = field(default_factory=list)
 
     @property
     def empty(self) -> bool:
         return not (self.mask_rows.size or self.zero_slots.size or self.dec.size or self.bias_rows.size
-                    or self.seen_slots.size or self.json_slots.size)
+                    or self.seen_slots.size or self.json_slots.size or self.schema_tabs)
 
     def check_seen(self) -> None:
         """The repetition-penalty sections agree with each other (a plan on the wire, a table update)."""
@@ -220,12 +224,50 @@ class SampleParams:
     # JSON mode: int32 [k, 2] (sampled row, state-table slot) of the step's JSON rows, or None. The mask kernel runs
     # over them before the sampler and the advance kernel behind it (ops/csrc/json_mask.hip); part of the plan
     json_rows: np.ndarray | None = None
+    # json_schema: int32 [k, 3] (sampled row, state-table slot, table index) of the step's schema rows, or None; the
+    # mask and advance kernels of ops/csrc/json_schema.hip run over them around the sampler; part of the plan
+    schema_rows: np.ndarray | None = None
 
 
 _PLAN_SCALARS = ("B", "T", "nbt", "bt_w", "n_rows", "s_total", "n_dec_items", "n_prefix_items", "cascade_prefix",
                  "n_items", "prefill_splits", "n_merge", "n_late", "late_off", "bt_need", "prefix_joined")
 PLAN_HDR = 32  # int64 header of a broadcast step plan
 PLAN_PAYLOAD_IDX = 1 + len(_PLAN_SCALARS) + 4  # header word holding the payload size (pack_plan)
+PLAN_SCHEMA_IDX = PLAN_HDR - 1  # header word holding the int32 word count of the trailing json_schema section
+
+
+def _schema_section(rows: np.ndarray, tabs: list) -> np.ndarray:
+    """The plan's trailing json_schema section as int32 words; it describes its own parts: [k rows, t tables], the rows
+    [k, 3], then per table (index, S, C), cls as 64 words and trans as ceil(S * C / 2) words (zero-padded)."""
+    parts = [np.array([rows.shape[0], len(tabs)], np.int32), rows.astype(np.int32, copy=False).reshape(-1)]
+    for idx, cls, trans in tabs:
+        cls, trans = np.ascontiguousarray(cls), np.ascontiguousarray(trans)
+        if cls.shape != (256,) or cls.dtype != np.uint8 or trans.ndim != 2 or trans.dtype != np.uint16:
+            raise ValueError("plan: a schema table is cls uint8 [256] and trans uint16 [S, C]")
+        flat = trans.reshape(-1)
+        if flat.size % 2:
+            flat = np.concatenate([flat, np.zeros(1, np.uint16)])
+        parts += [np.array([idx, trans.shape[0], trans.shape[1]], np.int32), cls.view(np.int32), flat.view(np.int32)]
+    return np.concatenate(parts)
+
+
+def _schema_unsection(words: np.ndarray) -> tuple[np.ndarray, list]:
+    k, t = int(words[0]), int(words[1])
+    o = 2 + 3 * k
+    rows = words[2:o].reshape(k, 3)
+    tabs = []
+    for _ in range(t):
+        idx, S, C = (int(v) for v in words[o:o + 3])
+        n = (S * C + 1) // 2
+        if S < 1 or C < 1 or o + 3 + 64 + n > words.size:
+            raise ValueError("plan: the json_schema section does not hold its tables")
+        cls = words[o + 3:o + 67].view(np.uint8).copy()
+        trans = words[o + 67:o + 67 + n].view(np.uint16)[:S * C].reshape(S, C).copy()
+        tabs.append((idx, cls, trans))
+        o += 67 + n
+    if o != words.size:
+        raise ValueError("plan: the json_schema section is longer than its parts")
+    return rows, tabs
 
 
 def _bt_rewidth(h: HostStep, i32: np.ndarray, w_from: int, w_to: int) -> np.ndarray:
@@ -272,8 +314,16 @@ def pack_plan(h: HostStep, sp: SampleParams) -> tuple[np.ndarray, np.ndarray]:
     if upd.json_slots.size or jrows.size:  # last: seeded slots [k], their records [k, 4], the step's JSON rows [j, 2]
         parts += [upd.json_slots.astype(np.int32, copy=False), upd.json_states.astype(np.int32, copy=False),
                   jrows.astype(np.int32, copy=False)]
+    srows = sp.schema_rows if sp.schema_rows is not None else np.zeros((0, 3), np.int32)
+    if srows.ndim != 2 or srows.shape[1] != 3:
+        raise ValueError("plan: schema rows must be (sampled row, slot, table) triples")
+    n_schema = 0
+    if srows.size or upd.schema_tabs:  # the trailing section; a step without it packs to the bytes it always did
+        parts.append(_schema_section(srows, upd.schema_tabs))
+        n_schema = parts[-1].size
     payload = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in parts])
     hdr = np.zeros(PLAN_HDR, dtype=np.int64)
+    hdr[PLAN_SCHEMA_IDX] = n_schema
     hdr[0] = 1
     k = len(_PLAN_SCALARS)
     hdr[1:1 + k] = [getattr(h, f) for f in _PLAN_SCALARS]
@@ -322,6 +372,10 @@ def unpack_plan(hdr: np.ndarray, payload: np.ndarray) -> tuple[HostStep, SampleP
         upd.json_states = take(np.int32, n_jseed * JSON_STATE_INTS).reshape(n_jseed, JSON_STATE_INTS)
         jrows = take(np.int32, 2 * n_jrows).reshape(n_jrows, 2)
         sp.json_rows = jrows if n_jrows else None
+    n_schema = int(hdr[PLAN_SCHEMA_IDX])
+    if n_schema:
+        srows, upd.schema_tabs = _schema_unsection(take(np.int32, n_schema))
+        sp.schema_rows = srows if srows.shape[0] else None
     sp.proc = proc if n_proc else None
     sp.upd = None if upd.empty else upd
     return h, sp

@@ -10,8 +10,12 @@ schema: ``min_p`` in [0, 1] and ``top_k`` >= 0 (0 turns either off), the sampler
 ``repetition_penalty`` in [0.1, 10] (1 or absent: off), the multiplicative penalty of HF ``generate`` / vLLM over the
 tokens of the prompt and of the output so far. ``response_format``: ``{"type": "text"}`` (or absent) changes nothing;
 ``{"type": "json_object"}`` is JSON mode — the reply is one JSON object (the sampler masks every token that would
-break RFC 8259, the mask built on the GPU: engine/json_mode.py); ``json_schema`` and any other type are refused, and so
-is JSON mode together with ``tools`` unless ``tool_choice`` is ``"none"``.
+break RFC 8259, the mask built on the GPU: engine/json_mode.py); ``{"type": "json_schema", "json_schema": {"name"?,
+"strict"?, "description"?, "schema": {...}}}`` is structured output — the reply is one JSON document that conforms to
+``schema``, a schema of the supported subset (engine/json_schema.py: it is compiled here, so every unsupported
+keyword and every limit is a 422 naming the keyword and its JSON pointer); enforcement is always on, whatever
+``strict`` says. Any other type is refused, and so is either structured type together with ``tools`` unless
+``tool_choice`` is ``"none"``.
 """
 from __future__ import annotations
 
@@ -61,7 +65,8 @@ class ChatCompletionRequest(BaseModel):
     top_k: Optional[int] = Field(None, ge=0)
     # a logit x of a token the prompt or the output so far holds becomes x / r (x > 0) or x * r (x <= 0); 1: off
     repetition_penalty: Optional[float] = Field(None, ge=0.1, le=10)
-    # {"type": "text"} | {"type": "json_object"} (JSON mode: the reply is one JSON object)
+    # {"type": "text"} | {"type": "json_object"} (JSON mode: the reply is one JSON object) | {"type": "json_schema",
+    # "json_schema": {"schema": {...}}} (the reply conforms to the schema)
     response_format: Optional[dict[str, Any]] = None
 
     @field_validator("response_format")
@@ -71,10 +76,18 @@ class ChatCompletionRequest(BaseModel):
             return v
         t = v.get("type")
         if t == "json_schema":
-            raise ValueError('response_format type "json_schema" is not supported; the supported structured type is '
-                             '"json_object"')
+            from kafka_llm_service_amd.engine.json_schema import check_name, compile_schema
+
+            js = v.get("json_schema")
+            if not isinstance(js, dict) or not isinstance(js.get("schema"), dict):
+                raise ValueError('response_format type "json_schema" needs `json_schema.schema`, a schema object; for '
+                                 'unconstrained JSON use "json_object"')
+            if "name" in js:
+                check_name(js["name"])
+            compile_schema(js["schema"])  # (SchemaError is a ValueError: a 422 with the keyword and its pointer)
+            return v
         if t not in ("text", "json_object"):
-            raise ValueError(f'response_format type must be "text" or "json_object", not {t!r}')
+            raise ValueError(f'response_format type must be "text", "json_object" or "json_schema", not {t!r}')
         return v
 
     @field_validator("repetition_penalty", mode="before")
@@ -110,7 +123,17 @@ class ChatCompletionRequest(BaseModel):
         if self.json_mode and self.tools and self.tool_choice != "none":
             raise ValueError('response_format "json_object" cannot be combined with tools unless tool_choice is '
                              '"none" (the JSON mask and the tool-call mask are not intersected)')
+        if self.json_schema is not None and self.tools and self.tool_choice != "none":
+            raise ValueError('response_format "json_schema" cannot be combined with tools unless tool_choice is '
+                             '"none" (the schema mask and the tool-call mask are not intersected)')
         return self
+
+    @property
+    def json_schema(self) -> Optional[dict]:
+        """The schema object of a ``json_schema`` response format, else None."""
+        if self.response_format and self.response_format.get("type") == "json_schema":
+            return self.response_format["json_schema"]["schema"]
+        return None
 
     @property
     def json_mode(self) -> bool:

@@ -174,11 +174,24 @@ class EngineLLMProvider(LLMProvider):
         ``response_format`` ``{"type": "json_object"}``: JSON mode — the engine masks every token that would keep the
         reply from being one JSON object, and once the object has closed allows only an end-of-sequence id, so the
         reply finishes with "stop" when the document closed and with "length" when ``max_tokens`` cut it. The mask
-        applies last, like a tool-call mask, and replaces it: a JSON-mode request decodes no tool call."""
+        applies last, like a tool-call mask, and replaces it: a JSON-mode request decodes no tool call.
+        ``{"type": "json_schema", "json_schema": {"schema": {...}}}`` does the same against the schema's automaton."""
         json_mode = (response_format or {}).get("type") == "json_object"
-        if response_format and not json_mode and response_format.get("type") != "text":
-            raise LLMProviderError('response_format type must be "text" or "json_object"', provider="engine",
-                                   status_code=400)
+        json_schema = None
+        if (response_format or {}).get("type") == "json_schema":
+            # structured output: the engine takes the canonical schema text and walks the schema's own automaton
+            # (engine/json_schema.py); like JSON mode it replaces the tool-call mask
+            from kafka_llm_service_amd.engine.json_schema import SchemaError, canonical_text, compile_schema
+
+            try:
+                schema = response_format["json_schema"]["schema"]
+                compile_schema(schema)
+                json_schema = canonical_text(schema)
+            except (KeyError, TypeError, SchemaError) as e:
+                raise LLMProviderError(f"response_format json_schema: {e}", provider="engine", status_code=400)
+        elif response_format and not json_mode and response_format.get("type") != "text":
+            raise LLMProviderError('response_format type must be "text", "json_object" or "json_schema"',
+                                   provider="engine", status_code=400)
         self.validate_messages(messages)
         bias = None
         if logit_bias:
@@ -208,9 +221,10 @@ class EngineLLMProvider(LLMProvider):
                                 presence_penalty=float(presence_penalty or 0.0), seed=seed,
                                 ignore_eos=self.ignore_eos, logprobs=bool(logprobs),
                                 top_logprobs=int(top_logprobs or 0) if logprobs else 0, logit_bias=bias,
-                                json_mode=json_mode,
+                                json_mode=json_mode, json_schema=json_schema,
                                 tool_grammar=({"tools": tools, "tool_choice": self._choice(tool_choice, messages)}
-                                              if tools and self.constrain_tools and not json_mode else None))
+                                              if tools and self.constrain_tools and not json_mode
+                                              and json_schema is None else None))
         stops = [s for s in (stop or []) if s]
         hold = max((len(s) for s in stops), default=1) - 1
         rid = f"req-{uuid.uuid4().hex}"

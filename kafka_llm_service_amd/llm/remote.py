@@ -69,6 +69,8 @@ class RemoteOpenAIProvider(LLMProvider):
             body["repetition_penalty"] = kw["repetition_penalty"]
         if (kw.get("response_format") or {}).get("type") == "json_object":  # (absent or "text" sends nothing)
             body["response_format"] = {"type": "json_object"}
+        elif (kw.get("response_format") or {}).get("type") == "json_schema":
+            body["response_format"] = kw["response_format"]
         return body
 
     async def stream_completion(self, messages: list[Message], *, temperature: Optional[float] = None,

@@ -8,6 +8,7 @@ Kernel inventory:
   sample (greedy / temperature / top-k / top-p) csrc/sampling.hip
   token_logprobs (logprob + top-k alternatives) csrc/logprobs.hip
   json_mask / json_advance (JSON-mode masks)    csrc/json_mask.hip
+  schema_mask / schema_advance (json_schema)    csrc/json_schema.hip
   moe_* / grouped GEMM                          csrc/moe.hip
   custom all-reduce                             csrc/allreduce.hip
 """
@@ -292,6 +293,113 @@ def json_advance(tabs: JsonTables, rows, sampled, state) -> None:
     for r, slot in rows.tolist():
         st = ref.json_advance_ref(jm.record_state(state[slot].numpy()), int(sampled[r]), tabs.table)
         state[slot] = torch.from_numpy(jm.state_record(st))
+
+
+SCHEMA_MASK_TOKENS = 1024  # tokens one workgroup of schema_mask_kernel walks per staged table (a multiple of 256; measured)
+SCHEMA_MASK_DWORD = True   # token bytes through aligned 4-byte loads
+
+
+class SchemaTables:
+    """The device pool of compiled schema tables (engine/json_schema.SchemaDfa) the structured-output ops read:
+    ``strans`` uint16 [n, SCHEMA_TAB_BYTES / 2], ``scls`` uint8 [n, 256], ``sdim`` int32 [n, 2] = (S, C). The host keeps
+    each loaded table (``dfas``: the CPU path walks it through the reference) and so knows which kernel instantiations
+    a launch needs."""
+
+    def __init__(self, n: int, device):
+        from kafka_llm_service_amd.engine import json_schema as js
+
+        if n < 1:
+            raise ValueError("schema tables: the pool needs at least one buffer")
+        self.n, self.device = int(n), torch.device(device)
+        self.strans = torch.zeros(self.n, js.SCHEMA_TAB_BYTES // 2, dtype=torch.uint16, device=self.device)
+        self.scls = torch.zeros(self.n, 256, dtype=torch.uint8, device=self.device)
+        self.sdim = torch.zeros(self.n, 2, dtype=torch.int32, device=self.device)
+        self.dfas: list = [None] * self.n
+
+    def load(self, idx: int, cls, trans, upload=None) -> None:
+        """Buffer ``idx`` becomes the table (``cls`` uint8 [256], ``trans`` uint16 [S, C]); ``upload``: numpy ->
+        device tensor (default: a plain copy). The table is checked here: the kernels trust its entries."""
+        from kafka_llm_service_amd.engine import json_schema as js
+
+        cls, trans = np.array(cls), np.array(trans)  # (own, writable, contiguous copies)
+        if not 0 <= int(idx) < self.n:
+            raise ValueError(f"schema tables: buffer {idx} outside the pool of {self.n}")
+        js.check_tables(cls, trans)
+        up = upload or (lambda a: torch.from_numpy(a).to(self.device))
+        S, C = trans.shape
+        # one H2D copy of (S, C), cls and trans as int32 words, the type every upload path knows (an odd table is padded
+        # by one zero entry, still inside its buffer), then three device copies into the pool
+        flat = trans.reshape(-1)
+        if flat.size % 2:
+            flat = np.concatenate([flat, np.zeros(1, np.uint16)])
+        dev = up(np.concatenate([np.array([S, C], np.int32), cls.view(np.int32), flat.view(np.int32)]))
+        self.sdim[idx].copy_(dev[:2])
+        self.scls[idx].view(torch.int32).copy_(dev[2:66])
+        self.strans[idx].view(torch.int32)[:flat.size // 2].copy_(dev[66:])
+        self.dfas[idx] = js.SchemaDfa(cls, trans, "")
+
+    def kinds(self, used=None) -> tuple[int, int]:
+        """(bit 0: a table is staged in LDS; bit 1: one is walked in global memory, the LDS bytes a launch allocates:
+        the largest table that fits SCHEMA_LDS_BYTES, rounded up to 16) over the buffers ``used`` — the tables a
+        launch's rows name, when the caller knows them on the host — or over every loaded buffer."""
+        from kafka_llm_service_amd.engine import json_schema as js
+
+        k = lds = 0
+        for d in (self.dfas if used is None else [self.dfas[int(t)] for t in used if 0 <= int(t) < self.n]):
+            if d is not None:
+                if d.nbytes <= js.SCHEMA_LDS_BYTES:
+                    k, lds = k | 1, max(lds, (d.nbytes + 15) & ~15)
+                else:
+                    k |= 2
+        return k, lds
+
+
+def _schema_check(pool: SchemaTables, rows, state, n_sampled: int) -> np.ndarray:
+    """The values the kernels guard against (CPU tensors only, as ``_json_check``); returns the rows as numpy."""
+    r = rows.reshape(-1, 3).numpy()
+    if r.size and (r.min() < 0 or r[:, 0].max() >= n_sampled or r[:, 1].max() >= state.shape[0]
+                   or r[:, 2].max() >= pool.n or any(pool.dfas[t] is None for t in r[:, 2].tolist())
+                   or (state[r[:, 1].tolist(), 3].numpy() != r[:, 2] + 1).any()):
+        raise ValueError("schema: a row names a sampled row, a slot or a table outside its array, or a slot whose "
+                         "record belongs to another table")
+    return r
+
+
+def schema_mask(tabs: JsonTables, pool: SchemaTables, rows, n_sampled: int, state, mask_tab, json_row0: int,
+                tokens: int | None = None, dword: bool | None = None, used=None) -> None:
+    """For every (sampled row, slot, table) of ``rows`` (int32 [k, 3]): row ``json_row0 + slot`` of ``mask_tab`` becomes
+    the vocabulary mask of the slot's schema state ``state[slot, 0]`` over table ``table`` of ``pool`` —
+    ``ref.schema_mask_ref`` word for word. ``tabs`` supplies the token bytes and the EOS ids. ``used``: the distinct
+    table buffers the rows name, if the host knows them (the engine does): the launch's LDS is then sized by those
+    tables, not by everything the pool still holds. Launches nothing for k = 0."""
+    if rows.shape[0] == 0:
+        return
+    if _gpu(mask_tab):
+        ext().schema_mask(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, tabs.eos, rows,
+                          int(n_sampled), state, mask_tab, int(json_row0), *pool.kinds(used),
+                          int(tokens or SCHEMA_MASK_TOKENS), SCHEMA_MASK_DWORD if dword is None else bool(dword))
+        return
+    r = _schema_check(pool, rows, state, n_sampled)
+    W = tabs.table.W
+    if json_row0 < 0 or json_row0 + state.shape[0] > mask_tab.shape[0] or mask_tab.shape[1] < W:
+        raise ValueError("schema_mask: the mask table does not hold the slots' rows")
+    for _, slot, t in r.tolist():
+        words = ref.schema_mask_ref(int(state[slot, 0]) & 0xFFFFFFFF, pool.dfas[t], tabs.table)
+        mask_tab[json_row0 + slot, :W] = torch.from_numpy(words.view(np.int32).copy())
+
+
+def schema_advance(tabs: JsonTables, pool: SchemaTables, rows, sampled, state) -> None:
+    """Behind the sampler: ``state[slot, 0]`` of every row advances over the bytes of the id ``sampled[row]`` (int64)
+    — ``ref.schema_advance_ref``; the record's other words stay. Launches nothing for k = 0."""
+    if rows.shape[0] == 0:
+        return
+    if _gpu(state):
+        ext().schema_advance(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, rows, sampled, state)
+        return
+    r = _schema_check(pool, rows, state, sampled.shape[0])
+    for row, slot, t in r.tolist():
+        state[slot, 0] = ref.schema_advance_ref(int(state[slot, 0]) & 0xFFFFFFFF, int(sampled[row]), pool.dfas[t],
+                                                tabs.table)
 
 
 LOGPROBS_MAX_K = 20      # OpenAI's top_logprobs bound; the kernel's register / LDS budget (csrc/logprobs.hip)

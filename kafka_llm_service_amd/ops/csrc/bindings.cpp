@@ -441,6 +441,71 @@ static void json_advance(at::Tensor trans, at::Tensor tok_off, at::Tensor tok_by
                                       (int)jstate.size(0), cur_stream()));
 }
 
+// Structured outputs (json_schema.hip): the shared checks of the table pool, the token bytes, the rows and the state
+// table, then the two launches.
+static int schema_check_tables(const at::Tensor& strans, const at::Tensor& scls, const at::Tensor& sdim,
+                               const at::Tensor& tok_off, const at::Tensor& tok_bytes, const at::Tensor& srows,
+                               const at::Tensor& jstate) {
+  TORCH_CHECK(strans.is_cuda() && strans.scalar_type() == at::kUInt16 && strans.is_contiguous() && strans.dim() == 2 &&
+                  strans.size(0) >= 1 && strans.size(1) == kafka::SCHEMA_TAB_BYTES / 2,
+              "schema: strans must be uint16 [n, SCHEMA_TAB_BYTES / 2] on the GPU");
+  TORCH_CHECK(scls.is_cuda() && scls.scalar_type() == at::kByte && scls.is_contiguous() && scls.dim() == 2 &&
+                  scls.size(0) == strans.size(0) && scls.size(1) == 256,
+              "schema: scls must be uint8 [n, 256] on the GPU");
+  TORCH_CHECK(sdim.is_cuda() && sdim.scalar_type() == at::kInt && sdim.is_contiguous() && sdim.dim() == 2 &&
+                  sdim.size(0) == strans.size(0) && sdim.size(1) == 2,
+              "schema: sdim must be int32 [n, 2] on the GPU");
+  TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.dim() == 1 &&
+                  tok_off.numel() >= 2,
+              "schema: tok_off must be int32 [V + 1] on the GPU");
+  TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
+                  tok_bytes.numel() >= 4 && reinterpret_cast<uintptr_t>(tok_bytes.data_ptr()) % 4 == 0,
+              "schema: tok_bytes must be uint8 on the GPU, 4-byte aligned and padded by 4 bytes");
+  TORCH_CHECK(srows.is_cuda() && srows.scalar_type() == at::kInt && srows.is_contiguous() && srows.dim() == 2 &&
+                  srows.size(1) == 3,
+              "schema: rows must be int32 [k, 3] (sampled row, slot, table) on the GPU");
+  TORCH_CHECK(jstate.is_cuda() && jstate.scalar_type() == at::kInt && jstate.is_contiguous() && jstate.dim() == 2 &&
+                  jstate.size(1) == kafka::JSON_STATE_INTS,
+              "schema: the state table must be int32 [slots, 4] on the GPU");
+  return (int)(tok_off.numel() - 1);
+}
+
+static void schema_mask(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off, at::Tensor tok_bytes,
+                        at::Tensor eos, at::Tensor srows, int64_t n_sampled, at::Tensor jstate, at::Tensor mask_tab,
+                        int64_t json_row0, int64_t kinds, int64_t lds_bytes, int64_t tokens, bool dword) {
+  const int V = schema_check_tables(strans, scls, sdim, tok_off, tok_bytes, srows, jstate);
+  TORCH_CHECK(eos.is_cuda() && eos.scalar_type() == at::kInt && eos.is_contiguous() &&
+                  eos.numel() <= kafka::JSON_MAX_EOS,
+              "schema_mask: eos must be int32 [<= 8] on the GPU");
+  TORCH_CHECK(mask_tab.is_cuda() && mask_tab.scalar_type() == at::kInt && mask_tab.is_contiguous() &&
+                  mask_tab.dim() == 2 && mask_tab.size(1) * 32 >= V && json_row0 >= 0 &&
+                  json_row0 + jstate.size(0) <= mask_tab.size(0),
+              "schema_mask: mask_tab must be int32 [>= json_row0 + slots, >= V / 32] on the GPU");
+  TORCH_CHECK(n_sampled >= 0 && n_sampled <= INT32_MAX && kinds >= 0 && kinds <= 3 && tokens >= 256 &&
+                  tokens <= (1 << 20) && tokens % 256 == 0 && lds_bytes >= 0 &&
+                  lds_bytes <= kafka::SCHEMA_LDS_BYTES && lds_bytes % 16 == 0,
+              "schema_mask: kinds must be in 0..3, lds_bytes a multiple of 16 up to SCHEMA_LDS_BYTES and tokens a "
+              "multiple of 256");
+  CHECK_HIP(kafka_launch_schema_mask(
+      strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(), (int)strans.size(0),
+      tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V, eos.data_ptr<int>(), (int)eos.numel(),
+      srows.data_ptr<int>(), (int)srows.size(0), (int)n_sampled, jstate.data_ptr<int>(), (int)jstate.size(0),
+      reinterpret_cast<uint32_t*>(mask_tab.data_ptr<int>()), mask_tab.size(1), mask_tab.size(0), (int)json_row0,
+      (int)kinds, (int)lds_bytes, (int)tokens, dword ? 1 : 0, cur_stream()));
+}
+
+static void schema_advance(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off,
+                           at::Tensor tok_bytes, at::Tensor srows, at::Tensor sampled, at::Tensor jstate) {
+  const int V = schema_check_tables(strans, scls, sdim, tok_off, tok_bytes, srows, jstate);
+  TORCH_CHECK(sampled.is_cuda() && sampled.scalar_type() == at::kLong && sampled.is_contiguous() && sampled.dim() == 1,
+              "schema_advance: the sampled ids must be int64 [n] on the GPU");
+  CHECK_HIP(kafka_launch_schema_advance(strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(),
+                                        (int)strans.size(0), tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V,
+                                        srows.data_ptr<int>(), (int)srows.size(0), sampled.data_ptr<int64_t>(),
+                                        (int)sampled.numel(), jstate.data_ptr<int>(), (int)jstate.size(0),
+                                        cur_stream()));
+}
+
 // Per-token logprobs (logprobs.hip). rows: int32 [R] or none (rows 0..R-1); tok_lp f32 [R], top_lp f32 [R, K] and
 // top_id int32 [R, K] share one row stride (views of one packed record buffer). The row ids are trusted (the Python
 // op range-checks a host list before uploading it); everything the kernel indexes by them is sized for every row.
@@ -1071,6 +1136,13 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("rows"), py::arg("state"), py::arg("mask_tab"), py::arg("json_row0"));
   m.def("json_advance", &json_advance, py::arg("trans"), py::arg("tok_off"), py::arg("tok_bytes"), py::arg("rows"),
         py::arg("sampled"), py::arg("state"));
+  m.def("schema_mask", &schema_mask, py::arg("strans"), py::arg("scls"), py::arg("sdim"), py::arg("tok_off"),
+        py::arg("tok_bytes"), py::arg("eos"), py::arg("rows"), py::arg("n_sampled"), py::arg("state"),
+        py::arg("mask_tab"), py::arg("json_row0"), py::arg("kinds") = 3,
+        py::arg("lds_bytes") = (int64_t)kafka::SCHEMA_LDS_BYTES, py::arg("tokens") = 1024,
+        py::arg("dword") = true);
+  m.def("schema_advance", &schema_advance, py::arg("strans"), py::arg("scls"), py::arg("sdim"), py::arg("tok_off"),
+        py::arg("tok_bytes"), py::arg("rows"), py::arg("sampled"), py::arg("state"));
   m.def("token_logprobs", &token_logprobs, py::arg("logits"), py::arg("tokens"), py::arg("rows"), py::arg("k"),
         py::arg("tok_lp"), py::arg("top_lp"), py::arg("top_id"), py::arg("ws") = py::none(), py::arg("nsplit") = 1);
   m.def("wstream_plan", &wstream_plan);

@@ -69,6 +69,16 @@ constexpr int JSON_MAX_DEPTH = 32;  // open containers; the stack is one bit per
 constexpr int JSON_MAX_EOS = 8;     // EOS ids the mask kernel compares a token with in DONE
 constexpr int JSON_EXPECT_KEY = 2, JSON_EXPECT_VALUE = 4, JSON_DONE = 7;
 
+// ---- structured outputs (json_schema.hip; engine/json_schema.py compiles a schema to cls uint8 [256] + trans uint16
+// [S, C]) ---------------------------------------------------------------------------------------------------------------
+// A schema row's record in the same state table is (state, 0, 0, table index + 1): word 3 is 0 for a JSON-mode row.
+constexpr int SCHEMA_MAX_STATES = 8192;        // states of one compiled automaton
+constexpr int SCHEMA_TAB_BYTES = 256 * 1024;   // one table of the device pool: S * C * 2 bytes at most
+// up to here the mask kernel stages the table in LDS: with the 256 B of cls, 160 KiB / 8, so eight 256-thread workgroups
+// (the CU's 32 waves) stay resident; at 32 KiB (four per CU) the LDS path measured slower than the global-memory walk
+constexpr int SCHEMA_LDS_BYTES = 20 * 1024 - 256;
+constexpr int SCHEMA_DEAD = 0xFFFF, SCHEMA_DONE = 1;  // (START is 0)
+
 // ---- weight tile formats of the streaming GEMMs (wstream_gemm.hip WFMT; ops.WEIGHT_FORMATS) ----------------------
 // bf16 tiles [N/32][K/16][64 lanes][8]; fp8: e4m3 bytes [N/32][K/32][64][16] + fp32 row scales [N]; MXFP4: e2m1 bytes
 // [N/32][K/64][64][16] + e8m0 block exponents [N/32][K/64][32][2]
@@ -188,6 +198,24 @@ hipError_t kafka_launch_json_mask(const uint8_t* trans, const int* tok_off, cons
 hipError_t kafka_launch_json_advance(const uint8_t* trans, const int* tok_off, const uint8_t* tok_bytes, int V,
                                      const int* jrows, int n_rows, const int64_t* sampled, int n_sampled, int* jstate,
                                      int n_slots, hipStream_t st);
+
+// ---- json_schema.hip
+// The masks and the advance of the step's schema rows, as the two JSON-mode launches above but over per-request
+// tables: strans uint16 [n_tabs, SCHEMA_TAB_BYTES / 2], scls uint8 [n_tabs, 256], sdim int32 [n_tabs, 2] = (S, C);
+// srows int32 [n_rows, 3]: (sampled row, slot, table). tok_bytes needs 4 readable bytes behind the last token and a
+// 4-byte aligned address. kinds: bit 0 launches the instantiation with the table in LDS (S * C * 2 <= lds_bytes <=
+// SCHEMA_LDS_BYTES, a multiple of 16: what the launch allocates), bit 1 the one that walks it in global memory; each
+// skips the other's rows. tokens: tokens of one
+// workgroup (a multiple of 256); dword: read token bytes through aligned 4-byte loads.
+hipError_t kafka_launch_schema_mask(const uint16_t* strans, const uint8_t* scls, const int* sdim, int n_tabs,
+                                    const int* tok_off, const uint8_t* tok_bytes, int V, const int* eos, int n_eos,
+                                    const int* srows, int n_rows, int n_sampled, const int* jstate, int n_slots,
+                                    uint32_t* mask_tab, int64_t mask_ld, int64_t mask_rows, int json_row0, int kinds,
+                                    int lds_bytes, int tokens, int dword, hipStream_t st);
+hipError_t kafka_launch_schema_advance(const uint16_t* strans, const uint8_t* scls, const int* sdim, int n_tabs,
+                                       const int* tok_off, const uint8_t* tok_bytes, int V, const int* srows,
+                                       int n_rows, const int64_t* sampled, int n_sampled, int* jstate, int n_slots,
+                                       hipStream_t st);
 
 // ---- logprobs.hip
 // Log softmax of the RAW logits (no temperature / penalties / mask) at each scored row's sampled token, and the row's

@@ -1046,3 +1046,57 @@ def json_mask_ref(state, table) -> np.ndarray:
             stk[live] = np.where(dead, kl, nk)
         keep[:V] = (table.lens > 0) & (s != jm.DEAD)
     return np.packbits(keep, bitorder="little").view("<u4")
+
+
+# ---- structured outputs: the walk of a compiled schema automaton (engine/json_schema.py), token masks and advance ------
+# A state is one integer: START 0, DONE 1, DEAD 0xFFFF; ``dfa`` holds ``cls`` uint8 [256] and ``trans`` uint16 [S, C].
+# csrc/json_schema.hip is held to these three functions bit for bit.
+def schema_walk(state: int, data: bytes, dfa) -> int:
+    """The state after reading ``data`` from ``state``: ``s = trans[s, cls[b]]`` per byte, DEAD as soon as a byte is
+    rejected. DONE has no outgoing edge; a state at or above S that is not DONE walks as DEAD."""
+    from kafka_llm_service_amd.engine import json_schema as js
+
+    s = int(state)
+    if s >= dfa.S:
+        s = js.DEAD
+    for b in data:
+        if s == js.DEAD:
+            break
+        s = int(dfa.trans[s, dfa.cls[b]])
+    return s
+
+
+def schema_advance_ref(state: int, token: int, dfa, table) -> int:
+    """The row's state after ``token`` (``table``: engine/json_mode.JsonTable): DONE stays DONE whatever the id;
+    elsewhere an id without bytes or outside the vocabulary gives DEAD."""
+    from kafka_llm_service_amd.engine import json_schema as js
+
+    s, token = int(state), int(token)
+    if s == js.DONE:
+        return s
+    if s >= dfa.S or not 0 <= token < table.V or table.lens[token] == 0:
+        return js.DEAD
+    return schema_walk(s, table.bytes_of(token), dfa)
+
+
+def schema_mask_ref(state: int, dfa, table) -> np.ndarray:
+    """uint32 [ceil(V / 32)], the bit layout and the rules of ``json_mask_ref``: in DONE the table's EOS ids; elsewhere
+    the ids with at least one byte whose bytes are all accepted in sequence from ``state``."""
+    from kafka_llm_service_amd.engine import json_schema as js
+
+    V, s0 = table.V, int(state)
+    keep = np.zeros(table.W * 32, dtype=bool)
+    if s0 == js.DONE:
+        keep[table.eos_ids] = True
+    elif s0 < dfa.S:
+        s = np.full(V, s0, dtype=np.int64)
+        off = table.tok_off[:-1].astype(np.int64)
+        live = np.flatnonzero(table.lens > 0)
+        trans, cls = dfa.trans.astype(np.int64), dfa.cls.astype(np.int64)
+        for j in range(int(table.lens.max())):
+            live = live[(table.lens[live] > j) & (s[live] != js.DEAD)]
+            if not live.size:
+                break
+            s[live] = trans[s[live], cls[table.tok_bytes[off[live] + j]]]
+        keep[:V] = (table.lens > 0) & (s != js.DEAD)
+    return np.packbits(keep, bitorder="little").view("<u4")

@@ -122,6 +122,8 @@ def _sampling_kwargs(req: ChatCompletionRequest) -> dict[str, Any]:
         kw["repetition_penalty"] = float(req.repetition_penalty)
     if req.json_mode:  # ({"type": "text"} or absent: nothing new goes down)
         kw["response_format"] = {"type": "json_object"}
+    elif req.json_schema is not None:  # (validated and compiled by the request schema)
+        kw["response_format"] = {"type": "json_schema", "json_schema": dict(req.response_format["json_schema"])}
     return kw
 
 
