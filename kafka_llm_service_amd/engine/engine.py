@@ -72,6 +72,9 @@ class EngineConfig:
     # e8m0 exponent per block: 4.25 bits per weight; same semantics).
     # fp8 and mxfp4 need the streaming decode GEMM (auto resolves to stream); env KAFKA_WEIGHT_DTYPE overrides
     weight_dtype: str = "bf16"          # bf16 | fp8 | mxfp4
+    # the default of SamplingParams.tool_grammar["mode"]: "program" (engine/constrained.py) or "automaton"
+    # (engine/tool_automaton.py: the call body's automaton masked on the device); env KAFKA_TOOL_GRAMMAR overrides
+    tool_grammar: str = "program"
     async_scheduling: bool = True       # plan step n+1 on the host while step n runs on the GPU
     # Mixtral data-parallel attention (engine/dp_attention.py): this rank serves its own sequences with whole
     # attention weights; experts are sharded over parallel.state's EP group and every step runs in lockstep with
@@ -277,9 +280,24 @@ class LLMEngine:
             from kafka_llm_service_amd.engine.constrained import ToolCallConstraint
             from kafka_llm_service_amd.engine.tokenizer import tokenizer_for_model
 
+            from kafka_llm_service_amd.engine import tool_automaton as ta
+
             g = params.tool_grammar
-            c = ToolCallConstraint(tokenizer_for_model(self.model_cfg), g.get("tools") or [], g.get("tool_choice"))
-            params = replace(params, allowed_tokens_fn=c, stop_token_ids=list(params.stop_token_ids) + [c.end])
+            plan = None
+            if ta.grammar_mode(g, os.environ.get("KAFKA_TOOL_GRAMMAR") or self.cfg.tool_grammar) == "automaton":
+                # the body compiled from the tools' own schemas; a tool set that does not compile raises here and the
+                # request is refused (tool_choice "none" has no body: the host mask below)
+                plan = ta.plan_for(tokenizer_for_model(self.model_cfg), g.get("tools") or [], g.get("tool_choice"))
+            if plan is not None:
+                if not self.runner.lp.n_json_slots:
+                    raise ValueError("the automaton tool grammar needs the logits processor's state slots")
+                params = replace(params, tool_plan=plan, stop_token_ids=list(params.stop_token_ids) + [plan.close])
+            else:
+                c = ToolCallConstraint(tokenizer_for_model(self.model_cfg), g.get("tools") or [],
+                                       g.get("tool_choice"))
+                if g.get("mode") == "automaton":  # (tool_choice "none": the host mask serves the request)
+                    params = replace(params, tool_grammar={**g, "mode": "program"})
+                params = replace(params, allowed_tokens_fn=c, stop_token_ids=list(params.stop_token_ids) + [c.end])
         seq = Sequence(request_id, prompt_ids, params, meta)
         if self.stop_checker_factory is not None and params.stop:
             seq.stop_checker = self.stop_checker_factory(params)

@@ -79,6 +79,9 @@ class DecodeGraphs:
             # a step with JSON-mode rows runs eagerly: the mask and advance kernels (ops/csrc/json_mask.hip) take a
             # row count that changes from step to step. The rows ride in the plan, so every TP rank decides alike
             return False
+        if sp.tool_rows is not None:
+            # and a step with automaton tool rows (ops/csrc/tool_grammar.hip), for the same reasons
+            return False
         if sp.schema_rows is not None:
             # likewise a step with json_schema rows (ops/csrc/json_schema.hip): its row count changes, and so may the
             # tables its launches read

@@ -87,9 +87,13 @@ def check_name(name) -> None:
 class _Nfa:
     """States are integers; ``edges[s]`` is a list of (byte-set as a 256-bit int, target), ``eps[s]`` of targets."""
 
-    def __init__(self):
+    def __init__(self, compact: bool = False, utf8: bool = True):
         self.edges: list[list[tuple[int, int]]] = []
         self.eps: list[list[int]] = []
+        # engine/tool_automaton.py: ``compact`` leaves out every whitespace loop (the json.dumps(separators=(",", ":"))
+        # shape); without ``utf8`` a string takes the bytes from 0x80 up one by one (byte-level BPE tokens split UTF-8
+        # sequences). The defaults build the tables of response_format json_schema
+        self.compact, self.utf8 = compact, utf8
 
     def new(self) -> int:
         if len(self.edges) >= _NFA_MAX:
@@ -102,7 +106,8 @@ class _Nfa:
         self.edges[a].append((m, b))
 
     def ws(self, a: int) -> int:
-        self.edges[a].append((_M_WS, a))
+        if not self.compact:
+            self.edges[a].append((_M_WS, a))
         return a
 
     def lit(self, a: int, data: bytes, b: int) -> None:
@@ -114,6 +119,8 @@ class _Nfa:
 
     def string(self, a: int, b: int) -> None:
         """JSON mode's string (engine/json_mode.py, the V_* states) from the opening quote at a to b."""
+        if not self.utf8:
+            return self._byte_string(a, b)
         n = self.new
         st, esc, u1, u2, u3, u4 = n(), n(), n(), n(), n(), n()
         c1, c2, c3, e0, ed, f0, f4 = n(), n(), n(), n(), n(), n(), n()
@@ -140,6 +147,19 @@ class _Nfa:
         e(ed, _mask(range(0x80, 0xA0)), c1)
         e(f0, _mask(range(0x90, 0xC0)), c2)
         e(f4, _mask(range(0x80, 0x90)), c2)
+
+    def _byte_string(self, a: int, b: int) -> None:
+        """The same string with every byte from 0x80 up taken as it comes."""
+        st, esc, u1, u2, u3, u4 = (self.new() for _ in range(6))
+        e = self.edge
+        e(a, 1 << 0x22, st)
+        e(st, _M_PLAIN | _mask(range(0x80, 0x100)), st)
+        e(st, 1 << 0x22, b)
+        e(st, 1 << 0x5C, esc)
+        e(esc, _mask(b'"\\/bfnrt'), st)
+        e(esc, 1 << 0x75, u1)
+        for x, y in ((u1, u2), (u2, u3), (u3, u4), (u4, st)):
+            e(x, _M_HEX, y)
 
     def number(self, a: int, b: int, integer: bool) -> None:
         """-?(0|[1-9][0-9]*) and, for a number, (\\.[0-9]+)?([eE][+-]?[0-9]+)? — it ends where b's bytes begin."""
@@ -173,8 +193,8 @@ def _dumps(v) -> bytes:
 
 
 class _Builder:
-    def __init__(self, root: dict):
-        self.nfa = _Nfa()
+    def __init__(self, root: dict, nfa: "_Nfa | None" = None):
+        self.nfa = nfa if nfa is not None else _Nfa()
         self.defs = root.get("$defs", {})
         if not isinstance(self.defs, dict):
             raise SchemaError("schema: `$defs` at #/$defs must be an object")

@@ -50,6 +50,12 @@ by the first schema request — schema steps never run inside a graph, so no cap
 are keyed by the schema's canonical text and refcounted by live sequences; unreferenced ones stay resident in LRU
 order, so a thread that sends the same schema every turn uploads it once. With as many buffers as state slots a live
 sequence always finds one. A new table travels in ``ProcUpdates.schema_tabs`` and is loaded on every TP rank.
+The automaton tool grammar (``SamplingParams.tool_plan``; engine/tool_automaton.py, ops/csrc/tool_grammar.hip) takes a
+slot and a mask row from the same space and a buffer of the same pool, under a key no schema text equals; its record is
+``(state, phase, 0, table index + 1)``, seeded as TOOL_FREE or TOOL_OPEN and replayed over the landed output ids after a
+preemption. Under ``tool_choice: "auto"`` the host drops the row from the tool rows once the first output id has landed
+and does not open a call: from then on it is an unconstrained row. New tables, seeds and the row list ride in
+``ProcUpdates.tool_tabs`` / ``tool_slots`` / ``tool_states`` and ``SampleParams.tool_rows``.
 Table writes (new mask rows, slot zeroing, count decrements of rolled-back tokens) are ``ProcUpdates`` applied on the stream before the step's sampler — on
 every TP rank, from the same plan, so every rank samples the same token.
 """
@@ -65,6 +71,7 @@ import torch
 from kafka_llm_service_amd.engine.step_plan import (BIAS_ROW_INTS, COUNT_SEEN_PROMPT, JSON_STATE_INTS, LOGIT_BIAS_MAX,
                                                     ProcUpdates)
 from kafka_llm_service_amd.engine.json_schema import DEAD as SCHEMA_DEAD, SCHEMA_MAX_STATES
+from kafka_llm_service_amd.engine.tool_automaton import TOOL_PHASES, tool_row_live
 
 MASK_ROWS = 512
 BIAS_ROWS = 512
@@ -142,10 +149,12 @@ class LogitsProcessor:
         self._stab_free: list[int] = list(range(json_slots - 1, -1, -1))
         self._sseq: dict[int, int] = {}  # seq_id -> buffer of the sequences that hold a reference
         self._slot_tab = np.full(max(1, json_slots), -1, dtype=np.int32)  # slot -> buffer (-1: a JSON-mode slot)
+        # slot -> (open id, close id) of an automaton tool row (engine/tool_automaton.py), -1 for every other slot
+        self._slot_tool = np.full((max(1, json_slots), 2), -1, dtype=np.int32)
         self.stats = {"mask_uploads": 0, "proc_steps": 0, "forced_rows": 0, "mask_rows_used": 0, "penalty_rows": 0,
                       "bias_uploads": 0, "bias_rows_used": 0, "min_p_rows": 0, "rep_rows": 0, "seen_uploads": 0,
                       "json_rows": 0, "json_seeds": 0, "schema_rows": 0, "schema_seeds": 0,
-                      "schema_table_uploads": 0}
+                      "schema_table_uploads": 0, "tool_rows": 0, "tool_seeds": 0}
 
     # ---- tables (allocated together on first use: a captured graph sees every address) --------------------------
     def tables(self) -> tuple[torch.Tensor, torch.Tensor]:
@@ -214,11 +223,26 @@ class LogitsProcessor:
         if proc is None or not self.n_json_slots:
             return None
         idx = np.flatnonzero((proc[:, 0] == 1) & (proc[:, 1] >= self.n_mask_rows))
-        idx = idx[self._slot_tab[proc[idx, 1] - self.n_mask_rows] >= 0]
+        slots = proc[idx, 1] - self.n_mask_rows
+        idx = idx[(self._slot_tab[slots] >= 0) & (self._slot_tool[slots, 0] < 0)]  # (a tool row is not a schema row)
         if not idx.size:
             return None
         slots = proc[idx, 1] - self.n_mask_rows
         return np.stack([idx, slots, self._slot_tab[slots]], axis=1).astype(np.int32)
+
+    def tool_rows(self, proc: np.ndarray | None) -> np.ndarray | None:
+        """int32 [k, 5] (sampled row, state slot, table buffer, open id, close id) of the automaton tool rows of
+        ``proc``, or None."""
+        if proc is None or not self.n_json_slots:
+            return None
+        idx = np.flatnonzero((proc[:, 0] == 1) & (proc[:, 1] >= self.n_mask_rows))
+        slots = proc[idx, 1] - self.n_mask_rows
+        idx = idx[self._slot_tool[slots, 0] >= 0]
+        if not idx.size:
+            return None
+        slots = proc[idx, 1] - self.n_mask_rows
+        return np.concatenate([np.stack([idx, slots, self._slot_tab[slots]], axis=1), self._slot_tool[slots]],
+                              axis=1).astype(np.int32)
 
     def _json_reclaim(self) -> None:
         """The slots, and the table references, of sequences that have finished since."""
@@ -226,19 +250,21 @@ class LogitsProcessor:
             slot = self._jslots.pop(sid)[0]
             self._jfree.append(slot)
             self._slot_tab[slot] = -1
+            self._slot_tool[slot] = -1
             buf = self._sseq.pop(sid, None)
             if buf is not None:
                 self._stab_refs[buf] -= 1
 
-    def _schema_table(self, seq, new_tabs: list) -> int:
+    def _schema_table(self, seq, new_tabs: list, key=None, dfa=None) -> int:
         """The pool buffer of the sequence's schema; a schema the pool does not hold takes a free buffer or the least
-        recently used unreferenced one, and its table joins ``new_tabs``."""
+        recently used unreferenced one, and its table joins ``new_tabs``. A tool row's body shares the pool under
+        ``key`` (a tuple, so no schema text equals it) with the automaton ``dfa`` it is already compiled to."""
         from kafka_llm_service_amd.engine.json_schema import compile_text
 
         buf = self._sseq.get(seq.seq_id)
         if buf is not None:
             return buf
-        text = seq.params.json_schema
+        text = seq.params.json_schema if key is None else key
         buf = self._stabs.get(text)
         if buf is None:
             if not self._stab_free:
@@ -248,7 +274,7 @@ class LogitsProcessor:
                     raise RuntimeError("logits processor: every schema table buffer is referenced")
                 self._stab_free.append(self._stabs.pop(victim))
             buf = self._stab_free.pop()
-            dfa = compile_text(text)
+            dfa = compile_text(text) if dfa is None else dfa
             self._stabs[text] = buf
             new_tabs.append((buf, dfa.cls, dfa.trans))
             self.stats["schema_table_uploads"] += 1
@@ -268,6 +294,21 @@ class LogitsProcessor:
                 raise RuntimeError("json_schema: a state is seeded from landed tokens only")
             st = ref.schema_advance_ref(st, t, dfa, table)
         return js.state_record(st, buf)
+
+    def tool_seed(self, seq, buf: int) -> np.ndarray:
+        """The tool row's record after the sequence's output ids so far: the phase its ``tool_choice`` starts in,
+        replayed through ``ref.tool_advance_ref`` (as ``json_seed``: all ids have landed when a prefill is sampled)."""
+        from kafka_llm_service_amd.engine import tool_automaton as ta
+        from kafka_llm_service_amd.engine.json_schema import START
+        from kafka_llm_service_amd.ops import reference as ref
+
+        plan, table = seq.params.tool_plan, self.json_table()
+        rec = ta.tool_record(START, plan.phase0, buf)
+        for t in seq.output_ids:
+            if t < 0:
+                raise RuntimeError("tool grammar: a record is seeded from landed tokens only")
+            rec = ref.tool_advance_ref(rec, t, plan.open, plan.close, plan.dfa, table)
+        return rec
 
     def schema_pool(self):
         """The device pool of schema tables (ops.SchemaTables), allocated by the first schema step."""
@@ -391,6 +432,7 @@ class LogitsProcessor:
         b_rows, b_words, b_used = [], [], set()
         seen = []  # (slot, (r, inv_r), ascending distinct prompt ids) of the slots this step seeds
         j_slots, j_states, s_tabs = [], [], []
+        t_slots, t_states, t_tabs = [], [], []
         if self._rep_seqs:
             self._release_finished_rep(zero)
         V, W = self.V, self.W
@@ -448,6 +490,23 @@ class LogitsProcessor:
                     self.stats["schema_seeds"] += 1
                 proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
                 self.stats["schema_rows"] += 1
+            plan = getattr(p, "tool_plan", None)
+            if plan is not None and tool_row_live(plan, s.output_ids):
+                if spec is not None or getattr(p, "json_mode", False) or getattr(p, "json_schema", None) is not None:
+                    raise ValueError("the automaton tool grammar and another token mask on one row: the masks are "
+                                     "not intersected")
+                if not (0 <= plan.open < V and 0 <= plan.close < V):
+                    raise ValueError("tool grammar: the envelope's tokens lie outside the vocabulary")
+                slot, new_slot = self._json_slot(s)
+                buf = self._schema_table(s, t_tabs, plan.key, plan.dfa)
+                self._slot_tab[slot] = buf
+                self._slot_tool[slot] = (plan.open, plan.close)
+                if new_slot or (n_decode is not None and i >= n_decode):
+                    t_slots.append(slot)
+                    t_states.append(self.tool_seed(s, buf))
+                    self.stats["tool_seeds"] += 1
+                proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
+                self.stats["tool_rows"] += 1
             rep = p.repetition_penalty
             if p.presence_penalty or p.frequency_penalty or rep != 1.0:
                 proc[i, 2], new_slot = self._slot(s, zero)
@@ -499,6 +558,10 @@ class LogitsProcessor:
             upd.json_slots = np.asarray(j_slots, dtype=np.int32)
             upd.json_states = np.stack(j_states).astype(np.int32)
         upd.schema_tabs = s_tabs
+        upd.tool_tabs = t_tabs
+        if t_slots:
+            upd.tool_slots = np.asarray(t_slots, dtype=np.int32)
+            upd.tool_states = np.stack(t_states).astype(np.int32)
         return proc, upd
 
     # ---- device side ----------------------------------------------------------------------------------------------
@@ -509,6 +572,18 @@ class LogitsProcessor:
         mask_tab, counts = self.tables()
         for buf, cls, trans in upd.schema_tabs:  # (checked by the pool: the kernels trust a table's entries)
             self.schema_pool().load(int(buf), cls, trans, upload)
+        for buf, cls, trans in upd.tool_tabs:
+            self.schema_pool().load(int(buf), cls, trans, upload)
+        if upd.tool_slots.size:
+            st = np.asarray(upd.tool_states)
+            if st.shape != (upd.tool_slots.size, JSON_STATE_INTS) or int(upd.tool_slots.min()) < 0 \
+                    or int(upd.tool_slots.max()) >= self.n_json_slots \
+                    or ((st[:, 0] < 0) | ((st[:, 0] >= SCHEMA_MAX_STATES) & (st[:, 0] != SCHEMA_DEAD))).any() \
+                    or (st[:, 1] < 0).any() or (st[:, 1] >= TOOL_PHASES).any() or st[:, 2].any() \
+                    or (st[:, 3] < 1).any() or (st[:, 3] > self.n_json_slots).any():
+                raise ValueError("logits processor: tool record update does not fit the state table")
+            self.jstate.index_copy_(0, upload(upd.tool_slots.astype(np.int64)),
+                                    upload(np.ascontiguousarray(st, dtype=np.int32)))
         if upd.json_slots.size:
             st = upd.json_states
             sch = st[:, 3] != 0 if st.ndim == 2 and st.shape[1] == JSON_STATE_INTS else np.zeros(0, bool)

@@ -21,6 +21,7 @@ from kafka_llm_service_amd import ops
 from kafka_llm_service_amd.engine.logits_proc import LogitsProcessor, spec_forced
 from kafka_llm_service_amd.engine.scheduler import ScheduledBatch
 from kafka_llm_service_amd.engine.sequence import Sequence
+from kafka_llm_service_amd.engine.tool_automaton import tool_row_live
 from kafka_llm_service_amd.engine.step_plan import (  # noqa: F401 - the planner's names, importable from here as before
     DECODE_TARGET_ITEMS, MAX_ITEM_KEYS, MAX_PARTIALS, MAX_PREFIX_CHUNKS, MIN_DECODE_KEYS, PLAN_HDR, PLAN_PAYLOAD_IDX,
     _PLAN_SCALARS, HostStep, SampleParams, decode_items, decode_items_fixed, merge_ranges, pack_plan,
@@ -313,8 +314,10 @@ class ModelRunner:
             arrays.append(sp.proc)
             if sp.json_rows is not None:  # (JSON rows are proc rows: behind them)
                 arrays.append(sp.json_rows)
-            if sp.schema_rows is not None:  # (and the json_schema rows: last)
+            if sp.schema_rows is not None:  # (and the json_schema rows)
                 arrays.append(sp.schema_rows)
+            if sp.tool_rows is not None:  # (and the tool grammar's rows: last)
+                arrays.append(sp.tool_rows)
         dev = self.stager.upload_many(arrays)
         if len(dev) > 2:
             has_t = not sp.greedy and sp.temp.shape[0]
@@ -322,7 +325,9 @@ class ModelRunner:
             self._sp_dev = (sp, *(dev[2:5] if has_t else (None, None, None)),
                             dev[i_proc] if sp.proc is not None else None)
             self._json_dev = (sp, dev[i_proc + 1]) if sp.proc is not None and sp.json_rows is not None else None
-            self._schema_dev = (sp, dev[-1]) if sp.proc is not None and sp.schema_rows is not None else None
+            i_tool = len(dev) - 1 if sp.proc is not None and sp.tool_rows is not None else len(dev)
+            self._schema_dev = (sp, dev[i_tool - 1]) if sp.proc is not None and sp.schema_rows is not None else None
+            self._tool_dev = (sp, dev[i_tool]) if i_tool < len(dev) else None
         return self.views(dev[0], dev[1], h)
 
     def views(self, d64: torch.Tensor, d32: torch.Tensor, h: HostStep) -> StepInput:
@@ -413,7 +418,8 @@ class ModelRunner:
             # (min_p acts under temperature only: a greedy row needs no processing row for it)
             if allowed is not None or p.presence_penalty or p.frequency_penalty or p.logit_bias \
                     or (p.min_p and p.temperature > 0) or p.repetition_penalty != 1.0 or p.json_mode \
-                    or p.json_schema is not None:
+                    or p.json_schema is not None or (p.tool_plan is not None and tool_row_live(p.tool_plan,
+                                                                                              s.output_ids)):
                 rows.append((i, s, allowed))
         proc = upd = None
         if rows:
@@ -422,6 +428,7 @@ class ModelRunner:
         sp = SampleParams(temp, topp, topk, seeds, proc, not temp.any(), upd, known)
         sp.json_rows = self.lp.json_rows(proc)
         sp.schema_rows = self.lp.schema_rows(proc)
+        sp.tool_rows = self.lp.tool_rows(proc)
         if lp_rows:
             sp.lp_rows, sp.lp_k = np.asarray(lp_rows, dtype=np.int32), lp_k
         return sp
@@ -456,10 +463,11 @@ class ModelRunner:
         always did."""
         jpre, self._json_dev = getattr(self, "_json_dev", None), None
         spre, self._schema_dev = getattr(self, "_schema_dev", None), None
-        if sp.json_rows is None and sp.schema_rows is None:
+        tpre, self._tool_dev = getattr(self, "_tool_dev", None), None
+        if sp.json_rows is None and sp.schema_rows is None and sp.tool_rows is None:
             return self._sample_device(logits, sp)
         tabs, mask_tab = self.lp.json_tables(), self.lp.tables()[0]
-        jrows = srows = None
+        jrows = srows = trows = None
         if sp.json_rows is not None:
             jrows = jpre[1] if jpre is not None and jpre[0] is sp else self._h2d(sp.json_rows)
             ops.json_mask(tabs, jrows, self.lp.jstate, mask_tab, self.lp.n_mask_rows)
@@ -467,7 +475,13 @@ class ModelRunner:
             srows = spre[1] if spre is not None and spre[0] is sp else self._h2d(sp.schema_rows)
             ops.schema_mask(tabs, self.lp.schema_pool(), srows, logits.shape[0], self.lp.jstate, mask_tab,
                             self.lp.n_mask_rows, used=np.unique(sp.schema_rows[:, 2]))
+        if sp.tool_rows is not None:  # the automaton tool grammar (ops/csrc/tool_grammar.hip), where the schema kernels go
+            trows = tpre[1] if tpre is not None and tpre[0] is sp else self._h2d(sp.tool_rows)
+            ops.tool_mask(tabs, self.lp.schema_pool(), trows, logits.shape[0], self.lp.jstate, mask_tab,
+                          self.lp.n_mask_rows, used=np.unique(sp.tool_rows[:, 2]))
         toks = self._sample_device(logits, sp)
+        if trows is not None:
+            ops.tool_advance(tabs, self.lp.schema_pool(), trows, toks, self.lp.jstate)
         if jrows is not None:
             ops.json_advance(tabs, jrows, toks, self.lp.jstate)
         if srows is not None:

@@ -36,7 +36,12 @@ class SamplingParams:
     allowed_tokens_fn: Callable | None = None
     # picklable tool-call grammar {"tools": [...], "tool_choice": ...}: the engine builds the constraint
     # (engine/constrained.py) on its own side, so it also works through the DP / TP worker pipes
+    # An optional key ``"mode"``: "program" (the default: the generator-based constraint) or "automaton" — the call's
+    # body compiled from the tools' schemas and masked on the device (engine/tool_automaton.py); the engine's default
+    # comes from env KAFKA_TOOL_GRAMMAR
     tool_grammar: dict | None = None
+    # set by the engine for an automaton request: engine/tool_automaton.ToolPlan (the body, the envelope's tokens)
+    tool_plan: object | None = None
     # OpenAI ``logprobs`` / ``top_logprobs``: the log-probability of every generated token and of the 0..20 most
     # likely tokens at its position, over the model's RAW logits (before temperature, penalties and grammar masks;
     # ops/csrc/logprobs.hip). They ride back in ``StepOutput.logprobs``.
@@ -65,6 +70,13 @@ class SamplingParams:
     json_schema: str | None = None
 
     def __post_init__(self):
+        if self.tool_grammar is not None and self.tool_grammar.get("mode") is not None:
+            from kafka_llm_service_amd.engine.tool_automaton import grammar_mode
+
+            if grammar_mode(self.tool_grammar) == "automaton" and (
+                    self.json_mode or self.json_schema is not None or self.allowed_tokens_fn is not None):
+                raise ValueError("tool_grammar mode \"automaton\" cannot be combined with json_mode, json_schema or "
+                                 "an explicit allowed_tokens_fn")
         if self.json_schema is not None:
             if not isinstance(self.json_schema, str):
                 raise ValueError("json_schema must be the canonical text of a schema, or None")

@@ -192,11 +192,17 @@ class ProcUpdates:
     # uint8 [256], trans uint16 [S, C]) — a schema the pool does not hold yet (engine/json_schema.py). A schema row's
     # seeded record rides in json_slots / json_states above as (state, 0, 0, table index + 1)
     schema_tabs: list = field(default_factory=list)
+    # automaton tool grammar (engine/tool_automaton.py): the call bodies' tables this step loads into the same pool, as
+    # schema_tabs; [k] slots the host (re)seeds and [k, JSON_STATE_INTS] their records (state, phase, 0, table index + 1)
+    tool_tabs: list = field(default_factory=list)
+    tool_slots: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    tool_states: np.ndarray = field(default_factory=lambda: np.zeros((0, JSON_STATE_INTS), np.int32))
 
     @property
     def empty(self) -> bool:
         return not (self.mask_rows.size or self.zero_slots.size or self.dec.size or self.bias_rows.size
-                    or self.seen_slots.size or self.json_slots.size or self.schema_tabs)
+                    or self.seen_slots.size or self.json_slots.size or self.schema_tabs or self.tool_tabs
+                    or self.tool_slots.size)
 
     def check_seen(self) -> None:
         """The repetition-penalty sections agree with each other (a plan on the wire, a table update)."""
@@ -227,6 +233,10 @@ class SampleParams:
     # json_schema: int32 [k, 3] (sampled row, state-table slot, table index) of the step's schema rows, or None; the
     # mask and advance kernels of ops/csrc/json_schema.hip run over them around the sampler; part of the plan
     schema_rows: np.ndarray | None = None
+    # automaton tool grammar: int32 [k, TOOL_ROW_INTS] (sampled row, state-table slot, table index, open id, close id)
+    # of the step's tool rows, or None; the kernels of ops/csrc/tool_grammar.hip run over them around the sampler; part
+    # of the plan
+    tool_rows: np.ndarray | None = None
 
 
 _PLAN_SCALARS = ("B", "T", "nbt", "bt_w", "n_rows", "s_total", "n_dec_items", "n_prefix_items", "cascade_prefix",
@@ -234,11 +244,16 @@ _PLAN_SCALARS = ("B", "T", "nbt", "bt_w", "n_rows", "s_total", "n_dec_items", "n
 PLAN_HDR = 32  # int64 header of a broadcast step plan
 PLAN_PAYLOAD_IDX = 1 + len(_PLAN_SCALARS) + 4  # header word holding the payload size (pack_plan)
 PLAN_SCHEMA_IDX = PLAN_HDR - 1  # header word holding the int32 word count of the trailing json_schema section
+# the tool grammar section, behind it, has a header word of its own in the upper half of the same int64: words 0..30 are
+# taken and the header's size is part of the wire format, while a section's int32 word count fits 31 bits
+PLAN_TOOL_SHIFT = 32
+TOOL_ROW_INTS = 5  # kafka_abi.h
 
 
 def _schema_section(rows: np.ndarray, tabs: list) -> np.ndarray:
     """The plan's trailing json_schema section as int32 words; it describes its own parts: [k rows, t tables], the rows
-    [k, 3], then per table (index, S, C), cls as 64 words and trans as ceil(S * C / 2) words (zero-padded)."""
+    [k, 3], then per table (index, S, C), cls as 64 words and trans as ceil(S * C / 2) words (zero-padded). The tool
+    grammar section is the same with rows of TOOL_ROW_INTS words."""
     parts = [np.array([rows.shape[0], len(tabs)], np.int32), rows.astype(np.int32, copy=False).reshape(-1)]
     for idx, cls, trans in tabs:
         cls, trans = np.ascontiguousarray(cls), np.ascontiguousarray(trans)
@@ -251,10 +266,12 @@ def _schema_section(rows: np.ndarray, tabs: list) -> np.ndarray:
     return np.concatenate(parts)
 
 
-def _schema_unsection(words: np.ndarray) -> tuple[np.ndarray, list]:
+def _schema_unsection(words: np.ndarray, row_ints: int = 3) -> tuple[np.ndarray, list]:
     k, t = int(words[0]), int(words[1])
-    o = 2 + 3 * k
-    rows = words[2:o].reshape(k, 3)
+    o = 2 + row_ints * k
+    if k < 0 or t < 0 or o > words.size:
+        raise ValueError("plan: the json_schema section does not hold its rows")
+    rows = words[2:o].reshape(k, row_ints)
     tabs = []
     for _ in range(t):
         idx, S, C = (int(v) for v in words[o:o + 3])
@@ -321,9 +338,20 @@ def pack_plan(h: HostStep, sp: SampleParams) -> tuple[np.ndarray, np.ndarray]:
     if srows.size or upd.schema_tabs:  # the trailing section; a step without it packs to the bytes it always did
         parts.append(_schema_section(srows, upd.schema_tabs))
         n_schema = parts[-1].size
+    trows = sp.tool_rows if sp.tool_rows is not None else np.zeros((0, TOOL_ROW_INTS), np.int32)
+    if trows.ndim != 2 or trows.shape[1] != TOOL_ROW_INTS:
+        raise ValueError("plan: tool rows must be (sampled row, slot, table, open, close) records")
+    if upd.tool_states.shape != (upd.tool_slots.size, JSON_STATE_INTS):
+        raise ValueError("plan: tool state slots and records disagree")
+    n_tool = 0
+    if trows.size or upd.tool_tabs or upd.tool_slots.size:  # the last section: [n seeds], slots [n], records [n, 4],
+        # then rows and tables as the json_schema section; a step without it packs to the bytes it always did
+        parts += [np.array([upd.tool_slots.size], np.int32), upd.tool_slots.astype(np.int32, copy=False),
+                  upd.tool_states.astype(np.int32, copy=False).reshape(-1), _schema_section(trows, upd.tool_tabs)]
+        n_tool = sum(p.size for p in parts[-4:])
     payload = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in parts])
     hdr = np.zeros(PLAN_HDR, dtype=np.int64)
-    hdr[PLAN_SCHEMA_IDX] = n_schema
+    hdr[PLAN_SCHEMA_IDX] = n_schema | (n_tool << PLAN_TOOL_SHIFT)
     hdr[0] = 1
     k = len(_PLAN_SCALARS)
     hdr[1:1 + k] = [getattr(h, f) for f in _PLAN_SCALARS]
@@ -372,10 +400,20 @@ def unpack_plan(hdr: np.ndarray, payload: np.ndarray) -> tuple[HostStep, SampleP
         upd.json_states = take(np.int32, n_jseed * JSON_STATE_INTS).reshape(n_jseed, JSON_STATE_INTS)
         jrows = take(np.int32, 2 * n_jrows).reshape(n_jrows, 2)
         sp.json_rows = jrows if n_jrows else None
-    n_schema = int(hdr[PLAN_SCHEMA_IDX])
+    n_schema = int(hdr[PLAN_SCHEMA_IDX]) & ((1 << PLAN_TOOL_SHIFT) - 1)
+    n_tool = int(hdr[PLAN_SCHEMA_IDX]) >> PLAN_TOOL_SHIFT
     if n_schema:
         srows, upd.schema_tabs = _schema_unsection(take(np.int32, n_schema))
         sp.schema_rows = srows if srows.shape[0] else None
+    if n_tool:
+        words = take(np.int32, n_tool)
+        ns = int(words[0]) if words.size else -1
+        if ns < 0 or 1 + ns * (1 + JSON_STATE_INTS) > words.size:
+            raise ValueError("plan: the tool grammar section does not hold its seeds")
+        upd.tool_slots = words[1:1 + ns]
+        upd.tool_states = words[1 + ns:1 + ns * (1 + JSON_STATE_INTS)].reshape(ns, JSON_STATE_INTS)
+        trows, upd.tool_tabs = _schema_unsection(words[1 + ns * (1 + JSON_STATE_INTS):], TOOL_ROW_INTS)
+        sp.tool_rows = trows if trows.shape[0] else None
     sp.proc = proc if n_proc else None
     sp.upd = None if upd.empty else upd
     return h, sp

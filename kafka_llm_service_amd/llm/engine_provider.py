@@ -42,8 +42,12 @@ def _gpu_host() -> bool:
 
 class EngineLLMProvider(LLMProvider):
     def __init__(self, client, default_max_tokens: int = 1024, model_name: str = "llama3-8b", tool_provider=None,
-                 ignore_eos: bool = False, constrain_tools: bool = True, tool_choice: Any = "auto"):
+                 ignore_eos: bool = False, constrain_tools: bool = True, tool_choice: Any = "auto",
+                 tool_grammar_mode: str | None = None):
         super().__init__(tool_provider)
+        # "program" | "automaton" (engine/tool_automaton.py), sent as the tool grammar's "mode"; None: the engine's own
+        # default (EngineConfig.tool_grammar / env KAFKA_TOOL_GRAMMAR)
+        self.tool_grammar_mode = tool_grammar_mode
         # schema-constrained tool calls (engine/constrained.py): every call the model opens is well-formed JSON
         # matching the tool's schema; tool_choice "required" / a named function forces one (random-init weights)
         self.constrain_tools = constrain_tools
@@ -222,7 +226,9 @@ class EngineLLMProvider(LLMProvider):
                                 ignore_eos=self.ignore_eos, logprobs=bool(logprobs),
                                 top_logprobs=int(top_logprobs or 0) if logprobs else 0, logit_bias=bias,
                                 json_mode=json_mode, json_schema=json_schema,
-                                tool_grammar=({"tools": tools, "tool_choice": self._choice(tool_choice, messages)}
+                                tool_grammar=({"tools": tools, "tool_choice": self._choice(tool_choice, messages),
+                                               **({"mode": self.tool_grammar_mode} if self.tool_grammar_mode
+                                                  else {})}
                                               if tools and self.constrain_tools and not json_mode
                                               and json_schema is None else None))
         stops = [s for s in (stop or []) if s]

@@ -9,6 +9,7 @@ Kernel inventory:
   token_logprobs (logprob + top-k alternatives) csrc/logprobs.hip
   json_mask / json_advance (JSON-mode masks)    csrc/json_mask.hip
   schema_mask / schema_advance (json_schema)    csrc/json_schema.hip
+  tool_mask / tool_advance (tool automaton)     csrc/tool_grammar.hip
   moe_* / grouped GEMM                          csrc/moe.hip
   custom all-reduce                             csrc/allreduce.hip
 """
@@ -400,6 +401,55 @@ def schema_advance(tabs: JsonTables, pool: SchemaTables, rows, sampled, state) -
     for row, slot, t in r.tolist():
         state[slot, 0] = ref.schema_advance_ref(int(state[slot, 0]) & 0xFFFFFFFF, int(sampled[row]), pool.dfas[t],
                                                 tabs.table)
+
+
+def _tool_check(pool: SchemaTables, rows, state, n_sampled: int, V: int) -> list:
+    """The rows the kernels would not skip (CPU tensors only), as lists (sampled row, slot, table, open, close)."""
+    from kafka_llm_service_amd.engine import tool_automaton as ta
+
+    keep = []
+    for r, slot, t, op, cl in rows.reshape(-1, 5).tolist():
+        if not (0 <= r < n_sampled and 0 <= slot < state.shape[0] and 0 <= t < pool.n and 0 <= op < V and 0 <= cl < V):
+            continue
+        if pool.dfas[t] is None or int(state[slot, 3]) != t + 1 or not 0 <= int(state[slot, 1]) < ta.TOOL_PHASES:
+            continue
+        keep.append((r, slot, t, op, cl))
+    return keep
+
+
+def tool_mask(tabs: JsonTables, pool: SchemaTables, rows, n_sampled: int, state, mask_tab, json_row0: int,
+              tokens: int | None = None, dword: bool | None = None, used=None) -> None:
+    """For every (sampled row, slot, table, open, close) of ``rows`` (int32 [k, 5]): row ``json_row0 + slot`` of
+    ``mask_tab`` becomes the vocabulary mask of the slot's tool record ``state[slot]`` — ``ref.tool_mask_ref`` word for
+    word (engine/tool_automaton.py: the envelope of a tool call around the body's table ``table`` of ``pool``). ``used``
+    as for ``schema_mask``. A row the kernel's skip rules name is left alone. Launches nothing for k = 0."""
+    if rows.shape[0] == 0:
+        return
+    if _gpu(mask_tab):
+        kinds, lds = pool.kinds(used)
+        ext().tool_mask(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, rows, int(n_sampled), state,
+                        mask_tab, int(json_row0), kinds or 2, lds, int(tokens or SCHEMA_MASK_TOKENS),
+                        SCHEMA_MASK_DWORD if dword is None else bool(dword))
+        return
+    W = tabs.table.W
+    if json_row0 < 0 or json_row0 + state.shape[0] > mask_tab.shape[0] or mask_tab.shape[1] < W:
+        raise ValueError("tool_mask: the mask table does not hold the slots' rows")
+    for _, slot, t, op, cl in _tool_check(pool, rows, state, n_sampled, tabs.table.V):
+        words = ref.tool_mask_words(state[slot].numpy(), op, cl, pool.dfas[t], tabs.table)
+        mask_tab[json_row0 + slot, :W] = torch.from_numpy(words.view(np.int32).copy())
+
+
+def tool_advance(tabs: JsonTables, pool: SchemaTables, rows, sampled, state) -> None:
+    """Behind the sampler: the record ``state[slot]`` of every row moves over the id ``sampled[row]`` (int64) —
+    ``ref.tool_advance_ref``; word 3 stays. Launches nothing for k = 0."""
+    if rows.shape[0] == 0:
+        return
+    if _gpu(state):
+        ext().tool_advance(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, rows, sampled, state)
+        return
+    for r, slot, t, op, cl in _tool_check(pool, rows, state, sampled.shape[0], tabs.table.V):
+        rec = ref.tool_advance_ref(state[slot].numpy(), int(sampled[r]), op, cl, pool.dfas[t], tabs.table)
+        state[slot] = torch.from_numpy(rec)
 
 
 LOGPROBS_MAX_K = 20      # OpenAI's top_logprobs bound; the kernel's register / LDS budget (csrc/logprobs.hip)

@@ -506,6 +506,50 @@ static void schema_advance(at::Tensor strans, at::Tensor scls, at::Tensor sdim, 
                                         cur_stream()));
 }
 
+// The automaton tool grammar (tool_grammar.hip): the schema launches' checks with rows of TOOL_ROW_INTS words.
+static int tool_check_tables(const at::Tensor& strans, const at::Tensor& scls, const at::Tensor& sdim,
+                             const at::Tensor& tok_off, const at::Tensor& tok_bytes, const at::Tensor& trows,
+                             const at::Tensor& jstate) {
+  TORCH_CHECK(trows.is_cuda() && trows.scalar_type() == at::kInt && trows.is_contiguous() && trows.dim() == 2 &&
+                  trows.size(1) == kafka::TOOL_ROW_INTS,
+              "tool grammar: rows must be int32 [k, 5] (sampled row, slot, table, open, close) on the GPU");
+  // (the rows are checked above; the pool, the token bytes and the state table as for a schema launch)
+  return schema_check_tables(strans, scls, sdim, tok_off, tok_bytes, trows.new_empty({0, 3}), jstate);
+}
+
+static void tool_mask(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off, at::Tensor tok_bytes,
+                      at::Tensor trows, int64_t n_sampled, at::Tensor jstate, at::Tensor mask_tab, int64_t json_row0,
+                      int64_t kinds, int64_t lds_bytes, int64_t tokens, bool dword) {
+  const int V = tool_check_tables(strans, scls, sdim, tok_off, tok_bytes, trows, jstate);
+  TORCH_CHECK(mask_tab.is_cuda() && mask_tab.scalar_type() == at::kInt && mask_tab.is_contiguous() &&
+                  mask_tab.dim() == 2 && mask_tab.size(1) * 32 >= V && json_row0 >= 0 &&
+                  json_row0 + jstate.size(0) <= mask_tab.size(0),
+              "tool_mask: mask_tab must be int32 [>= json_row0 + slots, >= V / 32] on the GPU");
+  TORCH_CHECK(n_sampled >= 0 && n_sampled <= INT32_MAX && kinds >= 1 && kinds <= 3 && tokens >= 256 &&
+                  tokens <= (1 << 20) && tokens % 256 == 0 && lds_bytes >= 0 &&
+                  lds_bytes <= kafka::SCHEMA_LDS_BYTES && lds_bytes % 16 == 0,
+              "tool_mask: kinds must be in 1..3, lds_bytes a multiple of 16 up to SCHEMA_LDS_BYTES and tokens a "
+              "multiple of 256");
+  CHECK_HIP(kafka_launch_tool_mask(
+      strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(), (int)strans.size(0),
+      tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V, trows.data_ptr<int>(), (int)trows.size(0),
+      (int)n_sampled, jstate.data_ptr<int>(), (int)jstate.size(0),
+      reinterpret_cast<uint32_t*>(mask_tab.data_ptr<int>()), mask_tab.size(1), mask_tab.size(0), (int)json_row0,
+      (int)kinds, (int)lds_bytes, (int)tokens, dword ? 1 : 0, cur_stream()));
+}
+
+static void tool_advance(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off,
+                         at::Tensor tok_bytes, at::Tensor trows, at::Tensor sampled, at::Tensor jstate) {
+  const int V = tool_check_tables(strans, scls, sdim, tok_off, tok_bytes, trows, jstate);
+  TORCH_CHECK(sampled.is_cuda() && sampled.scalar_type() == at::kLong && sampled.is_contiguous() && sampled.dim() == 1,
+              "tool_advance: the sampled ids must be int64 [n] on the GPU");
+  CHECK_HIP(kafka_launch_tool_advance(strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(),
+                                      (int)strans.size(0), tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V,
+                                      trows.data_ptr<int>(), (int)trows.size(0), sampled.data_ptr<int64_t>(),
+                                      (int)sampled.numel(), jstate.data_ptr<int>(), (int)jstate.size(0),
+                                      cur_stream()));
+}
+
 // Per-token logprobs (logprobs.hip). rows: int32 [R] or none (rows 0..R-1); tok_lp f32 [R], top_lp f32 [R, K] and
 // top_id int32 [R, K] share one row stride (views of one packed record buffer). The row ids are trusted (the Python
 // op range-checks a host list before uploading it); everything the kernel indexes by them is sized for every row.
@@ -1142,6 +1186,12 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("lds_bytes") = (int64_t)kafka::SCHEMA_LDS_BYTES, py::arg("tokens") = 1024,
         py::arg("dword") = true);
   m.def("schema_advance", &schema_advance, py::arg("strans"), py::arg("scls"), py::arg("sdim"), py::arg("tok_off"),
+        py::arg("tok_bytes"), py::arg("rows"), py::arg("sampled"), py::arg("state"));
+  m.def("tool_mask", &tool_mask, py::arg("strans"), py::arg("scls"), py::arg("sdim"), py::arg("tok_off"),
+        py::arg("tok_bytes"), py::arg("rows"), py::arg("n_sampled"), py::arg("state"), py::arg("mask_tab"),
+        py::arg("json_row0"), py::arg("kinds") = 3, py::arg("lds_bytes") = (int64_t)kafka::SCHEMA_LDS_BYTES,
+        py::arg("tokens") = 1024, py::arg("dword") = true);
+  m.def("tool_advance", &tool_advance, py::arg("strans"), py::arg("scls"), py::arg("sdim"), py::arg("tok_off"),
         py::arg("tok_bytes"), py::arg("rows"), py::arg("sampled"), py::arg("state"));
   m.def("token_logprobs", &token_logprobs, py::arg("logits"), py::arg("tokens"), py::arg("rows"), py::arg("k"),
         py::arg("tok_lp"), py::arg("top_lp"), py::arg("top_id"), py::arg("ws") = py::none(), py::arg("nsplit") = 1);

@@ -28,41 +28,11 @@
 // slot whose record names another table (word 3 != table + 1), is skipped: a bad index never becomes an out-of-range
 // access or a walk of one table's state over another table.
 #include "common.h"
+#include "schema_walk.h"
 
 namespace kafka {
 
 constexpr int SM_NT = 256;
-
-struct SchemaTab {
-  int S, C;  // S == 0: not usable
-};
-
-__device__ __forceinline__ SchemaTab schema_dim(const int* __restrict__ sdim, int tab) {
-  const int S = sdim[2 * tab], C = sdim[2 * tab + 1];
-  SchemaTab t;
-  const bool ok = S >= 2 && S <= SCHEMA_MAX_STATES && C >= 1 && C <= 256 && S * C * 2 <= SCHEMA_TAB_BYTES;
-  t.S = ok ? S : 0;
-  t.C = C;
-  return t;
-}
-
-// the state after the bytes [lo, hi) of the token table; `tr` and `cl` in LDS or in global memory
-template <bool DWORD, typename PT, typename PC>
-__device__ __forceinline__ uint32_t schema_token(uint32_t s, PT tr, PC cl, uint32_t S, uint32_t C,
-                                                 const uint8_t* __restrict__ tok_bytes, int lo, int hi) {
-  if (DWORD) {
-    const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(tok_bytes);
-    uint32_t w = lo < hi ? words[lo >> 2] : 0u;
-    for (int j = lo; j < hi && s < S; ++j) {
-      if ((j & 3) == 0 && j != lo) w = words[j >> 2];
-      const uint32_t b = (w >> ((j & 3) * 8)) & 0xFFu;
-      s = tr[s * C + cl[b]];
-    }
-  } else {
-    for (int j = lo; j < hi && s < S; ++j) s = tr[s * C + cl[tok_bytes[j]]];
-  }
-  return s;
-}
 
 template <bool LDS, bool DWORD>
 __global__ void __launch_bounds__(SM_NT) schema_mask_kernel(const uint16_t* __restrict__ strans,

@@ -79,6 +79,12 @@ constexpr int SCHEMA_TAB_BYTES = 256 * 1024;   // one table of the device pool: 
 constexpr int SCHEMA_LDS_BYTES = 20 * 1024 - 256;
 constexpr int SCHEMA_DEAD = 0xFFFF, SCHEMA_DONE = 1;  // (START is 0)
 
+// ---- automaton tool grammar (tool_grammar.hip; engine/tool_automaton.py compiles a call's body to a schema table) ----
+// A tool row's record in the same state table is (state, phase, 0, table index + 1); a row of the launch is int32
+// [TOOL_ROW_INTS] = (sampled row, slot, table, open id, close id).
+constexpr int TOOL_ROW_INTS = 5;
+constexpr int TOOL_FREE = 0, TOOL_OPEN = 1, TOOL_BODY = 2, TOOL_TEXT = 3, TOOL_CLOSED = 4, TOOL_PHASES = 5;
+
 // ---- weight tile formats of the streaming GEMMs (wstream_gemm.hip WFMT; ops.WEIGHT_FORMATS) ----------------------
 // bf16 tiles [N/32][K/16][64 lanes][8]; fp8: e4m3 bytes [N/32][K/32][64][16] + fp32 row scales [N]; MXFP4: e2m1 bytes
 // [N/32][K/64][64][16] + e8m0 block exponents [N/32][K/64][32][2]
@@ -216,6 +222,20 @@ hipError_t kafka_launch_schema_advance(const uint16_t* strans, const uint8_t* sc
                                        const int* tok_off, const uint8_t* tok_bytes, int V, const int* srows,
                                        int n_rows, const int64_t* sampled, int n_sampled, int* jstate, int n_slots,
                                        hipStream_t st);
+
+// ---- tool_grammar.hip
+// The masks and the advance of the step's tool rows over the schema pool's tables, as the two launches above with the
+// envelope of a tool call around the walk: trows int32 [n_rows, TOOL_ROW_INTS]. kinds (1..3), lds_bytes, tokens and
+// dword as for kafka_launch_schema_mask; a row that needs no walk is written by the first instantiation launched.
+hipError_t kafka_launch_tool_mask(const uint16_t* strans, const uint8_t* scls, const int* sdim, int n_tabs,
+                                  const int* tok_off, const uint8_t* tok_bytes, int V, const int* trows, int n_rows,
+                                  int n_sampled, const int* jstate, int n_slots, uint32_t* mask_tab, int64_t mask_ld,
+                                  int64_t mask_rows, int json_row0, int kinds, int lds_bytes, int tokens, int dword,
+                                  hipStream_t st);
+hipError_t kafka_launch_tool_advance(const uint16_t* strans, const uint8_t* scls, const int* sdim, int n_tabs,
+                                     const int* tok_off, const uint8_t* tok_bytes, int V, const int* trows,
+                                     int n_rows, const int64_t* sampled, int n_sampled, int* jstate, int n_slots,
+                                     hipStream_t st);
 
 // ---- logprobs.hip
 // Log softmax of the RAW logits (no temperature / penalties / mask) at each scored row's sampled token, and the row's

@@ -1100,3 +1100,62 @@ def schema_mask_ref(state: int, dfa, table) -> np.ndarray:
             s[live] = trans[s[live], cls[table.tok_bytes[off[live] + j]]]
         keep[:V] = (table.lens > 0) & (s != js.DEAD)
     return np.packbits(keep, bitorder="little").view("<u4")
+
+
+# ---- automaton tool grammar: the envelope around a call body's automaton (engine/tool_automaton.py) ------------------
+# A record is (state, phase, 0, table + 1); ``open`` and ``close`` are the special tokens (no bytes) that begin and end
+# a call. csrc/tool_grammar.hip is held to these two functions bit for bit.
+def tool_mask_ref(record, open: int, close: int, dfa, table) -> np.ndarray:
+    """bool [V]: the ids a tool row may draw. FREE and TEXT: every id; OPEN: ``open``; BODY before DONE: the ids with
+    bytes whose walk from the state stays alive (``schema_walk``; a state at or above S that is not DONE allows none);
+    BODY in DONE, and CLOSED: ``close``."""
+    from kafka_llm_service_amd.engine import json_schema as js
+    from kafka_llm_service_amd.engine import tool_automaton as ta
+
+    s, phase = int(record[0]) & 0xFFFFFFFF, int(record[1])
+    V = table.V
+    if not 0 <= phase < ta.TOOL_PHASES or not (0 <= open < V and 0 <= close < V):
+        raise ValueError("tool_mask_ref: a phase outside 0..4, or an envelope token outside the vocabulary")
+    keep = np.zeros(V, dtype=bool)
+    if phase in (ta.TOOL_FREE, ta.TOOL_TEXT):
+        keep[:] = True
+    elif phase == ta.TOOL_OPEN:
+        keep[open] = True
+    elif phase == ta.TOOL_CLOSED or s == js.DONE:
+        keep[close] = True
+    elif s < dfa.S:
+        # schema_walk over every id with bytes, in schema_mask_ref's vectorised form (s != DONE: no EOS branch there)
+        bits = np.unpackbits(schema_mask_ref(s, dfa, table).view(np.uint8), bitorder="little")
+        keep[:] = bits[:V].astype(bool)
+    return keep
+
+
+def tool_mask_words(record, open: int, close: int, dfa, table) -> np.ndarray:
+    """``tool_mask_ref`` as the mask row's uint32 [ceil(V / 32)] words (bit j of word w is id 32 w + j)."""
+    keep = np.zeros(table.W * 32, dtype=bool)
+    keep[:table.V] = tool_mask_ref(record, open, close, dfa, table)
+    return np.packbits(keep, bitorder="little").view("<u4")
+
+
+def tool_advance_ref(record, token: int, open: int, close: int, dfa, table) -> np.ndarray:
+    """The record after the drawn ``token`` (int32 [4]; word 3 as it was). FREE: ``open`` -> (START, BODY), else TEXT;
+    OPEN: ``open`` -> (START, BODY), else DEAD; BODY before DONE: the schema walk (DEAD for an id without bytes or
+    outside the vocabulary); BODY in DONE: ``close`` -> CLOSED, else DEAD; TEXT and CLOSED stay."""
+    from kafka_llm_service_amd.engine import json_schema as js
+    from kafka_llm_service_amd.engine import tool_automaton as ta
+
+    s, phase, token = int(record[0]) & 0xFFFFFFFF, int(record[1]), int(token)
+    if not 0 <= phase < ta.TOOL_PHASES:
+        raise ValueError("tool_advance_ref: a phase outside 0..4")
+    if phase == ta.TOOL_FREE:
+        s, phase = (js.START, ta.TOOL_BODY) if token == open else (s, ta.TOOL_TEXT)
+    elif phase == ta.TOOL_OPEN:
+        s, phase = (js.START, ta.TOOL_BODY) if token == open else (js.DEAD, phase)
+    elif phase == ta.TOOL_BODY:
+        if s == js.DONE:
+            s, phase = (s, ta.TOOL_CLOSED) if token == close else (js.DEAD, phase)
+        elif s >= dfa.S or not 0 <= token < table.V or table.lens[token] == 0:
+            s = js.DEAD
+        else:
+            s = schema_walk(s, table.bytes_of(token), dfa)
+    return np.array([s, phase, int(record[2]), int(record[3])], dtype=np.int64).astype(np.int32)

@@ -12,7 +12,8 @@ FLAGS = {"backend": "KAFKA_LLM_BACKEND", "model": "KAFKA_MODEL", "weights": "KAF
          "tp": "KAFKA_TP", "max_model_len": "KAFKA_MAX_MODEL_LEN", "db": "KAFKA_DB", "db_path": "LOCAL_DB_PATH",
          "sandbox": "KAFKA_SANDBOX", "sandbox_url": "LOCAL_SANDBOX_URL", "tool_choice": "KAFKA_TOOL_CHOICE",
          "prompt_sections": "KAFKA_PROMPT_SECTIONS", "served_model_name": "DEFAULT_MODEL",
-         "kv_dtype": "KAFKA_KV_DTYPE", "weight_dtype": "KAFKA_WEIGHT_DTYPE"}
+         "kv_dtype": "KAFKA_KV_DTYPE", "weight_dtype": "KAFKA_WEIGHT_DTYPE",
+         "tool_grammar": "KAFKA_TOOL_GRAMMAR"}
 
 
 def main() -> None:

@@ -85,13 +85,15 @@ class ServerConfig:
 
 def _engine_kwargs(e) -> dict[str, Any]:
     """Engine options from the environment: KAFKA_KV_DTYPE (bf16 | fp8 KV cache), KAFKA_WEIGHT_DTYPE (bf16 | fp8 | mxfp4
-    dense projections and lm_head), KAFKA_GRAPHS=1 (hipGraph decode
+    dense projections and lm_head), KAFKA_TOOL_GRAMMAR (program | automaton tool-call grammar), KAFKA_GRAPHS=1 (hipGraph decode
     steps), KAFKA_MAX_NUM_SEQS, KAFKA_MAX_BATCHED_TOKENS."""
     kw: dict[str, Any] = {}
     if e.get("KAFKA_KV_DTYPE"):
         kw["kv_dtype"] = e["KAFKA_KV_DTYPE"]
     if e.get("KAFKA_WEIGHT_DTYPE"):
         kw["weight_dtype"] = e["KAFKA_WEIGHT_DTYPE"]
+    if e.get("KAFKA_TOOL_GRAMMAR"):  # program | automaton: the default mode of the tool-call grammar
+        kw["tool_grammar"] = e["KAFKA_TOOL_GRAMMAR"]
     if e.get("KAFKA_GRAPHS") in ("0", "1"):  # unset: the engine's default (on for TP > 1)
         kw["use_graphs"] = e["KAFKA_GRAPHS"] == "1"
     if e.get("KAFKA_MAX_NUM_SEQS"):
@@ -206,7 +208,8 @@ class ServerState:
         self.engine_client = await make_engine_client(cfg)
         return EngineLLMProvider(self.engine_client, default_max_tokens=cfg.default_max_tokens,
                                  model_name=self.model_ids()[0], tool_choice=cfg.tool_choice,
-                                 ignore_eos=cfg.ignore_eos)
+                                 ignore_eos=cfg.ignore_eos,
+                                 tool_grammar_mode=cfg.engine_kwargs.get("tool_grammar"))
 
     async def stop(self) -> None:
         self.ready = False
