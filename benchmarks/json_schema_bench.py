@@ -1,5 +1,5 @@
 """Structured-output kernel time at V = 128,256 (the Llama-3 token table) for 1, 16 and 64 rows: schema mask + advance
-(ops/csrc/json_schema.hip) for four schemas — tiny, about ten properties, one padded to just under SCHEMA_LDS_BYTES (all
+(ops/csrc/table_grammar.hip) for four schemas — tiny, about ten properties, one padded to just under SCHEMA_LDS_BYTES (all
 three staged in LDS; the last sets the launch's LDS allocation to its maximum), large (table walked in global memory) —
 and two states (inside a free string, after a value), beside the JSON-mode kernels
 (ops/csrc/json_mask.hip) over the same token table, row counts and kind of state as the yardstick. Device events

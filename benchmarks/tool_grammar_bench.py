@@ -1,5 +1,5 @@
 """Tool grammar kernel time at V = 128,256 (the Llama-3 token table) for 1, 16 and 64 rows: tool mask + advance
-(ops/csrc/tool_grammar.hip) per phase of the envelope, beside schema mask + advance (ops/csrc/json_schema.hip) over the
+(ops/csrc/table_grammar.hip) per phase of the envelope, beside schema mask + advance (the same kernels) over the
 same table, state and row count in the same process as the yardstick. Two call bodies: the shell tools (table staged in
 LDS) and a tool with a 600-member enum (table walked in global memory); the BODY rows stand inside a free string.
 Device events around 200 back-to-back launches; everything measured alternates round by round (5 rounds) and the

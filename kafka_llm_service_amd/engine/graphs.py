@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from kafka_llm_service_amd import ops
+from kafka_llm_service_amd.engine.step_plan import GRAMMARS
 
 log = logging.getLogger("kafka.graphs")
 
@@ -75,16 +76,10 @@ class DecodeGraphs:
             # runs eagerly. Under TP the graph ends at the logit shard and the sampler is eager anyway, so the
             # decision stays what every rank takes from the broadcast plan (followers never see lp_rows)
             return False
-        if sp.json_rows is not None:
-            # a step with JSON-mode rows runs eagerly: the mask and advance kernels (ops/csrc/json_mask.hip) take a
-            # row count that changes from step to step. The rows ride in the plan, so every TP rank decides alike
-            return False
-        if sp.tool_rows is not None:
-            # and a step with automaton tool rows (ops/csrc/tool_grammar.hip), for the same reasons
-            return False
-        if sp.schema_rows is not None:
-            # likewise a step with json_schema rows (ops/csrc/json_schema.hip): its row count changes, and so may the
-            # tables its launches read
+        if any(getattr(sp, k + "_rows") is not None for k in GRAMMARS):
+            # a step with JSON-mode, json_schema or automaton tool rows runs eagerly: the mask and advance kernels
+            # (ops/csrc/json_mask.hip, table_grammar.hip) take a row count that changes from step to step, and so may
+            # the tables the table launches read. The rows ride in the plan, so every TP rank decides alike
             return False
         return not self.disabled and h.B > 0 and h.T == h.B and h.n_items == 0
 

@@ -24,7 +24,7 @@ The result (``SchemaDfa``): ``cls`` uint8 [256] byte -> class, ``trans`` uint16 
 DONE (every NFA state lies on a path to the accepting one, so every subset does). States are numbered in order of
 discovery and classes by their first byte, so equal schema texts give equal bytes in every process: TP ranks rely on
 it. ``ops/reference.py`` (``schema_walk`` / ``schema_mask_ref`` / ``schema_advance_ref``) defines the walk;
-``ops/csrc/json_schema.hip`` agrees with it bit for bit.
+``ops/csrc/table_grammar.hip`` agrees with it bit for bit.
 
 Limits (each a ``SchemaError`` that states the limit): canonical text <= 64 KiB, nesting <= 32 after ``$ref``
 expansion (the root is level 1; every ``properties`` / ``items`` / ``anyOf`` descent adds one), at most

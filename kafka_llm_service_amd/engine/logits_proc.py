@@ -43,14 +43,14 @@ kernel moves ``jstate[slot]`` over the drawn token right behind it, so the state
 carry no guard and never roll back, and two steps can be in flight. The host seeds a slot's record only when the row
 is sampled from a prefill — admission, or the re-prefill after a preemption or an eviction — by walking the output ids
 so far (all landed by then) through ``ref.json_advance_ref``.
-Structured outputs (``SamplingParams.json_schema``; engine/json_schema.py, ops/csrc/json_schema.hip) share those slots
+Structured outputs (``SamplingParams.json_schema``; engine/json_schema.py, ops/csrc/table_grammar.hip) share those slots
 and mask rows: a schema row's record is ``(state, 0, 0, table index + 1)``, and its kernels walk the request's own
 transition table out of a device pool of ``json_slots`` buffers (``ops.SchemaTables``: 64 MiB at 256 slots, allocated
 by the first schema request — schema steps never run inside a graph, so no captured graph needs the address). Tables
 are keyed by the schema's canonical text and refcounted by live sequences; unreferenced ones stay resident in LRU
 order, so a thread that sends the same schema every turn uploads it once. With as many buffers as state slots a live
 sequence always finds one. A new table travels in ``ProcUpdates.schema_tabs`` and is loaded on every TP rank.
-The automaton tool grammar (``SamplingParams.tool_plan``; engine/tool_automaton.py, ops/csrc/tool_grammar.hip) takes a
+The automaton tool grammar (``SamplingParams.tool_plan``; engine/tool_automaton.py, the same kernels) takes a
 slot and a mask row from the same space and a buffer of the same pool, under a key no schema text equals; its record is
 ``(state, phase, 0, table index + 1)``, seeded as TOOL_FREE or TOOL_OPEN and replayed over the landed output ids after a
 preemption. Under ``tool_choice: "auto"`` the host drops the row from the tool rows once the first output id has landed
@@ -207,42 +207,32 @@ class LogitsProcessor:
             self._json_dev = ops.JsonTables(self.json_table(), self.device)
         return self._json_dev
 
-    def json_rows(self, proc: np.ndarray | None) -> np.ndarray | None:
-        """int32 [k, 2] (sampled row, state slot) of the JSON rows of ``proc`` (mode-1 rows naming a mask row behind
-        the LRU-managed ones), or None."""
+    def grammar_rows(self, proc: np.ndarray | None) -> tuple:
+        """The grammar rows of ``proc`` (mode-1 rows naming a mask row behind the LRU-managed ones), split by what
+        their slot holds: (JSON int32 [k, 2], schema [k, 3], tool [k, 5]), each the leading columns of (sampled row,
+        state slot, table buffer, open id, close id), or None where there is no such row."""
         if proc is None or not self.n_json_slots:
-            return None
+            return None, None, None
         idx = np.flatnonzero((proc[:, 0] == 1) & (proc[:, 1] >= self.n_mask_rows))
-        idx = idx[self._slot_tab[proc[idx, 1] - self.n_mask_rows] < 0]  # (a schema row is not a JSON-mode row)
-        if not idx.size:
-            return None
-        return np.stack([idx, proc[idx, 1] - self.n_mask_rows], axis=1).astype(np.int32)
+        slots = proc[idx, 1] - self.n_mask_rows
+        tab, tool = self._slot_tab[slots], self._slot_tool[slots]
+        full = np.concatenate([np.stack([idx, slots, tab], axis=1), tool], axis=1).astype(np.int32)
+        is_tool = tool[:, 0] >= 0  # (a tool row has a table too, and is not a schema row)
+        return tuple(np.ascontiguousarray(full[m, :w]) if m.any() else None
+                     for m, w in ((tab < 0, 2), ((tab >= 0) & ~is_tool, 3), (is_tool, 5)))
+
+    def json_rows(self, proc: np.ndarray | None) -> np.ndarray | None:
+        """int32 [k, 2] (sampled row, state slot) of the JSON-mode rows of ``proc``, or None."""
+        return self.grammar_rows(proc)[0]
 
     def schema_rows(self, proc: np.ndarray | None) -> np.ndarray | None:
         """int32 [k, 3] (sampled row, state slot, table buffer) of the json_schema rows of ``proc``, or None."""
-        if proc is None or not self.n_json_slots:
-            return None
-        idx = np.flatnonzero((proc[:, 0] == 1) & (proc[:, 1] >= self.n_mask_rows))
-        slots = proc[idx, 1] - self.n_mask_rows
-        idx = idx[(self._slot_tab[slots] >= 0) & (self._slot_tool[slots, 0] < 0)]  # (a tool row is not a schema row)
-        if not idx.size:
-            return None
-        slots = proc[idx, 1] - self.n_mask_rows
-        return np.stack([idx, slots, self._slot_tab[slots]], axis=1).astype(np.int32)
+        return self.grammar_rows(proc)[1]
 
     def tool_rows(self, proc: np.ndarray | None) -> np.ndarray | None:
         """int32 [k, 5] (sampled row, state slot, table buffer, open id, close id) of the automaton tool rows of
         ``proc``, or None."""
-        if proc is None or not self.n_json_slots:
-            return None
-        idx = np.flatnonzero((proc[:, 0] == 1) & (proc[:, 1] >= self.n_mask_rows))
-        slots = proc[idx, 1] - self.n_mask_rows
-        idx = idx[self._slot_tool[slots, 0] >= 0]
-        if not idx.size:
-            return None
-        slots = proc[idx, 1] - self.n_mask_rows
-        return np.concatenate([np.stack([idx, slots, self._slot_tab[slots]], axis=1), self._slot_tool[slots]],
-                              axis=1).astype(np.int32)
+        return self.grammar_rows(proc)[2]
 
     def _json_reclaim(self) -> None:
         """The slots, and the table references, of sequences that have finished since."""
@@ -283,32 +273,44 @@ class LogitsProcessor:
         self._sseq[seq.seq_id] = buf
         return buf
 
+    @staticmethod
+    def _replay(seq, start, step):
+        """``start`` moved by ``step(state, id)`` over the sequence's output ids so far — the only place the host
+        computes a grammar state (all ids have landed when a prefill is sampled)."""
+        st = start
+        for t in seq.output_ids:
+            if t < 0:
+                raise RuntimeError("grammar rows: a state is seeded from landed tokens only")
+            st = step(st, t)
+        return st
+
+    def json_seed(self, seq) -> np.ndarray:
+        """The JSON-mode row's state record after the sequence's output ids so far."""
+        from kafka_llm_service_amd.engine import json_mode as jm
+        from kafka_llm_service_amd.ops import reference as ref
+
+        table = self.json_table()
+        return jm.state_record(self._replay(seq, jm.START_STATE, lambda st, t: ref.json_advance_ref(st, t, table)))
+
     def schema_seed(self, seq, buf: int) -> np.ndarray:
-        """The schema row's record after the sequence's output ids so far (as ``json_seed``)."""
+        """The schema row's record after the sequence's output ids so far."""
         from kafka_llm_service_amd.engine import json_schema as js
         from kafka_llm_service_amd.ops import reference as ref
 
-        table, dfa, st = self.json_table(), js.compile_text(seq.params.json_schema), js.START
-        for t in seq.output_ids:
-            if t < 0:
-                raise RuntimeError("json_schema: a state is seeded from landed tokens only")
-            st = ref.schema_advance_ref(st, t, dfa, table)
-        return js.state_record(st, buf)
+        table, dfa = self.json_table(), js.compile_text(seq.params.json_schema)
+        return js.state_record(self._replay(seq, js.START, lambda st, t: ref.schema_advance_ref(st, t, dfa, table)),
+                               buf)
 
     def tool_seed(self, seq, buf: int) -> np.ndarray:
         """The tool row's record after the sequence's output ids so far: the phase its ``tool_choice`` starts in,
-        replayed through ``ref.tool_advance_ref`` (as ``json_seed``: all ids have landed when a prefill is sampled)."""
+        replayed through ``ref.tool_advance_ref``."""
         from kafka_llm_service_amd.engine import tool_automaton as ta
         from kafka_llm_service_amd.engine.json_schema import START
         from kafka_llm_service_amd.ops import reference as ref
 
         plan, table = seq.params.tool_plan, self.json_table()
-        rec = ta.tool_record(START, plan.phase0, buf)
-        for t in seq.output_ids:
-            if t < 0:
-                raise RuntimeError("tool grammar: a record is seeded from landed tokens only")
-            rec = ref.tool_advance_ref(rec, t, plan.open, plan.close, plan.dfa, table)
-        return rec
+        return self._replay(seq, ta.tool_record(START, plan.phase0, buf),
+                            lambda rec, t: ref.tool_advance_ref(rec, t, plan.open, plan.close, plan.dfa, table))
 
     def schema_pool(self):
         """The device pool of schema tables (ops.SchemaTables), allocated by the first schema step."""
@@ -330,17 +332,26 @@ class LogitsProcessor:
         self._jslots[seq.seq_id] = (slot, seq)
         return slot, True
 
-    def json_seed(self, seq) -> np.ndarray:
-        """The state record after the sequence's output ids so far — the only place the host computes a state."""
-        from kafka_llm_service_amd.engine import json_mode as jm
-        from kafka_llm_service_amd.ops import reference as ref
-
-        table, st = self.json_table(), jm.START_STATE
-        for t in seq.output_ids:
-            if t < 0:
-                raise RuntimeError("JSON mode: a state is seeded from landed tokens only")
-            st = ref.json_advance_ref(st, t, table)
-        return jm.state_record(st)
+    def _grammar_row(self, proc: np.ndarray, i: int, seq, kind: str, seed_row: bool, slots: list, states: list,
+                     pool: tuple | None = None, envelope: tuple | None = None) -> None:
+        """Row ``i`` of ``proc`` becomes the ``kind`` ("json", "schema", "tool") row of ``seq``: a mode-1 row naming
+        the mask row of the sequence's state slot. A table row takes its pool buffer through ``pool``, the arguments
+        of ``_schema_table`` behind the sequence; a tool row records its ``envelope`` (open id, close id). A slot
+        assigned here, or a row sampled from a prefill (``seed_row``), has its record seeded: it joins ``slots`` /
+        ``states``."""
+        slot, new_slot = self._json_slot(seq)
+        seed_args = (seq,)
+        if pool is not None:
+            buf = self._slot_tab[slot] = self._schema_table(seq, *pool)
+            seed_args = (seq, buf)
+        if envelope is not None:
+            self._slot_tool[slot] = envelope
+        if new_slot or seed_row:
+            slots.append(slot)
+            states.append(getattr(self, kind + "_seed")(*seed_args))
+            self.stats[kind + "_seeds"] += 1
+        proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
+        self.stats[kind + "_rows"] += 1
 
     # ---- host side ----------------------------------------------------------------------------------------------
     def _table_row(self, lru: OrderedDict, n_rows: int, key, words_fn, upd_rows: list, upd_words: list, used: set,
@@ -438,6 +449,7 @@ class LogitsProcessor:
         V, W = self.V, self.W
         for i, s, spec in rows:
             p = s.params
+            from_prefill = n_decode is not None and i >= n_decode  # (a grammar row's record is then seeded)
             if spec is not None:
                 forced = spec_forced(spec)
                 if forced is not None:
@@ -471,25 +483,11 @@ class LogitsProcessor:
             if getattr(p, "json_mode", False):
                 if spec is not None:
                     raise ValueError("JSON mode and a token constraint on one row: the masks are not intersected")
-                slot, new_slot = self._json_slot(s)
-                if new_slot or (n_decode is not None and i >= n_decode):
-                    j_slots.append(slot)
-                    j_states.append(self.json_seed(s))
-                    self.stats["json_seeds"] += 1
-                proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
-                self.stats["json_rows"] += 1
+                self._grammar_row(proc, i, s, "json", from_prefill, j_slots, j_states)
             if getattr(p, "json_schema", None) is not None:
                 if spec is not None or getattr(p, "json_mode", False):
                     raise ValueError("json_schema and another token mask on one row: the masks are not intersected")
-                slot, new_slot = self._json_slot(s)
-                buf = self._schema_table(s, s_tabs)
-                self._slot_tab[slot] = buf
-                if new_slot or (n_decode is not None and i >= n_decode):
-                    j_slots.append(slot)
-                    j_states.append(self.schema_seed(s, buf))
-                    self.stats["schema_seeds"] += 1
-                proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
-                self.stats["schema_rows"] += 1
+                self._grammar_row(proc, i, s, "schema", from_prefill, j_slots, j_states, (s_tabs,))
             plan = getattr(p, "tool_plan", None)
             if plan is not None and tool_row_live(plan, s.output_ids):
                 if spec is not None or getattr(p, "json_mode", False) or getattr(p, "json_schema", None) is not None:
@@ -497,16 +495,8 @@ class LogitsProcessor:
                                      "not intersected")
                 if not (0 <= plan.open < V and 0 <= plan.close < V):
                     raise ValueError("tool grammar: the envelope's tokens lie outside the vocabulary")
-                slot, new_slot = self._json_slot(s)
-                buf = self._schema_table(s, t_tabs, plan.key, plan.dfa)
-                self._slot_tab[slot] = buf
-                self._slot_tool[slot] = (plan.open, plan.close)
-                if new_slot or (n_decode is not None and i >= n_decode):
-                    t_slots.append(slot)
-                    t_states.append(self.tool_seed(s, buf))
-                    self.stats["tool_seeds"] += 1
-                proc[i, 0], proc[i, 1] = 1, self.n_mask_rows + slot
-                self.stats["tool_rows"] += 1
+                self._grammar_row(proc, i, s, "tool", from_prefill, t_slots, t_states, (t_tabs, plan.key, plan.dfa),
+                                  (plan.open, plan.close))
             rep = p.repetition_penalty
             if p.presence_penalty or p.frequency_penalty or rep != 1.0:
                 proc[i, 2], new_slot = self._slot(s, zero)
@@ -565,37 +555,35 @@ class LogitsProcessor:
         return proc, upd
 
     # ---- device side ----------------------------------------------------------------------------------------------
+    def _write_records(self, what: str, slots: np.ndarray, st, json_ok: bool, phases: int, upload) -> None:
+        """The records ``st`` [k, 4] into the slots ``slots`` of the state table, checked first. A record whose word 3
+        is 0 is a JSON-mode record (state, depth, stack bits, 0), taken only with ``json_ok``; every other one is a
+        table record (state, phase < ``phases``, 0, buffer + 1): a schema record with ``phases`` 1, a tool record with
+        TOOL_PHASES."""
+        if not slots.size:
+            return
+        st = np.asarray(st)
+        ok = st.shape == (slots.size, JSON_STATE_INTS) and int(slots.min()) >= 0 \
+            and int(slots.max()) < self.n_json_slots
+        if ok:
+            tabrec = st[:, 3] != 0 if json_ok else np.ones(len(st), dtype=bool)
+            jm_st, tb = st[~tabrec], st[tabrec]
+            ok = not ((jm_st[:, 0] < 0) | (jm_st[:, 0] > 63) | (jm_st[:, 1] < 0) | (jm_st[:, 1] > 32)).any() and not (
+                (tb[:, 0] < 0) | ((tb[:, 0] >= SCHEMA_MAX_STATES) & (tb[:, 0] != SCHEMA_DEAD)) | (tb[:, 1] < 0)
+                | (tb[:, 1] >= phases) | (tb[:, 2] != 0) | (tb[:, 3] < 1) | (tb[:, 3] > self.n_json_slots)).any()
+        if not ok:
+            raise ValueError(f"logits processor: {what} update does not fit the state table")
+        self.jstate.index_copy_(0, upload(slots.astype(np.int64)), upload(np.ascontiguousarray(st, dtype=np.int32)))
+
     def apply(self, upd: ProcUpdates | None, upload) -> None:
         """Stream-ordered table writes (``upload``: numpy -> device tensor, e.g. the runner's staging ring)."""
         if upd is None or upd.empty:
             return
         mask_tab, counts = self.tables()
-        for buf, cls, trans in upd.schema_tabs:  # (checked by the pool: the kernels trust a table's entries)
+        for buf, cls, trans in (*upd.schema_tabs, *upd.tool_tabs):  # (checked by the pool: the kernels trust a table)
             self.schema_pool().load(int(buf), cls, trans, upload)
-        for buf, cls, trans in upd.tool_tabs:
-            self.schema_pool().load(int(buf), cls, trans, upload)
-        if upd.tool_slots.size:
-            st = np.asarray(upd.tool_states)
-            if st.shape != (upd.tool_slots.size, JSON_STATE_INTS) or int(upd.tool_slots.min()) < 0 \
-                    or int(upd.tool_slots.max()) >= self.n_json_slots \
-                    or ((st[:, 0] < 0) | ((st[:, 0] >= SCHEMA_MAX_STATES) & (st[:, 0] != SCHEMA_DEAD))).any() \
-                    or (st[:, 1] < 0).any() or (st[:, 1] >= TOOL_PHASES).any() or st[:, 2].any() \
-                    or (st[:, 3] < 1).any() or (st[:, 3] > self.n_json_slots).any():
-                raise ValueError("logits processor: tool record update does not fit the state table")
-            self.jstate.index_copy_(0, upload(upd.tool_slots.astype(np.int64)),
-                                    upload(np.ascontiguousarray(st, dtype=np.int32)))
-        if upd.json_slots.size:
-            st = upd.json_states
-            sch = st[:, 3] != 0 if st.ndim == 2 and st.shape[1] == JSON_STATE_INTS else np.zeros(0, bool)
-            jm_st, sc_st = st[~sch] if sch.size else st, st[sch] if sch.size else st[:0]
-            if st.shape != (upd.json_slots.size, JSON_STATE_INTS) or int(upd.json_slots.min()) < 0 \
-                    or int(upd.json_slots.max()) >= self.n_json_slots or (jm_st[:, 0] < 0).any() \
-                    or (jm_st[:, 0] > 63).any() or (jm_st[:, 1] < 0).any() or (jm_st[:, 1] > 32).any() \
-                    or ((sc_st[:, 0] < 0) | ((sc_st[:, 0] >= SCHEMA_MAX_STATES) & (sc_st[:, 0] != SCHEMA_DEAD))).any() \
-                    or sc_st[:, 1:3].any() or (sc_st[:, 3] < 1).any() or (sc_st[:, 3] > self.n_json_slots).any():
-                raise ValueError("logits processor: JSON state update does not fit the state table")
-            self.jstate.index_copy_(0, upload(upd.json_slots.astype(np.int64)),
-                                    upload(np.ascontiguousarray(st, dtype=np.int32)))
+        self._write_records("tool record", upd.tool_slots, upd.tool_states, False, TOOL_PHASES, upload)
+        self._write_records("JSON state", upd.json_slots, upd.json_states, True, 1, upload)
         if upd.mask_rows.size:
             if int(upd.mask_rows.max()) >= self.n_mask_rows or upd.mask_words.shape[1] != mask_tab.shape[1]:
                 raise ValueError("logits processor: mask update does not fit the table")

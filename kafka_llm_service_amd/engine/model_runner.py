@@ -26,7 +26,7 @@ from kafka_llm_service_amd.engine.step_plan import (  # noqa: F401 - the planner
     DECODE_TARGET_ITEMS, MAX_ITEM_KEYS, MAX_PARTIALS, MAX_PREFIX_CHUNKS, MIN_DECODE_KEYS, PLAN_HDR, PLAN_PAYLOAD_IDX,
     _PLAN_SCALARS, HostStep, SampleParams, decode_items, decode_items_fixed, merge_ranges, pack_plan,
     plan_prefill_items, prefix_groups, retile, unpack_plan)
-from kafka_llm_service_amd.engine.step_plan import PlanConfig, cdiv, join, plan_attention, section
+from kafka_llm_service_amd.engine.step_plan import GRAMMARS, PlanConfig, cdiv, join, plan_attention, section
 from kafka_llm_service_amd.models.attention import AttnMeta
 from kafka_llm_service_amd.models.llama import StepInput, TransformerLM
 
@@ -307,27 +307,18 @@ class ModelRunner:
         """One H2D copy of the packed buffers (and of the step's sampling parameters when ``sp`` samples with
         temperature: left in ``self._sp_dev`` for ``sample_device``), then views into it (identical on every TP
         rank)."""
-        arrays = [h.i64, h.i32]
+        named = {}  # what rides behind the two packed buffers, in upload order
         if sp is not None and not sp.greedy and sp.temp.shape[0]:
-            arrays += [np.concatenate([sp.temp, sp.topp]), sp.topk, sp.seeds]
+            named.update(f32=np.concatenate([sp.temp, sp.topp]), topk=sp.topk, seeds=sp.seeds)
         if sp is not None and sp.proc is not None:
-            arrays.append(sp.proc)
-            if sp.json_rows is not None:  # (JSON rows are proc rows: behind them)
-                arrays.append(sp.json_rows)
-            if sp.schema_rows is not None:  # (and the json_schema rows)
-                arrays.append(sp.schema_rows)
-            if sp.tool_rows is not None:  # (and the tool grammar's rows: last)
-                arrays.append(sp.tool_rows)
-        dev = self.stager.upload_many(arrays)
-        if len(dev) > 2:
-            has_t = not sp.greedy and sp.temp.shape[0]
-            i_proc = 5 if has_t else 2
-            self._sp_dev = (sp, *(dev[2:5] if has_t else (None, None, None)),
-                            dev[i_proc] if sp.proc is not None else None)
-            self._json_dev = (sp, dev[i_proc + 1]) if sp.proc is not None and sp.json_rows is not None else None
-            i_tool = len(dev) - 1 if sp.proc is not None and sp.tool_rows is not None else len(dev)
-            self._schema_dev = (sp, dev[i_tool - 1]) if sp.proc is not None and sp.schema_rows is not None else None
-            self._tool_dev = (sp, dev[i_tool]) if i_tool < len(dev) else None
+            named["proc"] = sp.proc
+            # (grammar rows are proc rows: behind them, JSON mode, json_schema, then the tool grammar)
+            named.update((k, getattr(sp, k + "_rows")) for k in GRAMMARS if getattr(sp, k + "_rows") is not None)
+        dev = self.stager.upload_many([h.i64, h.i32, *named.values()])
+        if named:
+            at = dict(zip(named, dev[2:]))
+            self._sp_dev = (sp, at.get("f32"), at.get("topk"), at.get("seeds"), at.get("proc"))
+            self._grammar_dev = (sp, {k: at[k] for k in GRAMMARS if k in at})
         return self.views(dev[0], dev[1], h)
 
     def views(self, d64: torch.Tensor, d32: torch.Tensor, h: HostStep) -> StepInput:
@@ -426,9 +417,7 @@ class ModelRunner:
             proc, upd = self.lp.build(rows, n, n_decode)
             upd = None if upd.empty else upd
         sp = SampleParams(temp, topp, topk, seeds, proc, not temp.any(), upd, known)
-        sp.json_rows = self.lp.json_rows(proc)
-        sp.schema_rows = self.lp.schema_rows(proc)
-        sp.tool_rows = self.lp.tool_rows(proc)
+        sp.json_rows, sp.schema_rows, sp.tool_rows = self.lp.grammar_rows(proc)
         if lp_rows:
             sp.lp_rows, sp.lp_k = np.asarray(lp_rows, dtype=np.int32), lp_k
         return sp
@@ -458,25 +447,28 @@ class ModelRunner:
     def sample_device(self, logits: torch.Tensor, sp: "SampleParams") -> torch.Tensor:
         """The step's sampler launch. A step with JSON rows launches the mask kernel in front of it (the rows' mask
         rows from their device states) and the advance kernel behind it (the states over the drawn ids); a step
-        with json_schema rows does the same with the kernels of ops/csrc/json_schema.hip over the requests' own tables
-        (JSON-mode mask, schema mask, sampler, then the two advances); a step without either launches exactly what it
-        always did."""
-        jpre, self._json_dev = getattr(self, "_json_dev", None), None
-        spre, self._schema_dev = getattr(self, "_schema_dev", None), None
-        tpre, self._tool_dev = getattr(self, "_tool_dev", None), None
-        if sp.json_rows is None and sp.schema_rows is None and sp.tool_rows is None:
+        with json_schema or automaton tool rows does the same with the kernels of ops/csrc/table_grammar.hip over the
+        requests' own tables (JSON-mode mask, schema mask, tool mask, sampler, then the advances: tool, JSON mode,
+        schema); a step without any launches exactly what it always did."""
+        pre, self._grammar_dev = getattr(self, "_grammar_dev", None), None
+        if all(getattr(sp, k + "_rows") is None for k in GRAMMARS):
             return self._sample_device(logits, sp)
+        on_dev = pre[1] if pre is not None and pre[0] is sp else {}  # (uploaded with the step's plan)
+
+        def dev_rows(kind: str):
+            rows = getattr(sp, kind + "_rows")
+            return None if rows is None else on_dev[kind] if kind in on_dev else self._h2d(rows)
+
         tabs, mask_tab = self.lp.json_tables(), self.lp.tables()[0]
-        jrows = srows = trows = None
-        if sp.json_rows is not None:
-            jrows = jpre[1] if jpre is not None and jpre[0] is sp else self._h2d(sp.json_rows)
+        jrows = dev_rows("json")
+        if jrows is not None:
             ops.json_mask(tabs, jrows, self.lp.jstate, mask_tab, self.lp.n_mask_rows)
-        if sp.schema_rows is not None:
-            srows = spre[1] if spre is not None and spre[0] is sp else self._h2d(sp.schema_rows)
+        srows = dev_rows("schema")
+        if srows is not None:
             ops.schema_mask(tabs, self.lp.schema_pool(), srows, logits.shape[0], self.lp.jstate, mask_tab,
                             self.lp.n_mask_rows, used=np.unique(sp.schema_rows[:, 2]))
-        if sp.tool_rows is not None:  # the automaton tool grammar (ops/csrc/tool_grammar.hip), where the schema kernels go
-            trows = tpre[1] if tpre is not None and tpre[0] is sp else self._h2d(sp.tool_rows)
+        trows = dev_rows("tool")
+        if trows is not None:
             ops.tool_mask(tabs, self.lp.schema_pool(), trows, logits.shape[0], self.lp.jstate, mask_tab,
                           self.lp.n_mask_rows, used=np.unique(sp.tool_rows[:, 2]))
         toks = self._sample_device(logits, sp)

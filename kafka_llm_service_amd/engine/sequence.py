@@ -66,7 +66,7 @@ class SamplingParams:
     # OpenAI ``response_format: {"type": "json_schema", ...}``: the canonical text of a schema of the supported subset
     # (engine/json_schema.py), or None. Every sampled token keeps the output a prefix of one document that conforms to
     # it; after the document only an EOS id is allowed. The schema compiles to a transition table of its own that the
-    # device kernels walk (ops/csrc/json_schema.hip); excludes ``json_mode`` and the token constraints.
+    # device kernels walk (ops/csrc/table_grammar.hip); excludes ``json_mode`` and the token constraints.
     json_schema: str | None = None
 
     def __post_init__(self):

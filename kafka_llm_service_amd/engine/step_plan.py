@@ -231,12 +231,14 @@ class SampleParams:
     # over them before the sampler and the advance kernel behind it (ops/csrc/json_mask.hip); part of the plan
     json_rows: np.ndarray | None = None
     # json_schema: int32 [k, 3] (sampled row, state-table slot, table index) of the step's schema rows, or None; the
-    # mask and advance kernels of ops/csrc/json_schema.hip run over them around the sampler; part of the plan
+    # mask and advance kernels of ops/csrc/table_grammar.hip run over them around the sampler; part of the plan
     schema_rows: np.ndarray | None = None
     # automaton tool grammar: int32 [k, TOOL_ROW_INTS] (sampled row, state-table slot, table index, open id, close id)
-    # of the step's tool rows, or None; the kernels of ops/csrc/tool_grammar.hip run over them around the sampler; part
-    # of the plan
+    # of the step's tool rows, or None; the same kernels run over them in launches of their own; part of the plan
     tool_rows: np.ndarray | None = None
+
+
+GRAMMARS = ("json", "schema", "tool")  # the ``*_rows`` of SampleParams, in the order of their upload and mask launches
 
 
 _PLAN_SCALARS = ("B", "T", "nbt", "bt_w", "n_rows", "s_total", "n_dec_items", "n_prefix_items", "cascade_prefix",

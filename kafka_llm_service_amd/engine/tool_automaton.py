@@ -1,5 +1,5 @@
 """The opt-in automaton tool grammar (``tool_grammar["mode"] == "automaton"``): a tool call's body as one byte-level
-automaton over the tools' own schemas, walked on the device (ops/csrc/tool_grammar.hip), inside an envelope of two
+automaton over the tools' own schemas, walked on the device (ops/csrc/table_grammar.hip), inside an envelope of two
 special tokens that have no bytes.
 
 The generator-based constraint (engine/constrained.py) stays the default. It bounds a string to 12 tokens, a number to

@@ -8,8 +8,8 @@ Kernel inventory:
   sample (greedy / temperature / top-k / top-p) csrc/sampling.hip
   token_logprobs (logprob + top-k alternatives) csrc/logprobs.hip
   json_mask / json_advance (JSON-mode masks)    csrc/json_mask.hip
-  schema_mask / schema_advance (json_schema)    csrc/json_schema.hip
-  tool_mask / tool_advance (tool automaton)     csrc/tool_grammar.hip
+  schema_mask / schema_advance (json_schema)    csrc/table_grammar.hip
+  tool_mask / tool_advance (tool automaton)     csrc/table_grammar.hip
   moe_* / grouped GEMM                          csrc/moe.hip
   custom all-reduce                             csrc/allreduce.hip
 """
@@ -355,15 +355,67 @@ class SchemaTables:
         return k, lds
 
 
-def _schema_check(pool: SchemaTables, rows, state, n_sampled: int) -> np.ndarray:
-    """The values the kernels guard against (CPU tensors only, as ``_json_check``); returns the rows as numpy."""
-    r = rows.reshape(-1, 3).numpy()
-    if r.size and (r.min() < 0 or r[:, 0].max() >= n_sampled or r[:, 1].max() >= state.shape[0]
-                   or r[:, 2].max() >= pool.n or any(pool.dfas[t] is None for t in r[:, 2].tolist())
-                   or (state[r[:, 1].tolist(), 3].numpy() != r[:, 2] + 1).any()):
-        raise ValueError("schema: a row names a sampled row, a slot or a table outside its array, or a slot whose "
-                         "record belongs to another table")
-    return r
+def _table_rows(pool: SchemaTables, rows, width: int, state, n_sampled: int, V: int) -> list:
+    """The rows the kernels would not skip (CPU tensors only), as lists of ``width`` ints: 3 (sampled row, slot, table)
+    or 5 (... open, close). A bad schema row raises, as ``_json_check``; a bad tool row is left out, as on the GPU."""
+    from kafka_llm_service_amd.engine import tool_automaton as ta
+
+    keep = []
+    for row in rows.reshape(-1, width).tolist():
+        r, slot, t = row[:3]
+        ok = (0 <= r < n_sampled and 0 <= slot < state.shape[0] and 0 <= t < pool.n and pool.dfas[t] is not None
+              and int(state[slot, 3]) == t + 1)
+        if ok and width == 5:
+            ok = 0 <= row[3] < V and 0 <= row[4] < V and 0 <= int(state[slot, 1]) < ta.TOOL_PHASES
+        if ok:
+            keep.append(row)
+        elif width == 3:
+            raise ValueError("schema: a row names a sampled row, a slot or a table outside its array, or a slot whose "
+                             "record belongs to another table")
+    return keep
+
+
+def _table_mask(tabs: JsonTables, pool: SchemaTables, rows, width: int, n_sampled: int, state, mask_tab,
+                json_row0: int, tokens, dword, used) -> None:
+    """``schema_mask`` (width 3) and ``tool_mask`` (width 5): one kernel pair, one CPU loop over the references."""
+    if rows.shape[0] == 0:
+        return
+    if _gpu(mask_tab):
+        kinds, lds = pool.kinds(used)
+        head = (pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes)
+        tail = (lds, int(tokens or SCHEMA_MASK_TOKENS), SCHEMA_MASK_DWORD if dword is None else bool(dword))
+        if width == 3:
+            ext().schema_mask(*head, tabs.eos, rows, int(n_sampled), state, mask_tab, int(json_row0), kinds, *tail)
+        else:
+            ext().tool_mask(*head, rows, int(n_sampled), state, mask_tab, int(json_row0), kinds or 2, *tail)
+        return
+    keep = _table_rows(pool, rows, width, state, n_sampled, tabs.table.V)
+    W = tabs.table.W
+    if json_row0 < 0 or json_row0 + state.shape[0] > mask_tab.shape[0] or mask_tab.shape[1] < W:
+        raise ValueError("the mask table does not hold the slots' rows")
+    for _, slot, t, *env in keep:
+        if width == 3:
+            words = ref.schema_mask_ref(int(state[slot, 0]) & 0xFFFFFFFF, pool.dfas[t], tabs.table)
+        else:
+            words = ref.tool_mask_words(state[slot].numpy(), *env, pool.dfas[t], tabs.table)
+        mask_tab[json_row0 + slot, :W] = torch.from_numpy(words.view(np.int32).copy())
+
+
+def _table_advance(tabs: JsonTables, pool: SchemaTables, rows, width: int, sampled, state) -> None:
+    """``schema_advance`` (width 3) and ``tool_advance`` (width 5)."""
+    if rows.shape[0] == 0:
+        return
+    if _gpu(state):
+        launch = ext().schema_advance if width == 3 else ext().tool_advance
+        launch(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, rows, sampled, state)
+        return
+    for r, slot, t, *env in _table_rows(pool, rows, width, state, sampled.shape[0], tabs.table.V):
+        if width == 3:
+            state[slot, 0] = ref.schema_advance_ref(int(state[slot, 0]) & 0xFFFFFFFF, int(sampled[r]), pool.dfas[t],
+                                                    tabs.table)
+        else:
+            state[slot] = torch.from_numpy(ref.tool_advance_ref(state[slot].numpy(), int(sampled[r]), *env,
+                                                                pool.dfas[t], tabs.table))
 
 
 def schema_mask(tabs: JsonTables, pool: SchemaTables, rows, n_sampled: int, state, mask_tab, json_row0: int,
@@ -373,48 +425,13 @@ def schema_mask(tabs: JsonTables, pool: SchemaTables, rows, n_sampled: int, stat
     ``ref.schema_mask_ref`` word for word. ``tabs`` supplies the token bytes and the EOS ids. ``used``: the distinct
     table buffers the rows name, if the host knows them (the engine does): the launch's LDS is then sized by those
     tables, not by everything the pool still holds. Launches nothing for k = 0."""
-    if rows.shape[0] == 0:
-        return
-    if _gpu(mask_tab):
-        ext().schema_mask(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, tabs.eos, rows,
-                          int(n_sampled), state, mask_tab, int(json_row0), *pool.kinds(used),
-                          int(tokens or SCHEMA_MASK_TOKENS), SCHEMA_MASK_DWORD if dword is None else bool(dword))
-        return
-    r = _schema_check(pool, rows, state, n_sampled)
-    W = tabs.table.W
-    if json_row0 < 0 or json_row0 + state.shape[0] > mask_tab.shape[0] or mask_tab.shape[1] < W:
-        raise ValueError("schema_mask: the mask table does not hold the slots' rows")
-    for _, slot, t in r.tolist():
-        words = ref.schema_mask_ref(int(state[slot, 0]) & 0xFFFFFFFF, pool.dfas[t], tabs.table)
-        mask_tab[json_row0 + slot, :W] = torch.from_numpy(words.view(np.int32).copy())
+    _table_mask(tabs, pool, rows, 3, n_sampled, state, mask_tab, json_row0, tokens, dword, used)
 
 
 def schema_advance(tabs: JsonTables, pool: SchemaTables, rows, sampled, state) -> None:
     """Behind the sampler: ``state[slot, 0]`` of every row advances over the bytes of the id ``sampled[row]`` (int64)
     — ``ref.schema_advance_ref``; the record's other words stay. Launches nothing for k = 0."""
-    if rows.shape[0] == 0:
-        return
-    if _gpu(state):
-        ext().schema_advance(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, rows, sampled, state)
-        return
-    r = _schema_check(pool, rows, state, sampled.shape[0])
-    for row, slot, t in r.tolist():
-        state[slot, 0] = ref.schema_advance_ref(int(state[slot, 0]) & 0xFFFFFFFF, int(sampled[row]), pool.dfas[t],
-                                                tabs.table)
-
-
-def _tool_check(pool: SchemaTables, rows, state, n_sampled: int, V: int) -> list:
-    """The rows the kernels would not skip (CPU tensors only), as lists (sampled row, slot, table, open, close)."""
-    from kafka_llm_service_amd.engine import tool_automaton as ta
-
-    keep = []
-    for r, slot, t, op, cl in rows.reshape(-1, 5).tolist():
-        if not (0 <= r < n_sampled and 0 <= slot < state.shape[0] and 0 <= t < pool.n and 0 <= op < V and 0 <= cl < V):
-            continue
-        if pool.dfas[t] is None or int(state[slot, 3]) != t + 1 or not 0 <= int(state[slot, 1]) < ta.TOOL_PHASES:
-            continue
-        keep.append((r, slot, t, op, cl))
-    return keep
+    _table_advance(tabs, pool, rows, 3, sampled, state)
 
 
 def tool_mask(tabs: JsonTables, pool: SchemaTables, rows, n_sampled: int, state, mask_tab, json_row0: int,
@@ -423,33 +440,13 @@ def tool_mask(tabs: JsonTables, pool: SchemaTables, rows, n_sampled: int, state,
     ``mask_tab`` becomes the vocabulary mask of the slot's tool record ``state[slot]`` — ``ref.tool_mask_ref`` word for
     word (engine/tool_automaton.py: the envelope of a tool call around the body's table ``table`` of ``pool``). ``used``
     as for ``schema_mask``. A row the kernel's skip rules name is left alone. Launches nothing for k = 0."""
-    if rows.shape[0] == 0:
-        return
-    if _gpu(mask_tab):
-        kinds, lds = pool.kinds(used)
-        ext().tool_mask(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, rows, int(n_sampled), state,
-                        mask_tab, int(json_row0), kinds or 2, lds, int(tokens or SCHEMA_MASK_TOKENS),
-                        SCHEMA_MASK_DWORD if dword is None else bool(dword))
-        return
-    W = tabs.table.W
-    if json_row0 < 0 or json_row0 + state.shape[0] > mask_tab.shape[0] or mask_tab.shape[1] < W:
-        raise ValueError("tool_mask: the mask table does not hold the slots' rows")
-    for _, slot, t, op, cl in _tool_check(pool, rows, state, n_sampled, tabs.table.V):
-        words = ref.tool_mask_words(state[slot].numpy(), op, cl, pool.dfas[t], tabs.table)
-        mask_tab[json_row0 + slot, :W] = torch.from_numpy(words.view(np.int32).copy())
+    _table_mask(tabs, pool, rows, 5, n_sampled, state, mask_tab, json_row0, tokens, dword, used)
 
 
 def tool_advance(tabs: JsonTables, pool: SchemaTables, rows, sampled, state) -> None:
     """Behind the sampler: the record ``state[slot]`` of every row moves over the id ``sampled[row]`` (int64) —
     ``ref.tool_advance_ref``; word 3 stays. Launches nothing for k = 0."""
-    if rows.shape[0] == 0:
-        return
-    if _gpu(state):
-        ext().tool_advance(pool.strans, pool.scls, pool.sdim, tabs.tok_off, tabs.tok_bytes, rows, sampled, state)
-        return
-    for r, slot, t, op, cl in _tool_check(pool, rows, state, sampled.shape[0], tabs.table.V):
-        rec = ref.tool_advance_ref(state[slot].numpy(), int(sampled[r]), op, cl, pool.dfas[t], tabs.table)
-        state[slot] = torch.from_numpy(rec)
+    _table_advance(tabs, pool, rows, 5, sampled, state)
 
 
 LOGPROBS_MAX_K = 20      # OpenAI's top_logprobs bound; the kernel's register / LDS budget (csrc/logprobs.hip)

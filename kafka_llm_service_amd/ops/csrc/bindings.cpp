@@ -441,113 +441,106 @@ static void json_advance(at::Tensor trans, at::Tensor tok_off, at::Tensor tok_by
                                       (int)jstate.size(0), cur_stream()));
 }
 
-// Structured outputs (json_schema.hip): the shared checks of the table pool, the token bytes, the rows and the state
-// table, then the two launches.
-static int schema_check_tables(const at::Tensor& strans, const at::Tensor& scls, const at::Tensor& sdim,
-                               const at::Tensor& tok_off, const at::Tensor& tok_bytes, const at::Tensor& srows,
-                               const at::Tensor& jstate) {
+// The table-walk grammars (table_grammar.hip), structured outputs with rows of 3 words and the automaton tool grammar
+// with rows of TOOL_ROW_INTS: the shared checks of the table pool, the token bytes, the rows and the state table, of a
+// mask launch and of an advance launch, then the four launches.
+static int table_check(const at::Tensor& strans, const at::Tensor& scls, const at::Tensor& sdim,
+                       const at::Tensor& tok_off, const at::Tensor& tok_bytes, const at::Tensor& rows, int row_ints,
+                       const at::Tensor& jstate) {
   TORCH_CHECK(strans.is_cuda() && strans.scalar_type() == at::kUInt16 && strans.is_contiguous() && strans.dim() == 2 &&
                   strans.size(0) >= 1 && strans.size(1) == kafka::SCHEMA_TAB_BYTES / 2,
-              "schema: strans must be uint16 [n, SCHEMA_TAB_BYTES / 2] on the GPU");
+              "table grammar: strans must be uint16 [n, SCHEMA_TAB_BYTES / 2] on the GPU");
   TORCH_CHECK(scls.is_cuda() && scls.scalar_type() == at::kByte && scls.is_contiguous() && scls.dim() == 2 &&
                   scls.size(0) == strans.size(0) && scls.size(1) == 256,
-              "schema: scls must be uint8 [n, 256] on the GPU");
+              "table grammar: scls must be uint8 [n, 256] on the GPU");
   TORCH_CHECK(sdim.is_cuda() && sdim.scalar_type() == at::kInt && sdim.is_contiguous() && sdim.dim() == 2 &&
                   sdim.size(0) == strans.size(0) && sdim.size(1) == 2,
-              "schema: sdim must be int32 [n, 2] on the GPU");
+              "table grammar: sdim must be int32 [n, 2] on the GPU");
   TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.dim() == 1 &&
                   tok_off.numel() >= 2,
-              "schema: tok_off must be int32 [V + 1] on the GPU");
+              "table grammar: tok_off must be int32 [V + 1] on the GPU");
   TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
                   tok_bytes.numel() >= 4 && reinterpret_cast<uintptr_t>(tok_bytes.data_ptr()) % 4 == 0,
-              "schema: tok_bytes must be uint8 on the GPU, 4-byte aligned and padded by 4 bytes");
-  TORCH_CHECK(srows.is_cuda() && srows.scalar_type() == at::kInt && srows.is_contiguous() && srows.dim() == 2 &&
-                  srows.size(1) == 3,
-              "schema: rows must be int32 [k, 3] (sampled row, slot, table) on the GPU");
+              "table grammar: tok_bytes must be uint8 on the GPU, 4-byte aligned and padded by 4 bytes");
+  TORCH_CHECK(rows.is_cuda() && rows.scalar_type() == at::kInt && rows.is_contiguous() && rows.dim() == 2 &&
+                  rows.size(1) == row_ints,
+              "table grammar: rows must be int32 [k, ", row_ints, "] (sampled row, slot, table",
+              row_ints == 3 ? "" : ", open, close", ") on the GPU");
   TORCH_CHECK(jstate.is_cuda() && jstate.scalar_type() == at::kInt && jstate.is_contiguous() && jstate.dim() == 2 &&
                   jstate.size(1) == kafka::JSON_STATE_INTS,
-              "schema: the state table must be int32 [slots, 4] on the GPU");
+              "table grammar: the state table must be int32 [slots, 4] on the GPU");
   return (int)(tok_off.numel() - 1);
 }
+
+static int table_mask_check(const at::Tensor& strans, const at::Tensor& scls, const at::Tensor& sdim,
+                            const at::Tensor& tok_off, const at::Tensor& tok_bytes, const at::Tensor& rows,
+                            int row_ints, int64_t n_sampled, const at::Tensor& jstate, const at::Tensor& mask_tab,
+                            int64_t json_row0, int64_t kinds_min, int64_t kinds, int64_t lds_bytes, int64_t tokens) {
+  const int V = table_check(strans, scls, sdim, tok_off, tok_bytes, rows, row_ints, jstate);
+  TORCH_CHECK(mask_tab.is_cuda() && mask_tab.scalar_type() == at::kInt && mask_tab.is_contiguous() &&
+                  mask_tab.dim() == 2 && mask_tab.size(1) * 32 >= V && json_row0 >= 0 &&
+                  json_row0 + jstate.size(0) <= mask_tab.size(0),
+              "table grammar: mask_tab must be int32 [>= json_row0 + slots, >= V / 32] on the GPU");
+  TORCH_CHECK(n_sampled >= 0 && n_sampled <= INT32_MAX && kinds >= kinds_min && kinds <= 3 && tokens >= 256 &&
+                  tokens <= (1 << 20) && tokens % 256 == 0 && lds_bytes >= 0 &&
+                  lds_bytes <= kafka::SCHEMA_LDS_BYTES && lds_bytes % 16 == 0,
+              "table grammar: kinds must be in ", kinds_min, "..3, lds_bytes a multiple of 16 up to SCHEMA_LDS_BYTES "
+              "and tokens a multiple of 256");
+  return V;
+}
+
+static uint32_t* mask_words(at::Tensor& mask_tab) { return reinterpret_cast<uint32_t*>(mask_tab.data_ptr<int>()); }
 
 static void schema_mask(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off, at::Tensor tok_bytes,
                         at::Tensor eos, at::Tensor srows, int64_t n_sampled, at::Tensor jstate, at::Tensor mask_tab,
                         int64_t json_row0, int64_t kinds, int64_t lds_bytes, int64_t tokens, bool dword) {
-  const int V = schema_check_tables(strans, scls, sdim, tok_off, tok_bytes, srows, jstate);
+  const int V = table_mask_check(strans, scls, sdim, tok_off, tok_bytes, srows, 3, n_sampled, jstate, mask_tab,
+                                 json_row0, 0, kinds, lds_bytes, tokens);
   TORCH_CHECK(eos.is_cuda() && eos.scalar_type() == at::kInt && eos.is_contiguous() &&
                   eos.numel() <= kafka::JSON_MAX_EOS,
               "schema_mask: eos must be int32 [<= 8] on the GPU");
-  TORCH_CHECK(mask_tab.is_cuda() && mask_tab.scalar_type() == at::kInt && mask_tab.is_contiguous() &&
-                  mask_tab.dim() == 2 && mask_tab.size(1) * 32 >= V && json_row0 >= 0 &&
-                  json_row0 + jstate.size(0) <= mask_tab.size(0),
-              "schema_mask: mask_tab must be int32 [>= json_row0 + slots, >= V / 32] on the GPU");
-  TORCH_CHECK(n_sampled >= 0 && n_sampled <= INT32_MAX && kinds >= 0 && kinds <= 3 && tokens >= 256 &&
-                  tokens <= (1 << 20) && tokens % 256 == 0 && lds_bytes >= 0 &&
-                  lds_bytes <= kafka::SCHEMA_LDS_BYTES && lds_bytes % 16 == 0,
-              "schema_mask: kinds must be in 0..3, lds_bytes a multiple of 16 up to SCHEMA_LDS_BYTES and tokens a "
-              "multiple of 256");
   CHECK_HIP(kafka_launch_schema_mask(
       strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(), (int)strans.size(0),
       tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V, eos.data_ptr<int>(), (int)eos.numel(),
       srows.data_ptr<int>(), (int)srows.size(0), (int)n_sampled, jstate.data_ptr<int>(), (int)jstate.size(0),
-      reinterpret_cast<uint32_t*>(mask_tab.data_ptr<int>()), mask_tab.size(1), mask_tab.size(0), (int)json_row0,
-      (int)kinds, (int)lds_bytes, (int)tokens, dword ? 1 : 0, cur_stream()));
-}
-
-static void schema_advance(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off,
-                           at::Tensor tok_bytes, at::Tensor srows, at::Tensor sampled, at::Tensor jstate) {
-  const int V = schema_check_tables(strans, scls, sdim, tok_off, tok_bytes, srows, jstate);
-  TORCH_CHECK(sampled.is_cuda() && sampled.scalar_type() == at::kLong && sampled.is_contiguous() && sampled.dim() == 1,
-              "schema_advance: the sampled ids must be int64 [n] on the GPU");
-  CHECK_HIP(kafka_launch_schema_advance(strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(),
-                                        (int)strans.size(0), tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V,
-                                        srows.data_ptr<int>(), (int)srows.size(0), sampled.data_ptr<int64_t>(),
-                                        (int)sampled.numel(), jstate.data_ptr<int>(), (int)jstate.size(0),
-                                        cur_stream()));
-}
-
-// The automaton tool grammar (tool_grammar.hip): the schema launches' checks with rows of TOOL_ROW_INTS words.
-static int tool_check_tables(const at::Tensor& strans, const at::Tensor& scls, const at::Tensor& sdim,
-                             const at::Tensor& tok_off, const at::Tensor& tok_bytes, const at::Tensor& trows,
-                             const at::Tensor& jstate) {
-  TORCH_CHECK(trows.is_cuda() && trows.scalar_type() == at::kInt && trows.is_contiguous() && trows.dim() == 2 &&
-                  trows.size(1) == kafka::TOOL_ROW_INTS,
-              "tool grammar: rows must be int32 [k, 5] (sampled row, slot, table, open, close) on the GPU");
-  // (the rows are checked above; the pool, the token bytes and the state table as for a schema launch)
-  return schema_check_tables(strans, scls, sdim, tok_off, tok_bytes, trows.new_empty({0, 3}), jstate);
+      mask_words(mask_tab), mask_tab.size(1), mask_tab.size(0), (int)json_row0, (int)kinds, (int)lds_bytes,
+      (int)tokens, dword ? 1 : 0, cur_stream()));
 }
 
 static void tool_mask(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off, at::Tensor tok_bytes,
                       at::Tensor trows, int64_t n_sampled, at::Tensor jstate, at::Tensor mask_tab, int64_t json_row0,
                       int64_t kinds, int64_t lds_bytes, int64_t tokens, bool dword) {
-  const int V = tool_check_tables(strans, scls, sdim, tok_off, tok_bytes, trows, jstate);
-  TORCH_CHECK(mask_tab.is_cuda() && mask_tab.scalar_type() == at::kInt && mask_tab.is_contiguous() &&
-                  mask_tab.dim() == 2 && mask_tab.size(1) * 32 >= V && json_row0 >= 0 &&
-                  json_row0 + jstate.size(0) <= mask_tab.size(0),
-              "tool_mask: mask_tab must be int32 [>= json_row0 + slots, >= V / 32] on the GPU");
-  TORCH_CHECK(n_sampled >= 0 && n_sampled <= INT32_MAX && kinds >= 1 && kinds <= 3 && tokens >= 256 &&
-                  tokens <= (1 << 20) && tokens % 256 == 0 && lds_bytes >= 0 &&
-                  lds_bytes <= kafka::SCHEMA_LDS_BYTES && lds_bytes % 16 == 0,
-              "tool_mask: kinds must be in 1..3, lds_bytes a multiple of 16 up to SCHEMA_LDS_BYTES and tokens a "
-              "multiple of 256");
+  const int V = table_mask_check(strans, scls, sdim, tok_off, tok_bytes, trows, kafka::TOOL_ROW_INTS, n_sampled,
+                                 jstate, mask_tab, json_row0, 1, kinds, lds_bytes, tokens);
   CHECK_HIP(kafka_launch_tool_mask(
       strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(), (int)strans.size(0),
       tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V, trows.data_ptr<int>(), (int)trows.size(0),
-      (int)n_sampled, jstate.data_ptr<int>(), (int)jstate.size(0),
-      reinterpret_cast<uint32_t*>(mask_tab.data_ptr<int>()), mask_tab.size(1), mask_tab.size(0), (int)json_row0,
-      (int)kinds, (int)lds_bytes, (int)tokens, dword ? 1 : 0, cur_stream()));
+      (int)n_sampled, jstate.data_ptr<int>(), (int)jstate.size(0), mask_words(mask_tab), mask_tab.size(1),
+      mask_tab.size(0), (int)json_row0, (int)kinds, (int)lds_bytes, (int)tokens, dword ? 1 : 0, cur_stream()));
+}
+
+// (the two advance launchers share one signature)
+static void table_advance(decltype(&kafka_launch_schema_advance) launch, int row_ints, at::Tensor& strans,
+                          at::Tensor& scls, at::Tensor& sdim, at::Tensor& tok_off, at::Tensor& tok_bytes,
+                          at::Tensor& rows, at::Tensor& sampled, at::Tensor& jstate) {
+  const int V = table_check(strans, scls, sdim, tok_off, tok_bytes, rows, row_ints, jstate);
+  TORCH_CHECK(sampled.is_cuda() && sampled.scalar_type() == at::kLong && sampled.is_contiguous() && sampled.dim() == 1,
+              "table grammar: the sampled ids must be int64 [n] on the GPU");
+  CHECK_HIP(launch(strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(), (int)strans.size(0),
+                   tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V, rows.data_ptr<int>(), (int)rows.size(0),
+                   sampled.data_ptr<int64_t>(), (int)sampled.numel(), jstate.data_ptr<int>(), (int)jstate.size(0),
+                   cur_stream()));
+}
+
+static void schema_advance(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off,
+                           at::Tensor tok_bytes, at::Tensor srows, at::Tensor sampled, at::Tensor jstate) {
+  table_advance(&kafka_launch_schema_advance, 3, strans, scls, sdim, tok_off, tok_bytes, srows, sampled, jstate);
 }
 
 static void tool_advance(at::Tensor strans, at::Tensor scls, at::Tensor sdim, at::Tensor tok_off,
                          at::Tensor tok_bytes, at::Tensor trows, at::Tensor sampled, at::Tensor jstate) {
-  const int V = tool_check_tables(strans, scls, sdim, tok_off, tok_bytes, trows, jstate);
-  TORCH_CHECK(sampled.is_cuda() && sampled.scalar_type() == at::kLong && sampled.is_contiguous() && sampled.dim() == 1,
-              "tool_advance: the sampled ids must be int64 [n] on the GPU");
-  CHECK_HIP(kafka_launch_tool_advance(strans.data_ptr<uint16_t>(), scls.data_ptr<uint8_t>(), sdim.data_ptr<int>(),
-                                      (int)strans.size(0), tok_off.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), V,
-                                      trows.data_ptr<int>(), (int)trows.size(0), sampled.data_ptr<int64_t>(),
-                                      (int)sampled.numel(), jstate.data_ptr<int>(), (int)jstate.size(0),
-                                      cur_stream()));
+  table_advance(&kafka_launch_tool_advance, kafka::TOOL_ROW_INTS, strans, scls, sdim, tok_off, tok_bytes, trows,
+                sampled, jstate);
 }
 
 // Per-token logprobs (logprobs.hip). rows: int32 [R] or none (rows 0..R-1); tok_lp f32 [R], top_lp f32 [R, K] and

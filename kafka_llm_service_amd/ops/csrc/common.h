@@ -210,6 +210,20 @@ __device__ __forceinline__ bf16x8 dq4(uint32_t v, float sc) {
   return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// Grammar masks (json_mask.hip, table_grammar.hip): 64 mask bits of the tokens [t0, t0 + 64) (t0 a multiple of 64
+// below V) into the row of W words: one 8-byte store, two 4-byte stores where the row's words are not 8-byte aligned,
+// one where the row's last word is the low half
+__device__ __forceinline__ void mask_store64(uint32_t* __restrict__ row, int W, int t0, unsigned long long bal) {
+  const int w = t0 >> 5;  // even; w < W because t0 < V
+  uint32_t* p = row + w;
+  if (w + 1 < W && (reinterpret_cast<uintptr_t>(p) & 7) == 0) {
+    *reinterpret_cast<unsigned long long*>(p) = bal;
+  } else {
+    p[0] = (uint32_t)bal;
+    if (w + 1 < W) p[1] = (uint32_t)(bal >> 32);
+  }
+}
+
 // Counter-based RNG (splitmix64 finaliser): deterministic given (seed, stream, index).
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;

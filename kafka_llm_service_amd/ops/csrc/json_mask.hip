@@ -8,8 +8,7 @@
 //
 // json_mask_kernel   grid (ceil(V / JM_TOKENS), JSON rows), 256 threads. The workgroup stages TRANS in LDS (16 KB);
 //   every lane walks one token's bytes from a private copy of the row's state; one wave ballot is 64 mask bits,
-//   stored by lane 0 as one 8-byte store into the slot's row of `mask_tab` (two 4-byte stores where the row's words
-//   are not 8-byte aligned, one where the last word of the row is the ballot's low half). A token past V reads
+//   stored by lane 0 into the slot's row of `mask_tab` (common.h: mask_store64). A token past V reads
 //   nothing and contributes a zero bit, so the surplus bits of the last word are clear. In DONE the allowed tokens
 //   are the EOS ids; a token without bytes is never allowed.
 // json_advance_kernel   one thread per JSON row, launched behind the sampler: reads the row's sampled id, walks its
@@ -125,16 +124,7 @@ __global__ void __launch_bounds__(JM_NT) json_mask_kernel(const uint8_t* __restr
       }
     }
     const unsigned long long bal = __ballot(ok);
-    if (lane == 0) {
-      const int w = t0 >> 5;  // even; w < W because t0 < V
-      uint32_t* p = row + w;
-      if (w + 1 < W && (reinterpret_cast<uintptr_t>(p) & 7) == 0) {
-        *reinterpret_cast<unsigned long long*>(p) = bal;
-      } else {
-        p[0] = (uint32_t)bal;
-        if (w + 1 < W) p[1] = (uint32_t)(bal >> 32);
-      }
-    }
+    if (lane == 0) mask_store64(row, W, t0, bal);
   }
 }
 

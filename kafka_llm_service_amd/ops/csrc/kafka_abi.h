@@ -69,7 +69,7 @@ constexpr int JSON_MAX_DEPTH = 32;  // open containers; the stack is one bit per
 constexpr int JSON_MAX_EOS = 8;     // EOS ids the mask kernel compares a token with in DONE
 constexpr int JSON_EXPECT_KEY = 2, JSON_EXPECT_VALUE = 4, JSON_DONE = 7;
 
-// ---- structured outputs (json_schema.hip; engine/json_schema.py compiles a schema to cls uint8 [256] + trans uint16
+// ---- structured outputs (table_grammar.hip; engine/json_schema.py compiles a schema to cls uint8 [256] + trans uint16
 // [S, C]) ---------------------------------------------------------------------------------------------------------------
 // A schema row's record in the same state table is (state, 0, 0, table index + 1): word 3 is 0 for a JSON-mode row.
 constexpr int SCHEMA_MAX_STATES = 8192;        // states of one compiled automaton
@@ -79,7 +79,7 @@ constexpr int SCHEMA_TAB_BYTES = 256 * 1024;   // one table of the device pool: 
 constexpr int SCHEMA_LDS_BYTES = 20 * 1024 - 256;
 constexpr int SCHEMA_DEAD = 0xFFFF, SCHEMA_DONE = 1;  // (START is 0)
 
-// ---- automaton tool grammar (tool_grammar.hip; engine/tool_automaton.py compiles a call's body to a schema table) ----
+// ---- automaton tool grammar (table_grammar.hip; engine/tool_automaton.py compiles a call's body to a schema table) ---
 // A tool row's record in the same state table is (state, phase, 0, table index + 1); a row of the launch is int32
 // [TOOL_ROW_INTS] = (sampled row, slot, table, open id, close id).
 constexpr int TOOL_ROW_INTS = 5;
@@ -205,13 +205,13 @@ hipError_t kafka_launch_json_advance(const uint8_t* trans, const int* tok_off, c
                                      const int* jrows, int n_rows, const int64_t* sampled, int n_sampled, int* jstate,
                                      int n_slots, hipStream_t st);
 
-// ---- json_schema.hip
+// ---- table_grammar.hip: schema rows
 // The masks and the advance of the step's schema rows, as the two JSON-mode launches above but over per-request
 // tables: strans uint16 [n_tabs, SCHEMA_TAB_BYTES / 2], scls uint8 [n_tabs, 256], sdim int32 [n_tabs, 2] = (S, C);
 // srows int32 [n_rows, 3]: (sampled row, slot, table). tok_bytes needs 4 readable bytes behind the last token and a
 // 4-byte aligned address. kinds: bit 0 launches the instantiation with the table in LDS (S * C * 2 <= lds_bytes <=
 // SCHEMA_LDS_BYTES, a multiple of 16: what the launch allocates), bit 1 the one that walks it in global memory; each
-// skips the other's rows. tokens: tokens of one
+// skips the other's rows, and a launch of one of them leaves the other's rows untouched. tokens: tokens of one
 // workgroup (a multiple of 256); dword: read token bytes through aligned 4-byte loads.
 hipError_t kafka_launch_schema_mask(const uint16_t* strans, const uint8_t* scls, const int* sdim, int n_tabs,
                                     const int* tok_off, const uint8_t* tok_bytes, int V, const int* eos, int n_eos,
@@ -223,9 +223,9 @@ hipError_t kafka_launch_schema_advance(const uint16_t* strans, const uint8_t* sc
                                        int n_rows, const int64_t* sampled, int n_sampled, int* jstate, int n_slots,
                                        hipStream_t st);
 
-// ---- tool_grammar.hip
-// The masks and the advance of the step's tool rows over the schema pool's tables, as the two launches above with the
-// envelope of a tool call around the walk: trows int32 [n_rows, TOOL_ROW_INTS]. kinds (1..3), lds_bytes, tokens and
+// ---- table_grammar.hip: tool rows
+// The masks and the advance of the step's tool rows over the schema pool's tables: the same two kernels as above with
+// the envelope of a tool call around the walk: trows int32 [n_rows, TOOL_ROW_INTS]. kinds (1..3), lds_bytes, tokens and
 // dword as for kafka_launch_schema_mask; a row that needs no walk is written by the first instantiation launched.
 hipError_t kafka_launch_tool_mask(const uint16_t* strans, const uint8_t* scls, const int* sdim, int n_tabs,
                                   const int* tok_off, const uint8_t* tok_bytes, int V, const int* trows, int n_rows,

@@ -1,4 +1,4 @@
-"""The automaton tool grammar on the GPU: the mask and advance kernels (ops/csrc/tool_grammar.hip) against the CPU
+"""The automaton tool grammar on the GPU: the mask and advance kernels (ops/csrc/table_grammar.hip) against the CPU
 definition word for word and record for record — all five phases, an LDS-sized and a global-sized table in one launch,
 mask rows 8-byte aligned and not — the sampler over device-written rows in a mixed batch, and the engine eager and
 under hipGraphs against the CPU reference on the engine's own logits. Integers throughout: every comparison is an
@@ -255,6 +255,109 @@ def test_advance_kernel_record_for_record(cuda, two_tables):
         assert got[i] == w, (i, r, t)
         n_dead += w[0] == js.DEAD
     assert n_dead == 11 and got[5][:2] == [js.DONE, ta.TOOL_CLOSED] and got[2][:2] == [js.START, ta.TOOL_BODY]
+
+
+def _body_states(tables):
+    """(buffer, dfa, state) over what the schema corpus visits: the states of a document from START to DONE, DEAD, and
+    states at and past S."""
+    out = []
+    for b, d, doc in tables:
+        states = sorted({ref.schema_walk(js.START, doc[:i], d) for i in range(len(doc) + 1)})
+        assert js.START in states and js.DONE in states and js.DEAD not in states
+        out += [(b, d, s) for s in states + [js.DEAD, d.S, js.SCHEMA_MAX_STATES - 1]]
+    return out
+
+
+def _one_eos_table(V):
+    """``synthetic_table(V)`` with the last id as its only EOS: the `close` of the tool rows below."""
+    t = synthetic_table(V)
+    return jm.JsonTable.from_byte_strings([t.bytes_of(i) for i in range(V)], [V - 1])
+
+
+@pytest.mark.parametrize("V", [1, 63, 64, 65, 1057])
+def test_a_schema_row_is_a_body_row_without_an_envelope(cuda, V, two_tables):
+    """What one kernel pair for both row widths rests on: the state ``s`` as the schema record (s, 0, 0, tab + 1) and
+    as the tool record (s, TOOL_BODY, 0, tab + 1) gives the same mask word for word — ``schema_mask_ref``'s, and in
+    DONE, where `close` is the table's one EOS id, ``tool_mask_words``' too — and, advanced over the same id, the same
+    word 0. Tables in LDS and in global memory, rows 8-byte aligned and not; rows of no slot keep the sentinel."""
+    table = _one_eos_table(V)
+    tabs, pool = ops.JsonTables(table, cuda), _pool(cuda, two_tables)
+    assert pool.kinds()[0] == 3 and table.eos_ids.tolist() == [V - 1]
+    op, cl = min(3, V - 1), V - 1
+    corpus = _body_states(two_tables)
+    k, row0, spare = len(corpus), 3, 2
+    assert k > 60 and {js.START, js.DONE, js.DEAD} <= {s for _, _, s in corpus}
+    # the schema record of corpus[i] in slot perm[2 i], its tool twin in slot perm[2 i + 1]
+    perm = np.random.default_rng(V).permutation(2 * k + spare)
+    state = np.zeros((2 * k + spare, 4), np.int32)
+    srows, trows = np.zeros((k, 3), np.int32), np.zeros((k, 5), np.int32)
+    for i, (b, _, s) in enumerate(corpus):
+        state[perm[2 * i]], state[perm[2 * i + 1]] = js.state_record(s, b), ta.tool_record(s, ta.TOOL_BODY, b)
+        srows[i], trows[i] = [i, perm[2 * i], b], [k - 1 - i, perm[2 * i + 1], b, op, cl]
+    want = [ref.schema_mask_ref(s, d, table) for _, d, s in corpus]
+    for shift in (0, 1):
+        flat, mask_tab = _mask_tab(cuda, row0 + 2 * k + spare + 1, table.W, shift)
+        st = torch.from_numpy(state.copy()).to(cuda)
+        ops.schema_mask(tabs, pool, torch.from_numpy(srows).to(cuda), k, st, mask_tab, row0)
+        ops.tool_mask(tabs, pool, torch.from_numpy(trows).to(cuda), k, st, mask_tab, row0)
+        mt, fl = mask_tab.cpu().numpy(), flat.cpu().numpy()
+        for i, (b, d, s) in enumerate(corpus):
+            g_s, g_t = mt[row0 + perm[2 * i]].view(np.uint32), mt[row0 + perm[2 * i + 1]].view(np.uint32)
+            assert np.array_equal(g_s, g_t), (V, shift, b, s)
+            assert np.array_equal(g_s, want[i]), (V, shift, b, s)
+            if s == js.DONE:
+                assert np.array_equal(g_t, ref.tool_mask_words(state[perm[2 * i + 1]], op, cl, d, table))
+                assert np.flatnonzero(np.unpackbits(g_t.view(np.uint8), bitorder="little")).tolist() == [cl]
+        written = {int(row0 + sl) for sl in perm[:2 * k]}
+        for r in range(mt.shape[0]):
+            if r not in written:
+                assert (mt[r] == SENTINEL).all(), f"V {V}: row {r} is no slot's row and was written"
+        assert (fl[:shift] == SENTINEL).all() and (fl[shift + mt.size:] == SENTINEL).all()
+        assert st.cpu().numpy().tolist() == state.tolist()  # (a mask launch writes no record)
+
+
+def test_a_schema_row_advances_as_a_body_row(cuda, two_tables):
+    """The advance half of the test above: both records over the same sampled id — a valid continuation, a dead byte,
+    an id without bytes, an id past V; in DONE the `close` id, where the schema row stays DONE and the tool row
+    closes — leave the same word 0, ``schema_advance_ref``'s, and every other word as its own reference says."""
+    V = 1057
+    table = _one_eos_table(V)
+    tabs, pool = ops.JsonTables(table, cuda), _pool(cuda, two_tables)
+    op, cl, empty = 5, V - 1, 3
+    assert table.lens[empty] == 0 and table.lens[op] > 0
+    single = [t for t in range(V - 1) if table.lens[t] == 1]
+    cases, kinds = [], set()  # (buffer, dfa, state, sampled id)
+    for b, d, s in _body_states(two_tables):
+        if s == js.DONE:
+            cases.append((b, d, s, cl))
+            continue
+        nxt = {t: ref.schema_advance_ref(s, t, d, table) for t in single}
+        live = next((t for t, n in nxt.items() if n != js.DEAD), None)
+        dead = next(t for t, n in nxt.items() if n == js.DEAD)
+        kinds.add(live is not None)
+        cases += [(b, d, s, t) for t in (live, dead, empty, V + 5) if t is not None]
+    assert kinds == {True, False}  # (DEAD and the states past S have no continuation)
+    k, spare = len(cases), 3
+    perm = np.random.default_rng(k).permutation(2 * k + spare)
+    st0 = np.zeros((2 * k + spare, 4), np.int32)
+    st0[perm[2 * k:]] = [7, 8, 9, 0]  # (other slots: anything, and it must stay)
+    srows, trows = np.zeros((k, 3), np.int32), np.zeros((k, 5), np.int32)
+    for i, (b, _, s, _) in enumerate(cases):
+        st0[perm[2 * i]], st0[perm[2 * i + 1]] = js.state_record(s, b), ta.tool_record(s, ta.TOOL_BODY, b)
+        srows[i], trows[i] = [i, perm[2 * i], b], [i, perm[2 * i + 1], b, op, cl]
+    state = torch.from_numpy(st0.copy()).to(cuda)
+    sampled = torch.tensor([t for _, _, _, t in cases], device=cuda)
+    ops.tool_advance(tabs, pool, torch.from_numpy(trows).to(cuda), sampled, state)
+    ops.schema_advance(tabs, pool, torch.from_numpy(srows).to(cuda), sampled, state)
+    got = state.cpu().numpy()
+    for i, (b, d, s, t) in enumerate(cases):
+        g_s, g_t = got[perm[2 * i]].tolist(), got[perm[2 * i + 1]].tolist()
+        assert g_s[0] == g_t[0] == ref.schema_advance_ref(s, t, d, table), (i, b, s, t)
+        assert g_s[1:] == [0, 0, b + 1], (i, b, s, t)
+        assert g_t == ref.tool_advance_ref(st0[perm[2 * i + 1]], t, op, cl, d, table).tolist(), (i, b, s, t)
+        if s == js.DONE:
+            assert g_s[0] == js.DONE and g_t[1] == ta.TOOL_CLOSED
+    assert (got[perm[2 * k:]] == [7, 8, 9, 0]).all()
 
 
 def test_sampler_reads_device_written_rows_in_a_mixed_batch(cuda):
