@@ -611,23 +611,16 @@ __device__ __forceinline__ void merge_one_piece(DecodeSmem<D>& sm, const DecodeA
 }
 
 // Ending B, a piece of a split row (S > 1, e.g. one long sequence spread over many workgroups), after its
-// write_partial<TICKET>: every piece has published its partial with agent-coherent write-through stores (another
-// XCD's workgroup may read it; a __threadfence release here would write back the whole L2 from every workgroup),
-// waits for them, takes a ticket, and the LAST of the S workgroups of (b, kvh) merges all npre + S partials
-// (agent-coherent loads) and writes the bf16 rows — no merge kernel launch. The last one also re-arms the counter
-// for the next launch.
+// write_partial<TICKET>: the ticket protocol of common.h. Every piece has published its partial with agent-coherent
+// write-through stores, waits for them and takes a ticket; the LAST of the S workgroups of (b, kvh) merges all
+// npre + S partials (agent-coherent loads) and writes the bf16 rows — no merge kernel launch.
 template <int D, bool OST>
 __device__ __forceinline__ void ticket_merge(DecodeSmem<D>& sm, const DecodeArgs& a, int b, int kvh, int64_t row0,
                                              int S, int npre) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();  // every wave's own partial stores, ahead of the barrier (the ticket protocol: common.h)
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int* tk = a.tickets + b * a.Hkv + kvh;
-    const int t = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sm.s_last = t == S - 1;
-    if (t == S - 1) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (threadIdx.x == 0) sm.s_last = take_ticket(a.tickets + b * a.Hkv + kvh, S);
   __syncthreads();
   if (!sm.s_last) return;
   const int n = npre + S;  // <= 64 (host-checked)

@@ -103,6 +103,12 @@ __device__ __forceinline__ void store_bf16x8(bf16* p, bf16x8 v) { *reinterpret_c
 //     bf16 outputs, cascade bf16 partials: tests/test_sc1_reuse_gpu.py rewrites each buffer after readers on every
 //     XCD cached it).
 //   * sc1 load -> not served from this XCD's (possibly stale) L2.
+// The ticket protocol (split rows of the sampler and the log-probabilities, split decode attention): the workgroups of
+// a row each (1) write a partial with agent-scope stores (publish, or 16-B sc1 stores), (2) wait until their vmcnt is
+// 0, so the stores have completed at the coherent level, (3) take a RELAXED agent-scope ticket — an acq_rel one
+// compiles to buffer_wbl2 + buffer_inv: write back and drop this XCD's whole L2, in every workgroup; (4) the last
+// arrival re-arms the ticket for the next launch and (5) reads every partial with agent-scope loads (peek, load16_sc1).
+// take_ticket is steps 2 to 4. The order is the protocol: no partial store after the wait, no plain load of a partial.
 // Round 5 saw sc1 stores at other sites (RMSNorm / RoPE / tile outputs) leave wrong data (21 GPU tests, NaN in
 // test_rope_kv_write). The cause was the STORE INSTRUCTION, not the scope: an inline-asm global_store_dwordx4 is
 // opaque to hipcc's hazard recognizer, and on gfx9 a VMEM store of more than 8 bytes followed by a VALU write of its
@@ -118,6 +124,21 @@ __device__ __forceinline__ void store_bf16x8(bf16* p, bf16x8 v) { *reinterpret_c
 // registers right after the store.
 __device__ __forceinline__ void store16_slab(float* p, f32x4 v) {
   asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, off sc1\n\ts_nop 4" ::"v"(p), "v"(v) : "memory");
+}
+// one word of a partial, agent scope
+__device__ __forceinline__ void publish(int* p, int v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int peek(const int* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// One thread, for its wave (whose lanes' partial stores the wait covers) or, after a barrier behind every wave's own
+// wait_vmcnt<0>(), for its workgroup: true for the last of the n arrivals, which has re-armed the ticket.
+__device__ __forceinline__ bool take_ticket(int* tk, int n) {
+  wait_vmcnt<0>();
+  const bool last = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n - 1;
+  if (last) publish(tk, 0);
+  return last;
 }
 
 // raw buffer over 2 GiB from a wave-uniform base (gfx9 dword3: untyped 32-bit data); loads through it are compiler

@@ -5,7 +5,7 @@
 // not what the sampler drew from. Per row:
 //   lse       = log sum_i exp(x_i)          fp32: max of the slice, then sum of exp(x - max), rescaled at the merge
 //   tok_lp    = x[token] - lse
-//   top_id[j] = the j-th entry in the order (value descending, index ascending) — `better()` of sampling.hip; bf16
+//   top_id[j] = the j-th entry in the order (value descending, index ascending) — `better()` of row_scan.h; bf16
 //               logits over 128k entries tie all the time, so the rule is exact, not "some index of the j-th value"
 //   top_lp[j] = x[top_id[j]] - lse;  slots past the row's length (V < K) hold id -1 and -inf
 // A NaN entry counts as -inf everywhere (it never wins a comparison and adds nothing to the sum), so an id is
@@ -17,10 +17,8 @@
 // HBM: every thread keeps the best of its entries below a bound, each wave draws K winners from its 64 lanes (the
 // winner's lane alone rescans its registers), and wave 0 merges the 16 sorted wave lists by their heads. With
 // nsplit > 1 the workgroup publishes (max, sum, its K winners) and the last of a row's workgroups to take its ticket
-// merges the nsplit sorted lists the same way — the sampler's publication protocol as it stands: agent-scope relaxed
-// stores, s_waitcnt vmcnt(0), a relaxed ticket the merger re-arms, agent-scope loads of the partials (an acq_rel
-// ticket would write back and drop the XCD's whole L2 in every workgroup).
-#include "common.h"
+// merges the nsplit sorted lists the same way (the ticket protocol of common.h).
+#include "row_scan.h"
 
 namespace kafka {
 
@@ -31,58 +29,8 @@ constexpr int LP_NV = 2;               // 8-entry vectors a thread holds in regi
 constexpr int LP_MAX_ROWS = 8192;      // ws: tickets [LP_MAX_ROWS] | partials [R][nsplit][LP_PART]
 constexpr int LP_MAX_SPLIT = 64;       // one lane per split in the merge
 constexpr int LP_PART = 2 + 2 * LP_KMAX;  // (max bits, sum bits, K x (value bits, index))
-constexpr int LP_NONE = 0x7fffffff;
-
-// 8 consecutive logits as fp32. AL: the address is 16-byte aligned (every row is: base and row stride) -> 16-byte
-// loads; otherwise (a view with an odd row stride) element loads — correct, not fast.
-template <typename T, bool AL>
-struct LVec8 {
-  static __device__ __forceinline__ void load(const T* p, float (&v)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)p[j];
-  }
-};
-template <>
-struct LVec8<bf16, true> {
-  static __device__ __forceinline__ void load(const bf16* p, float (&v)[8]) {
-    bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)a[j];
-  }
-};
-template <>
-struct LVec8<float, true> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[8]) {
-    f32x4 a = *reinterpret_cast<const f32x4*>(p);
-    f32x4 b = *reinterpret_cast<const f32x4*>(p + 4);
-    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-    v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-  }
-};
-
-struct Cand {
-  float v;
-  int i;
-};
 
 __device__ __forceinline__ float no_nan(float v) { return v == v ? v : -INFINITY; }
-
-__device__ __forceinline__ Cand cand_better(Cand a, Cand b) {
-  if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-  return a;
-}
-
-// c comes strictly after b in the order (value descending, index ascending)
-__device__ __forceinline__ bool cand_after(Cand c, Cand b) { return c.v < b.v || (c.v == b.v && c.i > b.i); }
-
-__device__ __forceinline__ Cand wave_best(Cand a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    Cand b{__shfl_xor(a.v, o, 64), __shfl_xor(a.i, o, 64)};
-    a = cand_better(a, b);
-  }
-  return a;
-}
 
 // The entries this thread owns: vectors v0 + tid, v0 + tid + 1024, ... below v1 (in `reg` when REG, else re-read) and
 // the tail entry `ti` (>= 0 for the first V % 8 threads of the row's last split).
@@ -99,12 +47,14 @@ __device__ __forceinline__ void own_entries(const T* __restrict__ x, const float
       }
     }
   } else {
-    for (int vi = v0 + threadIdx.x; vi < v1; vi += LNT) {
-      float v[8];
-      LVec8<T, AL>::load(x + (int64_t)vi * 8, v);
+    scan_slice<LNT>(
+        RowSlice{v0, v1, 0, 0},  // (the tail entry is in tv)
+        [&](int i0, float (&v)[8]) {
+          Vec8<T, AL>::load(x + i0, v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) f(no_nan(v[j]), vi * 8 + j);
-    }
+          for (int j = 0; j < 8; ++j) v[j] = no_nan(v[j]);
+        },
+        [&](int) { return 0.f; }, f);
   }
   if (ti >= 0) f(tv, ti);
 }
@@ -112,10 +62,10 @@ __device__ __forceinline__ void own_entries(const T* __restrict__ x, const float
 template <typename T, bool REG, bool AL>
 __device__ __forceinline__ Cand own_best(const T* __restrict__ x, const float (&reg)[LP_NV][8], int v0, int v1, int ti,
                                          float tv, Cand bound) {
-  Cand best{-INFINITY, LP_NONE};
+  Cand best{-INFINITY, CAND_NONE};
   own_entries<T, REG, AL>(x, reg, v0, v1, ti, tv, [&](float v, int i) {
     const Cand c{v, i};
-    if (cand_after(c, bound)) best = cand_better(best, c);
+    if (cand_after(c, bound)) best = better(best, c);
   });
   return best;
 }
@@ -124,15 +74,15 @@ __device__ __forceinline__ Cand own_best(const T* __restrict__ x, const float (&
 // lane j returns winner j.
 __device__ __forceinline__ Cand merge_heads(const float* lv, const int* li, int n, int K, int lane) {
   int pos = 0;
-  Cand head{-INFINITY, LP_NONE};
+  Cand head{-INFINITY, CAND_NONE};
   if (lane < n) head = Cand{lv[lane * K], li[lane * K]};
-  Cand mine{-INFINITY, LP_NONE};
+  Cand mine{-INFINITY, CAND_NONE};
   for (int r = 0; r < K; ++r) {
     const Cand w = wave_best(head);
     if (lane == r) mine = w;
-    if (lane < n && head.i == w.i && w.i != LP_NONE) {
+    if (lane < n && head.i == w.i && w.i != CAND_NONE) {
       ++pos;
-      head = pos < K ? Cand{lv[lane * K + pos], li[lane * K + pos]} : Cand{-INFINITY, LP_NONE};
+      head = pos < K ? Cand{lv[lane * K + pos], li[lane * K + pos]} : Cand{-INFINITY, CAND_NONE};
     }
   }
   return mine;
@@ -152,11 +102,9 @@ __global__ __launch_bounds__(LNT) void token_logprobs_kernel(const T* __restrict
   const int row = rows ? rows[r] : r;
   const T* x = logits + (int64_t)row * stride;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nvec = V >> 3;
-  const int tail0 = nvec << 3;
-  const int per = (nvec + nsplit - 1) / nsplit;
-  const int v0 = sp * per, v1 = min(nvec, v0 + per);
-  const int ti = (sp == nsplit - 1 && tail0 + tid < V) ? tail0 + tid : -1;
+  const RowSlice sl = row_slice(V, sp, nsplit);
+  const int v0 = sl.v0, v1 = sl.v1;
+  const int ti = sl.t0 + tid < sl.t1 ? sl.t0 + tid : -1;
   const float tv = ti >= 0 ? no_nan((float)x[ti]) : -INFINITY;
   float reg[LP_NV][8];
   if constexpr (REG) {
@@ -164,7 +112,7 @@ __global__ __launch_bounds__(LNT) void token_logprobs_kernel(const T* __restrict
     for (int k = 0; k < LP_NV; ++k) {
       const int vi = v0 + tid + k * LNT;
       if (vi < v1) {
-        LVec8<T, AL>::load(x + (int64_t)vi * 8, reg[k]);
+        Vec8<T, AL>::load(x + (int64_t)vi * 8, reg[k]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) reg[k][j] = no_nan(reg[k][j]);
       }
@@ -181,7 +129,7 @@ __global__ __launch_bounds__(LNT) void token_logprobs_kernel(const T* __restrict
   s = block_sum<LNT>(s, red);
 
   // K winners of the slice: per wave from its lanes' bests, then wave 0 over the 16 wave lists
-  Cand mine{-INFINITY, LP_NONE};
+  Cand mine{-INFINITY, CAND_NONE};
   if (K > 0) {
     Cand cur = own_best<T, REG, AL>(x, reg, v0, v1, ti, tv, Cand{INFINITY, -1});
     for (int j = 0; j < K; ++j) {
@@ -190,7 +138,7 @@ __global__ __launch_bounds__(LNT) void token_logprobs_kernel(const T* __restrict
         lv[wave * K + j] = w.v;
         li[wave * K + j] = w.i;
       }
-      if (cur.i == w.i && w.i != LP_NONE) cur = own_best<T, REG, AL>(x, reg, v0, v1, ti, tv, w);
+      if (cur.i == w.i && w.i != CAND_NONE) cur = own_best<T, REG, AL>(x, reg, v0, v1, ti, tv, w);
     }
     __syncthreads();
     if (wave != 0) return;
@@ -201,31 +149,24 @@ __global__ __launch_bounds__(LNT) void token_logprobs_kernel(const T* __restrict
 
   float lse = ms + __logf(s);
   if (nsplit > 1) {
-    // ws: tickets (zero, re-armed here) | [R][nsplit][LP_PART]
-    int* tk_row = ws + r;
-    int* part = ws + LP_MAX_ROWS + ((int64_t)r * nsplit + sp) * LP_PART;
+    // ws: tickets (zero, re-armed by the last arrival) | [R][nsplit][LP_PART]; the ticket protocol of common.h
+    int* p0 = ws + LP_MAX_ROWS + (int64_t)r * nsplit * LP_PART;
+    int* part = p0 + sp * LP_PART;
     if (lane == 0) {
-      __hip_atomic_store(part, __float_as_int(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(part + 1, __float_as_int(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      publish(part, __float_as_int(m));
+      publish(part + 1, __float_as_int(s));
     }
     if (lane < K) {
-      __hip_atomic_store(part + 2 + 2 * lane, __float_as_int(mine.v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(part + 3 + 2 * lane, mine.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      publish(part + 2 + 2 * lane, __float_as_int(mine.v));
+      publish(part + 3 + 2 * lane, mine.i);
     }
-    // as the sampler's ticket (sampling.hip): every lane's agent-scope stores above have completed at the coherent
-    // level once this wave's vmcnt is 0, then a RELAXED ticket; the last workgroup reads the partials with
-    // agent-scope loads, which do not hit a stale L2 line
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add(tk_row, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t = __shfl(t, 0, 64);
-    if (t != nsplit - 1) return;
-    if (lane == 0) __hip_atomic_store(tk_row, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int* p0 = ws + LP_MAX_ROWS + (int64_t)r * nsplit * LP_PART;
+    int last = 0;
+    if (lane == 0) last = take_ticket(ws + r, nsplit);  // (its wait is the wave's: every lane's stores above)
+    if (!__shfl(last, 0, 64)) return;
     float pm = -INFINITY, ps = 0.f;
     if (lane < nsplit) {
-      pm = __int_as_float(__hip_atomic_load(p0 + lane * LP_PART, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      ps = __int_as_float(__hip_atomic_load(p0 + lane * LP_PART + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      pm = __int_as_float(peek(p0 + lane * LP_PART));
+      ps = __int_as_float(peek(p0 + lane * LP_PART + 1));
     }
     const float gm = wave_max(pm);
     const float gms = gm == -INFINITY ? 0.f : gm;
@@ -235,8 +176,8 @@ __global__ __launch_bounds__(LNT) void token_logprobs_kernel(const T* __restrict
       // the nsplit sorted lists into LDS (only this wave is left in the workgroup), then merged by their heads
       for (int e = lane; e < nsplit * K; e += 64) {
         const int* q = p0 + (e / K) * LP_PART + 2 + 2 * (e % K);
-        lv[e] = __int_as_float(__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        li[e] = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        lv[e] = __int_as_float(peek(q));
+        li[e] = peek(q + 1);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -246,7 +187,7 @@ __global__ __launch_bounds__(LNT) void token_logprobs_kernel(const T* __restrict
   }
 
   if (lane < K) {
-    const bool ok = mine.i != LP_NONE;
+    const bool ok = mine.i != CAND_NONE;
     top_id[(int64_t)r * ld + lane] = ok ? mine.i : -1;
     top_lp[(int64_t)r * ld + lane] = ok ? mine.v - lse : -INFINITY;
   }

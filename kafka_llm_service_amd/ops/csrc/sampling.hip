@@ -18,60 +18,12 @@
 // takes a slice of the vocabulary, publishes its (value, index) winner, and the last of a row's workgroups to take
 // its ticket reduces them — the noise of index i is the same in every split, so the token is the one-workgroup
 // result. A 64-row decode batch then runs 512 workgroups instead of 64 (128k-entry rows: 62 -> ~10 us).
-#include "common.h"
+#include "row_scan.h"
 
 namespace kafka {
 
-template <typename T>
-struct Vec8;
-template <>
-struct Vec8<bf16> {
-  static __device__ __forceinline__ void load(const bf16* p, float (&v)[8]) {
-    bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)a[j];
-  }
-};
-template <>
-struct Vec8<float> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[8]) {
-    f32x4 a = *reinterpret_cast<const f32x4*>(p);
-    f32x4 b = *reinterpret_cast<const f32x4*>(p + 4);
-    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-    v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-  }
-};
-
 constexpr int SNT = 1024;
 constexpr int SAMPLE_MAX_ROWS = 65536;  // ws: tickets [SAMPLE_MAX_ROWS] | partials [B][nsplit][2]
-
-struct ArgMax {
-  float v;
-  int i;
-};
-
-__device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) {
-  if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-  return a;
-}
-
-__device__ __forceinline__ ArgMax block_argmax(ArgMax a, float* sv, int* si) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ArgMax b{__shfl_xor(a.v, o, 64), __shfl_xor(a.i, o, 64)};
-    a = better(a, b);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sv[w] = a.v;
-    si[w] = a.i;
-  }
-  __syncthreads();
-  ArgMax r{sv[0], si[0]};
-  for (int k = 1; k < SNT / 64; ++k) r = better(r, ArgMax{sv[k], si[k]});
-  __syncthreads();
-  return r;
-}
 
 __device__ __forceinline__ float gumbel(uint64_t seed, uint64_t stream, uint64_t idx) {
   const float u = uniform01(seed, stream, idx);  // (0, 1]
@@ -256,6 +208,30 @@ __device__ __forceinline__ void emit_token(int64_t* out_tokens, int row, int tok
   }
 }
 
+// One pass over slice s of the row as the sampler sees it: f(x_i * inv_t, i) over the processed logits.
+template <typename T, bool PROC, bool REP, typename F>
+__device__ __forceinline__ void scan_row(const T* x, const RowProc& rp, const RowSlice& s, float inv_t, F&& f) {
+  scan_slice<SNT>(
+      s, [&](int i0, float (&v)[8]) { load8p<T, PROC, REP>(x, i0, rp, v); },
+      [&](int i) { return load1p<T, PROC, REP>(x, i, rp); }, [&](float v, int i) { f(v * inv_t, i); });
+}
+
+// Thread 0 of split sp publishes the split's two-int partial and takes the row's ticket (the ticket protocol of
+// common.h); the last of the row's nsplit arrivals reads every pair, g(k, a_k, b_k), and gets true.
+// ws: tickets (zero, re-armed by the last arrival) | [B][nsplit][2]
+template <typename G>
+__device__ __forceinline__ bool publish_pair(int* ws, int row, int sp, int nsplit, int a, int b, G&& g) {
+  int* p0 = ws + SAMPLE_MAX_ROWS + (int64_t)row * nsplit * 2;
+  publish(p0 + 2 * sp, a);
+  publish(p0 + 2 * sp + 1, b);
+  if (!take_ticket(ws + row, nsplit)) return false;
+  for (int k = 0; k < nsplit; ++k) {
+    const int ak = peek(p0 + 2 * k), bk = peek(p0 + 2 * k + 1);
+    g(k, ak, bk);
+  }
+  return true;
+}
+
 // the split's LDS, outside the template so that a kernel with two row bodies holds it once
 struct MinPLds {
   float* pm;
@@ -286,82 +262,45 @@ __device__ __forceinline__ void sample_min_p_split(const T* x, int V, const RowP
   float* pm = lds.pm;
   int *pw = lds.pw, *pflag = lds.pflag;
   int& s_last = *lds.last;
-  const int nvec = V >> 3, tail0 = nvec << 3;
-  const int per = (nvec + nsplit - 1) / nsplit;
-  // best of xv + noise over slice k's tokens with xv >= thr (the last slice owns the scalar tail)
-  auto scan = [&](int k, float thr, ArgMax a) -> ArgMax {
-    const int v0 = k * per, v1 = min(nvec, v0 + per);
-    for (int vi = v0 + threadIdx.x; vi < v1; vi += SNT) {
-      float v[8];
-      load8p<T, true, REP>(x, vi * 8, rp, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float xv = v[j] * inv_t;
-        if (xv >= thr) a = better(a, ArgMax{xv + gumbel_fast(key, vi * 8 + j), vi * 8 + j});
-      }
-    }
-    if (k == nsplit - 1)
-      for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
-        const float xv = load1p<T, true, REP>(x, i, rp) * inv_t;
-        if (xv >= thr) a = better(a, ArgMax{xv + gumbel_fast(key, i), i});
-      }
+  // best of xv + noise over slice k's tokens with xv >= thr
+  auto scan = [&](int k, float thr, Cand a) -> Cand {
+    scan_row<T, true, REP>(x, rp, row_slice(V, k, nsplit), inv_t, [&](float xv, int i) {
+      if (xv >= thr) a = better(a, Cand{xv + gumbel_fast(key, i), i});
+    });
     return a;
   };
   float m = -INFINITY;
-  {
-    const int v0 = sp * per, v1 = min(nvec, v0 + per);
-    for (int vi = v0 + threadIdx.x; vi < v1; vi += SNT) {
-      float v[8];
-      load8p<T, true, REP>(x, vi * 8, rp, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) m = fmaxf(m, v[j] * inv_t);
-    }
-    if (sp == nsplit - 1)
-      for (int i = tail0 + threadIdx.x; i < V; i += SNT) m = fmaxf(m, load1p<T, true, REP>(x, i, rp) * inv_t);
-  }
+  scan_row<T, true, REP>(x, rp, row_slice(V, sp, nsplit), inv_t, [&](float xv, int) { m = fmaxf(m, xv); });
   m = block_max<SNT>(m, red);
-  ArgMax a = block_argmax(scan(sp, m + rp.lmp, ArgMax{-INFINITY, 0x7fffffff}), sv, si);
+  Cand a = block_argmax<SNT>(scan(sp, m + rp.lmp, Cand{-INFINITY, CAND_NONE}), sv, si);
   if (nsplit == 1) {  // one slice: its threshold is the row's
     if (threadIdx.x == 0) emit_token<true>(out_tokens, row, a.i, V, rp);
     return;
   }
-  if (threadIdx.x == 0) {  // the ticket protocol of the plain rows (sample_kernel), its order unchanged
-    int* tk_row = ws + row;
-    int* part = ws + SAMPLE_MAX_ROWS + ((int64_t)row * nsplit + sp) * 2;
-    __hip_atomic_store(part, __float_as_int(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(part + 1, a.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = __hip_atomic_fetch_add(tk_row, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = t == nsplit - 1;
-    if (last) {
-      __hip_atomic_store(tk_row, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int* p0 = ws + SAMPLE_MAX_ROWS + (int64_t)row * nsplit * 2;
-      for (int k = 0; k < nsplit; ++k) {
-        pm[k] = __int_as_float(__hip_atomic_load(p0 + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        pw[k] = __hip_atomic_load(p0 + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    s_last = last;
-  }
+  if (threadIdx.x == 0)
+    s_last = publish_pair(ws, row, sp, nsplit, __float_as_int(m), a.i, [&](int k, int mk, int wk) {
+      pm[k] = __int_as_float(mk);
+      pw[k] = wk;
+    });
   __syncthreads();
   if (!s_last) return;  // (uniform) the whole last workgroup stays: a rescan is a job for all of it
   float M = -INFINITY;
   for (int k = 0; k < nsplit; ++k) M = fmaxf(M, pm[k]);
   const float thr = M + rp.lmp;
-  ArgMax r{-INFINITY, 0x7fffffff};
+  Cand r{-INFINITY, CAND_NONE};
   if ((int)threadIdx.x < nsplit) {  // thread k judges slice k
     const int w = pw[threadIdx.x];
     int flag = 0;
     if (pm[threadIdx.x] >= thr && w >= 0 && w < V) {
       const float xv = load1p<T, true, REP>(x, w, rp) * inv_t;
-      if (xv >= thr) r = ArgMax{xv + gumbel_fast(key, w), w}; else flag = 1;
+      if (xv >= thr) r = Cand{xv + gumbel_fast(key, w), w}; else flag = 1;
     }
     pflag[threadIdx.x] = flag;
   }
   __syncthreads();
   for (int k = 0; k < nsplit; ++k)
     if (pflag[k]) r = scan(k, thr, r);
-  r = block_argmax(r, sv, si);
+  r = block_argmax<SNT>(r, sv, si);
   if (threadIdx.x == 0) emit_token<true>(out_tokens, row, r.i, V, rp);
 }
 
@@ -374,8 +313,6 @@ __device__ __forceinline__ void sample_row(const T* x, int V, const float* tempe
                                            int64_t* out_tokens, int max_rounds, int* ws, const RowProc& rp, int row,
                                            int sp, int nsplit, float* sv, int* si, float* red) {
   const float temp = temperature ? temperature[row] : 0.f;
-  const int nvec = V >> 3;
-  const int tail0 = nvec << 3;
   const float tp = top_p ? top_p[row] : 1.f;
   const int tk = top_k ? top_k[row] : 0;
   const bool filtered = temp > 0.f && ((tp < 1.f) || (tk > 0 && tk < V));
@@ -393,73 +330,34 @@ __device__ __forceinline__ void sample_row(const T* x, int V, const float* tempe
         return;
       }
     }
-    const int per = (nvec + nsplit - 1) / nsplit;
-    const int v0 = sp * per, v1 = min(nvec, v0 + per);
-    ArgMax a{-INFINITY, 0x7fffffff};
-    for (int vi = v0 + threadIdx.x; vi < v1; vi += SNT) {
-      float v[8];
-      load8p<T, PROC, REP>(x, vi * 8, rp, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float xv = v[j] * inv_t;
-        a = better(a, ArgMax{greedy ? xv : xv + gumbel_fast(key, vi * 8 + j), vi * 8 + j});
-      }
-    }
-    if (sp == nsplit - 1)
-      for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
-        const float xv = load1p<T, PROC, REP>(x, i, rp) * inv_t;
-        a = better(a, ArgMax{greedy ? xv : xv + gumbel_fast(key, i), i});
-      }
-    a = block_argmax(a, sv, si);
+    Cand a{-INFINITY, CAND_NONE};
+    scan_row<T, PROC, REP>(x, rp, row_slice(V, sp, nsplit), inv_t, [&](float xv, int i) {
+      a = better(a, Cand{greedy ? xv : xv + gumbel_fast(key, i), i});
+    });
+    a = block_argmax<SNT>(a, sv, si);
     if (threadIdx.x != 0) return;
-    if (nsplit == 1) {
-      emit_token<PROC>(out_tokens, row, a.i, V, rp);
-      return;
+    if (nsplit > 1) {  // the row's token is the best of its splits' winners: the last split to arrive finds it
+      const Cand mine = a;
+      a = Cand{-INFINITY, CAND_NONE};
+      if (!publish_pair(ws, row, sp, nsplit, __float_as_int(mine.v), mine.i,
+                        [&](int, int vk, int ik) { a = better(a, Cand{__int_as_float(vk), ik}); }))
+        return;
     }
-    // ws: tickets (zero, re-armed here) | [B][nsplit][2] (value bits, index)
-    int* tk_row = ws + row;
-    int* part = ws + SAMPLE_MAX_ROWS + ((int64_t)row * nsplit + sp) * 2;
-    __hip_atomic_store(part, __float_as_int(a.v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(part + 1, a.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // the ticket as the decode kernel's (attention.hip): the agent-scope stores above have completed at the coherent
-    // level once vmcnt is 0, then a RELAXED ticket — an acq_rel one compiles to buffer_wbl2 + buffer_inv (write back
-    // and drop this XCD's whole L2) in every one of the B x nsplit workgroups; the last one reads the partials with
-    // agent-scope (sc1) loads, which do not hit a stale L2 line
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = __hip_atomic_fetch_add(tk_row, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t != nsplit - 1) return;
-    __hip_atomic_store(tk_row, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int* p0 = ws + SAMPLE_MAX_ROWS + (int64_t)row * nsplit * 2;
-    ArgMax r{-INFINITY, 0x7fffffff};
-    for (int k = 0; k < nsplit; ++k)
-      r = better(r, ArgMax{__int_as_float(__hip_atomic_load(p0 + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)),
-                           __hip_atomic_load(p0 + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)});
-    emit_token<PROC>(out_tokens, row, r.i, V, rp);
+    emit_token<PROC>(out_tokens, row, a.i, V, rp);
     return;
   }
   if (sp != 0) return;  // top-k / top-p rows: one workgroup runs the whole-row rejection sampler
+  const RowSlice all = row_slice(V, 0, 1);
   const float inv_t = 1.f / temp;
   const int64_t step = step_ptr ? step_ptr[0] : 0;
   const uint64_t seed = seeds ? (uint64_t)seeds[row] : 0x1234ull;
 
-  // pass 1: max of x (needed for the mass test only)
+  // max of x (needed for the mass test only), then z = sum of exp(x - max)
   float mx = -INFINITY;
-  float z = 0.f;
-  for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
-    float v[8];
-    load8p<T, PROC, REP>(x, vi * 8, rp, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) mx = fmaxf(mx, v[j] * inv_t);
-  }
-  for (int i = tail0 + threadIdx.x; i < V; i += SNT) mx = fmaxf(mx, load1p<T, PROC, REP>(x, i, rp) * inv_t);
+  scan_row<T, PROC, REP>(x, rp, all, inv_t, [&](float xv, int) { mx = fmaxf(mx, xv); });
   mx = block_max<SNT>(mx, red);
-  for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
-    float v[8];
-    load8p<T, PROC, REP>(x, vi * 8, rp, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z += __expf(v[j] * inv_t - mx);
-  }
-  for (int i = tail0 + threadIdx.x; i < V; i += SNT) z += __expf(load1p<T, PROC, REP>(x, i, rp) * inv_t - mx);
+  float z = 0.f;
+  scan_row<T, PROC, REP>(x, rp, all, inv_t, [&](float xv, int) { z += __expf(xv - mx); });
   z = block_sum<SNT>(z, red);
   // min_p: a candidate also passes the row's threshold (z and the mass stay the whole row's: the ratio to the maximum
   // does not change under renormalisation). The maximum passes its own threshold, so round 0 has a candidate.
@@ -469,44 +367,29 @@ __device__ __forceinline__ void sample_row(const T* x, int V, const float* tempe
   int result = -1;
   for (int round = 0; round < max_rounds; ++round) {
     const uint64_t stream = ((uint64_t)step << 8) ^ (uint64_t)round;
-    ArgMax a{-INFINITY, 0x7fffffff};
-    for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
+    Cand a{-INFINITY, CAND_NONE};
+    // scan_slice's loop pair over `all`, in its order, written out: as a scan_row call this pass spills SGPRs in the
+    // REP instantiation (profiles/sampler_rowscan/resource_usage.txt)
+    auto draw = [&](float xv, int i) {
+      if (PROC ? (xv > pivot && xv >= thr) : xv > pivot) a = better(a, Cand{xv + gumbel(seed, stream, i), i});
+    };
+    for (int vi = all.v0 + threadIdx.x; vi < all.v1; vi += SNT) {
       float v[8];
       load8p<T, PROC, REP>(x, vi * 8, rp, v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float xv = v[j] * inv_t;
-        if (PROC ? (xv > pivot && xv >= thr) : xv > pivot)
-          a = better(a, ArgMax{xv + gumbel(seed, stream, vi * 8 + j), vi * 8 + j});
-      }
+      for (int j = 0; j < 8; ++j) draw(v[j] * inv_t, vi * 8 + j);
     }
-    for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
-      const float xv = load1p<T, PROC, REP>(x, i, rp) * inv_t;
-      if (PROC ? (xv > pivot && xv >= thr) : xv > pivot) a = better(a, ArgMax{xv + gumbel(seed, stream, i), i});
-    }
-    a = block_argmax(a, sv, si);
-    if (a.i == 0x7fffffff) break;
+    for (int i = all.t0 + threadIdx.x; i < all.t1; i += SNT) draw(load1p<T, PROC, REP>(x, i, rp) * inv_t, i);
+    a = block_argmax<SNT>(a, sv, si);
+    if (a.i == CAND_NONE) break;
     const float xc = load1p<T, PROC, REP>(x, a.i, rp) * inv_t;
     float mass = 0.f, cnt = 0.f;
-    for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
-      float v[8];
-      load8p<T, PROC, REP>(x, vi * 8, rp, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float xv = v[j] * inv_t;
-        if (xv > xc) {
-          mass += __expf(xv - mx);
-          cnt += 1.f;
-        }
-      }
-    }
-    for (int i = tail0 + threadIdx.x; i < V; i += SNT) {
-      const float xv = load1p<T, PROC, REP>(x, i, rp) * inv_t;
+    scan_row<T, PROC, REP>(x, rp, all, inv_t, [&](float xv, int) {
       if (xv > xc) {
         mass += __expf(xv - mx);
         cnt += 1.f;
       }
-    }
+    });
     mass = block_sum<SNT>(mass, red) / z;
     cnt = block_sum<SNT>(cnt, red);
     const bool ok_p = mass < tp;
@@ -517,17 +400,10 @@ __device__ __forceinline__ void sample_row(const T* x, int V, const float* tempe
     }
     pivot = xc;
   }
-  if (result < 0) {  // fallback: argmax
-    ArgMax a{-INFINITY, 0x7fffffff};
-    for (int vi = threadIdx.x; vi < nvec; vi += SNT) {
-      float v[8];
-      load8p<T, PROC, REP>(x, vi * 8, rp, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a = better(a, ArgMax{v[j], vi * 8 + j});
-    }
-    for (int i = tail0 + threadIdx.x; i < V; i += SNT) a = better(a, ArgMax{load1p<T, PROC, REP>(x, i, rp), i});
-    a = block_argmax(a, sv, si);
-    result = a.i;
+  if (result < 0) {  // fallback: argmax of the processed row itself (x * 1)
+    Cand a{-INFINITY, CAND_NONE};
+    scan_row<T, PROC, REP>(x, rp, all, 1.f, [&](float v, int i) { a = better(a, Cand{v, i}); });
+    result = block_argmax<SNT>(a, sv, si).i;
   }
   if (threadIdx.x == 0) emit_token<PROC>(out_tokens, row, result, V, rp);
 }

@@ -292,6 +292,84 @@ def test_sample_ragged_vocab_matches_replay(cuda, V):
                 _same(out, rep, f"{msg}, nsplit {nsplit}")
 
 
+def _padded(cuda, x):
+    """x on the device in rows of a padded stride whose padding holds the dtype's largest finite value."""
+    B, V = x.shape
+    buf = torch.full((B, (V + 7) // 8 * 8 + 8), torch.finfo(x.dtype).max, dtype=x.dtype, device=cuda)
+    buf[:, :V] = x.to(cuda)
+    return buf[:, :V]
+
+
+@pytest.mark.gpu
+def test_sample_fallback_argmax_matches_replay(cuda):
+    """A top_p that no mass is below accepts no candidate, so the pivot climbs until nothing lies above it and every row
+    ends in the fallback: the fp32 argmax of the row itself, over its vectors and its scalar tail, not past V. The
+    value is -1, not 0: the mass above the row's maximum is exactly 0, which the replay's band around ``mass < top_p``
+    (SAMPLE_MASS_BAND) has to call ambiguous in every row; against -1 no mass is anywhere near."""
+    from kafka_llm_service_amd.ops._ext import ext
+
+    B, V = 8, 1031
+    x = torch.randn(B, V, generator=torch.Generator().manual_seed(77)) * 3
+    x[0::3, V - 1] = x[0::3].max(1).values + 1  # rows 0, 3 and 6 peak at the tail's end
+    temp = torch.tensor([0.5, 0.7, 1.0, 1.5] * 2)
+    seeds = torch.arange(B, dtype=torch.long) * 7919 + 5
+    step = torch.tensor([4], dtype=torch.long)
+    topp = torch.full((B,), -1.0)
+    rep = ref.sample_replay(x, temp, topp, None, seeds, step)
+    msg = _capped(rep, "fallback V 1031")
+    assert bool(rep.fell_back.all()), msg
+    assert torch.equal(rep.tokens, x.argmax(-1)) and int((rep.tokens >= V // 8 * 8).sum()) >= 3, msg
+    xg = _padded(cuda, x)
+    for nsplit in (1, 8):
+        out = torch.full((B,), -1, dtype=torch.long, device=cuda)
+        ext().sample(xg, temp.to(cuda), topp.to(cuda), None, seeds.to(cuda), step.to(cuda), out, _ws(cuda, B, nsplit),
+                     nsplit)
+        _same(out, rep, f"{msg}, nsplit {nsplit}")
+        assert torch.equal(out.cpu(), x.argmax(-1))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V,owning", [(1031, 64), (1039, 43)])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_sample_64_splits_short_ragged_row_matches_replay(cuda, dtype, V, owning):
+    """A short ragged row over 64 splits. V = 1031: 128 vectors, two in every slice, the last slice also owns the tail
+    of 7. V = 1039: 129 vectors, three per slice, so slices 0..42 own vectors and 43..63 own none — a greedy or plain
+    split with nothing to offer, a min_p split that publishes (-inf, no winner) — and the empty last slice still owns
+    the tail of 7. Greedy, plain-temperature and min_p rows (proc[7]), three launches on one workspace (the tickets
+    re-arm): the tokens are the replay's at 64 splits and those of the one-workgroup launch."""
+    from test_min_p import min_p_proc
+
+    from kafka_llm_service_amd.ops._ext import ext
+
+    B, NS = 16, 64
+    nvec = V // 8
+    per = -(-nvec // NS)  # the kernel's partition (row_slice): slice k holds the vectors [k * per, min(nvec, k * per + per))
+    assert sum(k * per < nvec for k in range(NS)) == owning and V - nvec * 8 == 7
+    x = torch.randn(B, V, generator=torch.Generator().manual_seed(64)) * 3
+    x[0::3, V - 1] = x[0::3].max(1).values + 1
+    x = x.to(dtype)
+    temp, seeds = _mixed_params(B, seed0=V)  # rows 0, 4, 8, 12 greedy
+    step = torch.tensor([6], dtype=torch.long)
+    proc = min_p_proc(B, [0.1 if i % 2 else 0.0 for i in range(B)])  # odd rows: min_p under temperature
+    assert bool((proc[1::2, 7] != 0).all()) and not bool(proc[0::2, 7].any())
+    rep = ref.sample_replay(x, temp, seeds=seeds, step=step, proc=proc, nsplit=NS)
+    msg = _capped(rep, f"64 splits V {V} {dtype}")
+    assert torch.equal(rep.tokens, ref.sample_replay(x, temp, seeds=seeds, step=step, proc=proc, nsplit=1).tokens)
+    assert torch.equal(rep.tokens[0::4], x[0::4].float().argmax(-1))
+    xg, pg = _padded(cuda, x), proc.to(cuda)
+    mt = torch.zeros(1, (V + 31) // 32, dtype=torch.int32, device=cuda)
+    one = torch.full((B,), -1, dtype=torch.long, device=cuda)
+    ext().sample(xg, temp.to(cuda), None, None, seeds.to(cuda), step.to(cuda), one, None, 1, pg, mt, None, None)
+    _same(one, rep, f"{msg}, one workgroup")
+    ws = _ws(cuda, B, NS)
+    for launch in range(3):
+        out = torch.full((B,), -1, dtype=torch.long, device=cuda)
+        ext().sample(xg, temp.to(cuda), None, None, seeds.to(cuda), step.to(cuda), out, ws, NS, pg, mt, None, None)
+        _same(out, rep, f"{msg}, launch {launch}")
+        assert torch.equal(out, one), f"{msg}, launch {launch}: 64 splits differ from one workgroup"
+    assert not bool(ws[:65536].any())  # every ticket re-armed
+
+
 def _filtered_case(V, dtype):
     """Rows walk the product top_k x top_p x T (64 rows over two steps, stride 7 through its 90 entries); row 0 takes
     top_k = V with top_p = 1 (the plain stream), row 1 is a row of equal logits and row 2 a row whose maximum occurs
