@@ -7,9 +7,9 @@ Per layer (SURVEY.md §3.2 "Target equivalent"):
     -> [TP all-reduce]                                     (Mixtral: router -> expert MLPs, models/moe.py)
 Decode-sized steps (T <= 128) run every projection on the weight-streaming MFMA kernel (``ops/csrc/wstream_gemm.hip``,
 wave-tiled weight copies, SwiGLU fused into gate_up; the grouped variant for Mixtral's experts); 129..256-row mixed
-steps run qkv / o / down on the skinny MFMA GEMM (``ops/csrc/skinny_gemm.hip``, SKINNY below); other prefill-sized
-steps use hipBLASLt through ``torch.nn.functional.linear`` (bf16, fp32 accumulate). Norm / RoPE / attention / sampling run
-in the hand-written kernels of ``ops/csrc``.
+steps run qkv / o / down on the skinny MFMA GEMM (``ops/csrc/skinny_gemm.hip``, SKINNY below; bf16, fp8 and mxfp4 tiles
+alike); other prefill-sized steps use hipBLASLt through ``torch.nn.functional.linear`` (bf16, fp32 accumulate). Norm /
+RoPE / attention / sampling run in the hand-written kernels of ``ops/csrc``.
 
 Weights are stored HF-style ``[out, in]`` so safetensors checkpoints load without transposes; random init (seeded,
 synthetic benchmarks — no checkpoints are downloadable here) is the default.
@@ -40,6 +40,11 @@ TP_OVERLAP = os.environ.get("KAFKA_TP_OVERLAP", "0") == "1"
 # (ops.linear_skinny, csrc/skinny_gemm.hip) instead of hipBLASLt: env KAFKA_SKINNY, a comma list of qkv / o / down
 # ("" = none; "+" also separates). gate_up stays on hipBLASLt (faster there). Same-box A/B, 2 interleaved rounds:
 # 7,857 (none) -> 7,924 tok/s (o+down or all three), profiles/r03/skinny_gemm/bench_ab_wired.jsonl.
+# The set is the same for every tile format. fp8 and mxfp4 tiles run the kernel's quantised variants, and under the
+# rule "faster than F.linear on the dequantised copy at every row count, in both rounds, by more than the rounds differ"
+# qkv / o / down pass in both formats (1.26-2.05x) and gate_up in neither (fp8 0.87-1.05x, mxfp4 0.94-1.14x):
+# profiles/wq_skinny/skinny_fp8.jsonl, skinny_mxfp4.jsonl; headline +2.3 % (fp8) and +2.2 % (mxfp4) over the parent,
+# profiles/wq_skinny/bench_ab.jsonl.
 # Prefill-sized TP seams whose message exceeds the custom all-reduce's buffer (RCCL): the row-parallel GEMM and the
 # all-reduce are pipelined over row blocks of at least PIPE_ROWS tokens, at most PIPE_CHUNKS blocks
 # (comm.pipelined_linear_all_reduce; env KAFKA_TP_PIPE_CHUNKS, 1 = off). At Llama-3-70B TP = 8 a 2k-token chunk has
@@ -189,17 +194,18 @@ class TransformerLM:
         where their tiled copy is made (ops.tile_experts_fp8: ``w13_t`` / ``w2_t`` uint8, ``w13_s`` / ``w2_s`` fp32
         [E_local, N]; every expert-parallel rank quantises its own whole experts, rows over their whole K, so a rank's
         tiles equal the matching slice of the unsharded model's) and row-major ``w13`` / ``w2`` become the dequantised
-        experts that ``ops.grouped_gemm`` runs on prefill-sized steps. Embedding, norms and router stay bf16; the
-        skinny GEMM and the fused decode layer do not take fp8 tiles (hipBLASLt / the unfused layer run).
+        experts that ``ops.grouped_gemm`` runs on prefill-sized steps. Embedding, norms and router stay bf16;
+        129..256-row steps run the SKINNY projections on the skinny GEMM's fp8 variant; the fused decode layer does not
+        take fp8 tiles (the unfused layer runs).
 
         ``weight_dtype="mxfp4"``: the tiles of the dense projections, the lm_head and the MoE experts are OCP MXFP4 —
         e2m1 elements in 32-column blocks along K with one e8m0 exponent per block (ops.tile_weight_mxfp4: ``<name>_t``
         float4_e2m1fn_x2, ``<name>_s`` the float8_e8m0fnu block-scale image), 4.25 bits per weight. Semantics and
         exclusions are fp8's: the row-major tensors become the dequantised values (e2m1 * 2^e, exact in bf16), so every
-        step size, export and the oracle see one quantised model; no skinny GEMM, fused decode layer or overlapped TP
-        seam. Blocks run along K and every rank quantises its own shard, so a row-parallel shard cut on a multiple of
-        64 columns has exactly the matching slice of the unsharded model's tiles. The experts are quantised where
-        their tiled copy is made, as for fp8 (ops.tile_experts_mxfp4: ``w13_t`` / ``w2_t`` float4_e2m1fn_x2
+        step size, export and the oracle see one quantised model; the skinny GEMM has its mxfp4 variant, no fused decode
+        layer or overlapped TP seam. Blocks run along K and every rank quantises its own shard, so a row-parallel shard
+        cut on a multiple of 64 columns has exactly the matching slice of the unsharded model's tiles. The experts are
+        quantised where their tiled copy is made, as for fp8 (ops.tile_experts_mxfp4: ``w13_t`` / ``w2_t`` float4_e2m1fn_x2
         [E_local, N/32, K/64, 64, 16], ``w13_s`` / ``w2_s`` the e8m0 images [E_local, N/32, K/64, 32, 2]; every
         expert-parallel rank quantises its own whole experts; row-major ``w13`` / ``w2`` become the dequantised experts),
         and in tiled-only mode their single row-major copy stays unquantised bf16 as well."""
@@ -262,14 +268,14 @@ class TransformerLM:
     def _linear(self, x: torch.Tensor, w: torch.Tensor, wt: torch.Tensor | None, max_splits: int = 8,
                 kind: str = "", st: torch.Tensor | None = None):
         """x @ w^T: the weight-streaming kernel for decode-sized x (bf16 or a split-K slab out), the skinny MFMA GEMM
-        for 129..256 rows of the projections in SKINNY (bf16 tiles only), else hipBLASLt. ``st``: fp8 / mxfp4 tiles' scales."""
+        for 129..256 rows of the projections in SKINNY (tiles of every format), else hipBLASLt. ``st``: the scales of
+        fp8 / mxfp4 tiles."""
         M = x.shape[0]
         if self.stream and wt is not None:
             if 0 < M <= self.stream_max_m:
                 return ops.linear_stream(x, wt, max_splits, scale=st)
-            if kind in SKINNY and wt.dtype == torch.bfloat16 and \
-                    ops.skinny_plan(M, wt.shape[0] * 32, x.shape[1], max_splits):
-                return ops.linear_skinny(x, wt, max_splits)
+            if kind in SKINNY and ops.skinny_plan(M, wt.shape[0] * 32, x.shape[1], max_splits):
+                return ops.linear_skinny(x, wt, max_splits, scale=st)
         return F.linear(x, self._dense(w, wt, st=st))
 
     @staticmethod
@@ -344,8 +350,9 @@ class TransformerLM:
             if self.stream and lw.glu and 0 < T <= self.stream_max_m:
                 a = ops.linear_glu(x, lw.gate_up_t, scale=lw.gate_up_s)  # SwiGLU in the GEMM epilogue (or on its slabs)
             elif (self.stream and lw.glu and "gate_up" in SKINNY and lw.gate_up_t is not None
-                  and lw.gate_up_t.dtype == torch.bfloat16 and ops.skinny_plan(T, lw.gate_up_t.shape[0] * 32, x.shape[1])):
-                a = ops.linear_skinny(x, lw.gate_up_t, glu=True)  # fused SwiGLU (one split) or gate | up slabs
+                  and ops.skinny_plan(T, lw.gate_up_t.shape[0] * 32, x.shape[1])):
+                # fused SwiGLU (one split) or gate | up slabs
+                a = ops.linear_skinny(x, lw.gate_up_t, glu=True, scale=lw.gate_up_s)
                 if ops.is_slab(a):
                     a = ops.silu_mul(a)
             else:

@@ -671,25 +671,39 @@ def skinny_plan(M: int, N: int, K: int, max_splits: int = 8) -> int:
     return s
 
 
-def linear_skinny(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bool = False) -> torch.Tensor:
+def linear_skinny(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bool = False,
+                  scale: torch.Tensor | None = None) -> torch.Tensor:
     """y = x @ W^T for 129..256 rows from the wave-tiled weight (mixed decode + prefill steps): bf16 [M, N] (or the
-    activated [M, N/2] with ``glu``) for one split, else fp32 split-K slabs [S, M, N] in gate | up order for glu."""
-    if wt.dtype != torch.bfloat16:
-        _refuse_quantised("linear_skinny", wt)
+    activated [M, N/2] with ``glu``) for one split, else fp32 split-K slabs [S, M, N] in gate | up order for glu.
+    fp8 tiles (``tile_weight_fp8``) need their row scales ``scale``, MXFP4 tiles (``tile_weight_mxfp4``) their e8m0
+    block-scale image: the kernel dequantises the raw tiles next to its MFMAs, with the plan, outputs and bits of the
+    same call on the bf16 tiles of the dequantised weight."""
     M, K = x.shape
+    f = WEIGHT_FORMATS.get(wt.dtype)
+    if f is None:
+        raise ValueError(f"linear_skinny: no weight tile format has dtype {wt.dtype}")
+    if f.scale_dtype is None:
+        if scale is not None:
+            raise ValueError(f"linear_skinny: {f.name} weight tiles take no scale")
+    else:
+        _check_scale("linear_skinny", f, wt, scale)
+        if wt.shape[1] * f.vk != K:
+            raise ValueError(f"linear_skinny: x has K={K}, the {f.name} tiles K={wt.shape[1] * f.vk}")
     N = wt.shape[0] * 32
     S = skinny_plan(M, N, K, max_splits)
     if S == 0:
         raise ValueError(f"linear_skinny: unsupported shape M={M} N={N} K={K}")
     if _gpu(x):
+        y = p = None
         if S == 1:
             y = torch.empty(M, N // 2 if glu else N, dtype=x.dtype, device=x.device)
-            ext().skinny_gemm(x, wt, y, None, 1, bool(glu))
-            return y
-        p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        ext().skinny_gemm(x, wt, None, p, int(S), bool(glu))
-        return p
-    w = untile_weight(wt, glu).float()
+        else:
+            p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
+        if f.raw:
+            wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
+        ext().skinny_gemm(x, wt, y, p, int(S), bool(glu), scale, f.abi)
+        return y if S == 1 else p
+    w = f.untile(wt, scale, glu).float()
     y = x.float() @ w.t()
     if S == 1:
         return (ref.silu_mul(y) if glu else y).to(x.dtype)

@@ -803,15 +803,15 @@ static int64_t skinny_plan(int64_t M, int64_t N, int64_t K, int64_t max_splits) 
   return kafka_skinny_plan((int)M, (int)N, (int)K, (int)max_splits, &s) == 0 ? s : 0;
 }
 
+// scale and fmt come last and default to bf16 tiles without a scale, the call this entry has always taken: the tiles
+// of format fmt (WF_*) with their scales as for wstream_gemm
 static void skinny_gemm(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> y, c10::optional<at::Tensor> p,
-                        int64_t splits, bool glu) {
-  CHECK_CUDA(x); CHECK_DT(x, at::kBFloat16); CHECK_DT(wt, at::kBFloat16); CHECK_LASTDIM(x);
-  TORCH_CHECK(x.dim() == 2 && x.stride(0) % 8 == 0, "skinny_gemm: x must be [M, K] with 16-B rows");
-  TORCH_CHECK(wt.dim() == 4 && wt.is_contiguous() && wt.size(2) == 64 && wt.size(3) == 8,
-              "skinny_gemm: wt must be contiguous [N/32, K/16, 64, 8]");
+                        int64_t splits, bool glu, c10::optional<at::Tensor> scale, int64_t fmt) {
+  check_stream_x("skinny_gemm", x);
+  const int vk = check_wfmt("skinny_gemm", fmt, wt, scale, 0);
   const int M = x.size(0), K = x.size(1), N = wt.size(0) * 32;
-  TORCH_CHECK(wt.size(1) * 16 == K && M > 0 && M <= 256 && N % 128 == 0 && K % (64 * splits) == 0,
-              "skinny_gemm: shape");
+  TORCH_CHECK(splits >= 1 && wt.size(1) * vk == K && M > 0 && M <= 256 && N % 128 == 0 && K % (64 * splits) == 0,
+              "skinny_gemm: shape (x has K = ", K, ", the tiles ", wt.size(1) * vk, ")");
   bf16* yp = nullptr;
   int64_t ldy = 0;
   float* pp = nullptr;
@@ -828,8 +828,9 @@ static void skinny_gemm(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> y
                 "skinny_gemm: slab shape must be [splits, M, N]");
     pp = p->data_ptr<float>();
   }
-  CHECK_HIP(kafka_launch_skinny_gemm(bptr(x), x.stride(0), bptr(wt), M, N, K, (int)splits, glu ? 1 : 0, yp, ldy, pp,
-                                     cur_stream()));
+  CHECK_HIP(kafka_launch_skinny_gemm(bptr(x), x.stride(0), (int)fmt, wt.data_ptr(),
+                                     scale.has_value() ? scale->data_ptr() : nullptr, M, N, K, (int)splits,
+                                     glu ? 1 : 0, yp, ldy, pp, cur_stream()));
 }
 
 // explicit-configuration variant (microbenchmark sweeps): (mt, kc, splits) as given, no planning
@@ -1197,7 +1198,8 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("v_cache"), py::arg("slots"), py::arg("Hq"), py::arg("Hkv"), py::arg("max_splits"),
         py::arg("stamps") = py::none());
   m.def("skinny_plan", &skinny_plan);
-  m.def("skinny_gemm", &skinny_gemm);
+  m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"), py::arg("splits"),
+        py::arg("glu"), py::arg("scale") = py::none(), py::arg("fmt") = (int64_t)kafka::WF_BF16);
   m.def("wstream_gemm_cfg", &wstream_gemm_cfg);
   m.def("slab_reduce", &slab_reduce);
   m.def("wstream_grouped", &wstream_grouped, py::arg("x"), py::arg("wt"), py::arg("scale"), py::arg("fmt"),

@@ -281,8 +281,10 @@ hipError_t kafka_launch_wstream_grouped(const bf16* X, int64_t ldx, int wfmt, co
 // Split plan for a shape (mirrored by ops.skinny_plan): the fewest power-of-two splits that give >= 192 workgroups
 // while every split keeps >= 4 K stages of 64.
 int kafka_skinny_plan(int M, int N, int K, int max_splits, int* splits);
-hipError_t kafka_launch_skinny_gemm(const bf16* X, int64_t ldx, const bf16* Wt, int M, int N, int K, int splits,
-                                    int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st);
+// wfmt (WF_*) names the layout of Wt and scale as for kafka_launch_wstream_gemm (bf16 tiles: scale == nullptr); the plan,
+// grid and outputs do not depend on it.
+hipError_t kafka_launch_skinny_gemm(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale, int M,
+                                    int N, int K, int splits, int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st);
 
 // ---- moe.hip
 hipError_t kafka_launch_moe_route(const bf16* logits, int64_t ld, int T, int E, int K, int BM, float* topk_w,
