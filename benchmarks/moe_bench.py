@@ -10,7 +10,11 @@ e2m1 tiles with their e8m0 block-scale images (ops.tile_experts_mxfp4) the same 
 routing in one process, the formats interleaved within every timing round: one JSON line per T with us/layer and the
 effective TB/s over the bytes actually streamed (tiles + scales of the experts with >= 1 token) per format.
 
+``--tiles-only`` times prefill-sized steps (T = 1024 .. 8192) on the grouped tile GEMM (ops.grouped_tiles_*, the tiles of
+``--weight-dtype``) beside ops.grouped_gemm + silu_mul on the dequantised row-major experts, two interleaved rounds.
+
   python benchmarks/moe_bench.py            # T = 1, 16, 64, 128, 512, 2048
+  python benchmarks/moe_bench.py --tiles-only --weight-dtype mxfp4
   python benchmarks/moe_bench.py 1,64,256 --weight-dtype fp8
   python benchmarks/moe_bench.py 64,128,256,512 --compare bf16,fp8,mxfp4
 """
@@ -74,12 +78,55 @@ def compare(Ts, fmts, dev, E, K, d, F, router, w13, w2, iters=20, rounds=5):
         print(json.dumps(row), flush=True)
 
 
+def tiles_only(Ts, wd, dev, E, K, d, F, router, w13, w2, rounds=2):
+    """Prefill-sized steps: the layer on the grouped tile GEMM (ops.grouped_tiles_*, the experts' tiles of format ``wd``)
+    beside ops.grouped_gemm + silu_mul on the dequantised row-major experts, interleaved round by round; every round's
+    us per layer is printed, with the achieved TFLOP/s of the medians. Also the largest output difference of the two."""
+    (w13t, w13s), (w2t, w2s) = ops.tile_experts_as(w13, wd, True), ops.tile_experts_as(w2, wd)
+    if w13s is not None:
+        w13, w2 = ops.untile_experts_as(w13t, w13s, True), ops.untile_experts_as(w2t, w2s)
+    for T in Ts:
+        x = torch.randn(T, d, device=dev, dtype=torch.bfloat16)
+
+        def layer_rows():
+            r = ops.moe_route(torch.nn.functional.linear(x, router), K)
+            a = ops.silu_mul(ops.grouped_gemm(x, w13, r, gather=True))
+            out = torch.zeros(T, d, dtype=torch.float32, device=dev)
+            return ops.grouped_gemm(a, w2, r, gather=False, combine_out=out)
+
+        def layer_tiles():
+            r = ops.moe_route(torch.nn.functional.linear(x, router), K)
+            a = ops.grouped_tiles_glu(x, w13t, r, scale=w13s)
+            out = torch.zeros(T, d, dtype=torch.float32, device=dev)
+            return ops.grouped_tiles_combine(a, w2t, r, T, out, scale=w2s)
+
+        o_r, o_t = layer_rows(), layer_tiles()
+        diff = float((o_r - o_t).abs().max() / o_r.abs().max())
+        res = {"rows": [], "tiles": []}
+        for _ in range(rounds):
+            res["rows"].append(timeit(layer_rows, iters=10, rounds=3))
+            res["tiles"].append(timeit(layer_tiles, iters=10, rounds=3))
+        flop = 2 * T * K * 3 * F * d
+        med = {k: statistics.median(v) for k, v in res.items()}
+        print(json.dumps({"weight_dtype": wd, "T": T,
+                          "grouped_gemm_us_per_layer": [round(v, 1) for v in res["rows"]],
+                          "grouped_tiles_us_per_layer": [round(v, 1) for v in res["tiles"]],
+                          "grouped_gemm_TFLOP/s": round(flop / med["rows"] / 1e6, 1),
+                          "grouped_tiles_TFLOP/s": round(flop / med["tiles"] / 1e6, 1),
+                          "max_rel_diff": round(diff, 5)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("Ts", nargs="?", default="1,16,64,128,512,2048", help="comma-separated token counts")
     ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"])
     ap.add_argument("--compare", default="", help="comma-separated expert formats to time interleaved (streaming kernel)")
+    ap.add_argument("--tiles-only", action="store_true",
+                    help="prefill sizes (default T = 1024, 2048, 4096, 8192): the grouped tile GEMM on the expert tiles "
+                         "of --weight-dtype beside grouped_gemm on the dequantised row-major experts")
     args = ap.parse_args()
+    if args.tiles_only and args.Ts == ap.get_default("Ts"):
+        args.Ts = "1024,2048,4096,8192"
     Ts = [int(x) for x in args.Ts.split(",")]
     wd = args.weight_dtype
     dev = torch.device("cuda:0")
@@ -93,6 +140,8 @@ def main():
         if any(T > 512 for T in Ts):
             ap.error("--compare times the streaming kernel: T <= 512")
         return compare(Ts, fmts, dev, E, K, d, F, router, w13, w2)
+    if args.tiles_only:
+        return tiles_only(Ts, wd, dev, E, K, d, F, router, w13, w2)
     # (tiles, scales or None) in the grouped weight-streaming layout; quantised: w13 / w2 become the dequantised experts
     # the LDS-tiled grouped GEMM reads
     (w13t, w13s), (w2t, w2s) = ops.tile_experts_as(w13, wd, True), ops.tile_experts_as(w2, wd)

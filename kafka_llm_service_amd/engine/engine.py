@@ -72,6 +72,10 @@ class EngineConfig:
     # e8m0 exponent per block: 4.25 bits per weight; same semantics).
     # fp8 and mxfp4 need the streaming decode GEMM (auto resolves to stream); env KAFKA_WEIGHT_DTYPE overrides
     weight_dtype: str = "bf16"          # bf16 | fp8 | mxfp4
+    # MoE models: keep the experts in their wave tiles alone (no row-major / dequantised bf16 copy, 90 GB for
+    # Mixtral-8x7B); steps above models/moe.py MOE_STREAM_MAX_T then run the grouped tile GEMM
+    # (csrc/grouped_tile_gemm.hip) on the tiles. Needs the streaming decode GEMM; env KAFKA_EXPERT_TILES_ONLY=1 overrides
+    expert_tiles_only: bool = False
     # the default of SamplingParams.tool_grammar["mode"]: "program" (engine/constrained.py) or "automaton"
     # (engine/tool_automaton.py: the call body's automaton masked on the device); env KAFKA_TOOL_GRAMMAR overrides
     tool_grammar: str = "program"
@@ -154,11 +158,23 @@ class LLMEngine:
         if self.model.stream and self.model.weight_dtype != wdt:
             raise ValueError(f"the model's streamed weights are {self.model.weight_dtype}, the engine asks for {wdt}")
         cfg.weight_dtype = wdt
+        eto = os.environ.get("KAFKA_EXPERT_TILES_ONLY")
+        eto = cfg.expert_tiles_only if eto is None else eto == "1"
+        if eto and (mode != "stream" or not mc.num_experts):
+            raise ValueError("expert_tiles_only needs a MoE model and decode_gemm auto | stream (its experts live in "
+                             "the streaming kernels' tiles)")
+        if self.model.stream and self.model.expert_tiles_only != eto:
+            raise ValueError(f"the model's expert_tiles_only is {self.model.expert_tiles_only}, the engine asks for {eto}")
+        cfg.expert_tiles_only = eto
         if mode == "stream" and not self.model.stream:
-            need = self.model.stream_weight_bytes(wdt)
-            free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else need * 4
+            need = self.model.stream_weight_bytes(wdt, expert_tiles_only=eto)
+            free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else max(need, 1) * 4
             if need <= 0.5 * free:
-                self.model.enable_stream_weights(weight_dtype=wdt)  # before the KV pool is sized from the free memory
+                # before the KV pool is sized from the free memory
+                self.model.enable_stream_weights(weight_dtype=wdt, expert_tiles_only=eto)
+            elif eto:
+                raise ValueError(f"expert_tiles_only: the tiled copies need {need / 1e9:.1f} GB more than the row-major "
+                                 f"experts they replace, {free / 1e9:.1f} GB are free")
             else:  # e.g. Llama-3-70B on one GPU: a second copy of 140 GB would starve the KV pool
                 log.warning("wave-tiled weight copy (%.1f GB) does not fit next to the KV pool (%.1f GB free): "
                             "keeping tiled weights only (prefill untiles per projection)", need / 1e9, free / 1e9)
@@ -230,9 +246,9 @@ class LLMEngine:
         self._coll_mark = (0, 0)  # (collective calls, steps) at the last perf_stats() read
         self._n_added = 0
         self.stop_checker_factory = None  # set by the frontend: (request params) -> incremental stop-string checker
-        log.info("engine ready: %s tp=%d weights %s (%.1f GB) kv pages=%d (%s, %.1f GB) load %.1fs", mc.name, cfg.tp,
-                 self.model.weight_dtype, self.model.weight_bytes() / 1e9, nb, cfg.kv_dtype, nb * page_bytes / 1e9,
-                 self.load_s)
+        log.info("engine ready: %s tp=%d weights %s%s (%.1f GB) kv pages=%d (%s, %.1f GB) load %.1fs", mc.name, cfg.tp,
+                 self.model.weight_dtype, ", expert tiles only" if self.model.expert_tiles_only else "",
+                 self.model.weight_bytes() / 1e9, nb, cfg.kv_dtype, nb * page_bytes / 1e9, self.load_s)
 
     # ------------------------------------------------------------------------------------------------------------
 

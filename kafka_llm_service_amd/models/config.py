@@ -84,6 +84,12 @@ PRESETS: dict[str, ModelConfig] = {
     "mixtral-8x7b": ModelConfig(name="mixtral-8x7b", arch="mixtral", vocab_size=32000, rope_theta=1e6,
                                 max_position_embeddings=32768, num_experts=8, num_experts_per_tok=2,
                                 bos_token_id=1, eos_token_ids=[2]),
+    # 271 GB of bf16 experts (72 GB as MXFP4 tiles): on one GPU only with quantised expert tiles and no row-major copy
+    # (EngineConfig.expert_tiles_only). vocab 32768 is the 8x22B checkpoint's
+    "mixtral-8x22b": ModelConfig(name="mixtral-8x22b", arch="mixtral", hidden_size=6144, intermediate_size=16384,
+                                 num_layers=56, num_heads=48, num_kv_heads=8, head_dim=128, vocab_size=32768,
+                                 rope_theta=1e6, max_position_embeddings=65536, num_experts=8, num_experts_per_tok=2,
+                                 bos_token_id=1, eos_token_ids=[2]),
     # small configs with the same head geometry (head_dim 128, GQA) for tests and smoke runs
     "tiny-llama": ModelConfig(name="tiny-llama", hidden_size=512, intermediate_size=1024, num_layers=2,
                               num_heads=8, num_kv_heads=2, vocab_size=128256, max_position_embeddings=131072,

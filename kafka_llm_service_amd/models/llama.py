@@ -127,6 +127,7 @@ class TransformerLM:
         self.weight_dtype = "bf16"  # of the streamed projections and the lm_head (enable_stream_weights)
         self.stream = False  # decode GEMMs on the weight-streaming kernel (enable_stream_weights)
         self.tiled_only = False  # row-major dense weights dropped (enable_stream_weights(tiled_only=True))
+        self.expert_tiles_only = False  # row-major experts dropped (enable_stream_weights(expert_tiles_only=True))
         self.stream_max_m = ops.STREAM_MAX_M  # rows up to which a step's projections stream
         self._fused_shapes = None  # whether the fused decode layer applies to this model (decided on first use)
 
@@ -147,8 +148,10 @@ class TransformerLM:
             self.moe.serve_idle(lw, self.cfg.hidden_size, self.dtype, self.device)
 
     # ------------------------------------------------------------------------------------------------------------
-    def stream_weight_bytes(self, weight_dtype: str = "bf16") -> int:
-        """Bytes enable_stream_weights would add (the wave-tiled copies; 0 in tiled-only mode). ``"fp8"``: one byte
+    def stream_weight_bytes(self, weight_dtype: str = "bf16", expert_tiles_only: bool = False) -> int:
+        """Bytes enable_stream_weights would add (the wave-tiled copies; 0 in tiled-only mode; with
+        ``expert_tiles_only`` the expert tiles minus the row-major experts they replace, which can be negative and is
+        only valid before the call, while the row-major experts exist). ``"fp8"``: one byte
         per element plus a 4-byte scale per row for the dense projections, the lm_head and the MoE experts (a scale
         per row of every expert). ``"mxfp4"``: half a byte per element plus one exponent byte per 32 (4.25 bits) for the
         dense projections, the lm_head and the MoE experts alike."""
@@ -164,6 +167,8 @@ class TransformerLM:
                 w = getattr(lw, name)
                 if w is not None and ops.stream_moe_supported(w.shape[1], w.shape[2]):
                     n += ops.tiled_weight_bytes(w.shape, expert_dtype)
+                    if expert_tiles_only:
+                        n -= w.numel() * w.element_size()
         if self.lm_head is not None and ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
             n += ops.tiled_weight_bytes(self.lm_head.shape, weight_dtype)
         return n
@@ -174,7 +179,8 @@ class TransformerLM:
         (bf16, fp8 and mxfp4 all have their grouped kernel)."""
         return weight_dtype if ops.weight_format(weight_dtype).experts else "bf16"
 
-    def enable_stream_weights(self, tiled_only: bool = False, weight_dtype: str = "bf16") -> int:
+    def enable_stream_weights(self, tiled_only: bool = False, weight_dtype: str = "bf16",
+                              expert_tiles_only: bool = False) -> int:
         """Keep a wave-tiled copy of every dense projection and of the lm_head (ops.tile_weight) so decode-sized
         steps (T <= ops.STREAM_MAX_M) run the weight-streaming MFMA GEMM (csrc/wstream_gemm.hip) instead of
         hipBLASLt; prefill-sized steps keep the row-major weights. Costs one more copy of those weights (16 GB for
@@ -208,8 +214,25 @@ class TransformerLM:
         quantised where their tiled copy is made, as for fp8 (ops.tile_experts_mxfp4: ``w13_t`` / ``w2_t`` float4_e2m1fn_x2
         [E_local, N/32, K/64, 64, 16], ``w13_s`` / ``w2_s`` the e8m0 images [E_local, N/32, K/64, 32, 2]; every
         expert-parallel rank quantises its own whole experts; row-major ``w13`` / ``w2`` become the dequantised experts),
-        and in tiled-only mode their single row-major copy stays unquantised bf16 as well."""
+        and in tiled-only mode their single row-major copy stays unquantised bf16 as well.
+
+        ``expert_tiles_only``: the experts are tiled (and quantised) exactly as above and then live in their tiles
+        alone: ``w13`` / ``w2`` become None instead of the (dequantised) row-major copy, which only steps above
+        ``moe.MOE_STREAM_MAX_T`` read. Those steps run ``ops.grouped_tiles_glu`` / ``ops.grouped_tiles_combine``
+        (csrc/grouped_tile_gemm.hip) on the same tiles; export and the dense oracle read ``expert_weight``. Mixtral-8x7B
+        then holds 24 GB (mxfp4), 45 GB (fp8) or 90 GB (bf16) of experts instead of that plus 90 GB. Needs every expert
+        matrix to pass ``ops.stream_moe_supported``; not together with ``tiled_only`` (which keeps row-major experts
+        and no tiles). The returned bytes count the freed copies (they can be negative)."""
         expert_dtype = self._expert_dtype(weight_dtype)  # (refuses an unknown weight_dtype)
+        if expert_tiles_only:
+            if tiled_only:
+                raise ValueError("expert_tiles_only drops the row-major experts and keeps their tiles; tiled_only keeps "
+                                 "the row-major experts and makes no tiles: pick one")
+            for lw in self.layers:
+                for w in (lw.w13, lw.w2):
+                    if w is not None and not ops.stream_moe_supported(w.shape[1], w.shape[2]):
+                        raise ValueError(f"expert_tiles_only: experts [N, K] = {tuple(w.shape[1:])} have no tiled "
+                                         "kernels (N % 64 == 0 and K % 256 == 0)")
         added = 0
 
         def tile(w, glu=False):
@@ -243,9 +266,13 @@ class TransformerLM:
                     wt, st = ops.tile_experts_as(w, expert_dtype, glu)
                     setattr(lw, name + "_t", wt)
                     setattr(lw, name + "_s", st)
-                    if st is not None:
+                    if expert_tiles_only:
+                        setattr(lw, name, None)
+                        added -= w.numel() * w.element_size()
+                    elif st is not None:
                         setattr(lw, name, ops.untile_experts_as(wt, st, glu))
                     added += ops.tiled_weight_bytes(w.shape, expert_dtype)
+                    del w
         if ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
             # (an lm_head that aliases the embedding gets a tensor of its own here: the embedding keeps its values)
             self.lm_head_t, self.lm_head_s, keep, nbytes = tile(self.lm_head)
@@ -256,13 +283,14 @@ class TransformerLM:
                 added += nbytes
         self.stream = True
         self.tiled_only = tiled_only
+        self.expert_tiles_only = expert_tiles_only
         self.weight_dtype = weight_dtype
         # tiled-only: any larger step would untile every projection for hipBLASLt, so the streaming kernel takes
         # steps up to its 256-row limit (two row tiles beyond 128) — slower than hipBLASLt there, far cheaper than
         # untiling
         self.stream_max_m = ops.STREAM_KERNEL_MAX_M if tiled_only else ops.STREAM_MAX_M
-        if tiled_only and self.device.type == "cuda":
-            torch.cuda.empty_cache()
+        if (tiled_only or expert_tiles_only) and self.device.type == "cuda":
+            torch.cuda.empty_cache()  # the dropped copies go back to the device before the KV pool is sized
         return added
 
     def _linear(self, x: torch.Tensor, w: torch.Tensor, wt: torch.Tensor | None, max_splits: int = 8,
@@ -293,6 +321,14 @@ class TransformerLM:
             return self._dense(self.lm_head, self.lm_head_t, st=self.lm_head_s)
         return self._dense(getattr(lw, name), getattr(lw, name + "_t"), bool(lw.glu) and name == "gate_up",
                            getattr(lw, name + "_s"))
+
+    def expert_weight(self, lw: LayerWeights, name: str) -> torch.Tensor:
+        """Row-major [E_local, N, K] experts ``"w13"`` / ``"w2"`` of ``lw`` in either mode: the stored tensor, or the
+        untiled (fp8 / mxfp4: dequantised) tiles of an expert-tiles-only model: what export and the dense oracle read."""
+        w = getattr(lw, name)
+        if w is not None:
+            return w
+        return ops.untile_experts_as(getattr(lw, name + "_t"), getattr(lw, name + "_s"), name == "w13")
 
     def forward(self, inp: StepInput, k_caches: list[torch.Tensor], v_caches: list[torch.Tensor],
                 gather: bool = True) -> torch.Tensor:

@@ -16,6 +16,10 @@ Decode-sized steps (T <= MOE_STREAM_MAX_T) of a model with streamed weights inst
 are e4m3 tiles with per-row scales ``w13_s`` / ``w2_s`` (half the streamed bytes), with ``weight_dtype="mxfp4"`` e2m1
 tiles with their e8m0 block-scale images in the same slots (4.25 / 16 of the bytes); either way the row-major ``w13`` /
 ``w2`` hold the dequantised values, so larger steps (``ops.grouped_gemm``) compute with the same quantised experts.
+
+An expert-tiles-only model (``enable_stream_weights(expert_tiles_only=True)``: ``w13`` / ``w2`` are None) has no
+row-major experts: its larger steps run ``ops.grouped_tiles_glu`` / ``ops.grouped_tiles_combine``
+(csrc/grouped_tile_gemm.hip), a compute-oriented grouped MFMA GEMM on the same tiles of any format.
 """
 from __future__ import annotations
 
@@ -72,6 +76,12 @@ class MoEBlock:
             a = ops.grouped_stream_glu(x, lw.w13_t, r, e_lo=self.e0, scale=lw.w13_s)
             out = torch.zeros(T, d, dtype=torch.float32, device=x.device)
             ops.grouped_stream_combine(a, lw.w2_t, r, T, out, e_lo=self.e0, scale=lw.w2_s)
+            return self._finish(out, x.dtype)
+        if lw.w13 is None:
+            # expert-tiles-only model: prefill-sized steps read the same tiles (csrc/grouped_tile_gemm.hip)
+            a = ops.grouped_tiles_glu(x, lw.w13_t, r, e_lo=self.e0, scale=lw.w13_s)
+            out = torch.zeros(T, d, dtype=torch.float32, device=x.device)
+            ops.grouped_tiles_combine(a, lw.w2_t, r, T, out, e_lo=self.e0, scale=lw.w2_s)
             return self._finish(out, x.dtype)
         # gate_up for every (token, expert) entry routed to a local expert, rows gathered from x by the kernel
         h = ops.grouped_gemm(x, lw.w13, r, gather=True, e_lo=self.e0)
@@ -142,6 +152,9 @@ class MoEBlock:
         if self.model.stream and lw.w13_t is not None and rows.shape[0] <= MOE_STREAM_MAX_T:
             a = ops.grouped_stream_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
             ops.grouped_stream_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
+        elif lw.w13 is None:  # expert-tiles-only model
+            a = ops.grouped_tiles_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
+            ops.grouped_tiles_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
         else:
             h = ops.grouped_gemm(rows, lw.w13, rr, gather=True, e_lo=0)
             ops.grouped_gemm(ops.silu_mul(h), lw.w2, rr, gather=False, e_lo=0, combine_out=y)
@@ -186,6 +199,9 @@ class MoEBlock:
         if self.model.stream and lw.w13_t is not None and rows.shape[0] <= MOE_STREAM_MAX_T:
             a = ops.grouped_stream_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
             ops.grouped_stream_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
+        elif lw.w13 is None:  # expert-tiles-only model
+            a = ops.grouped_tiles_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
+            ops.grouped_tiles_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
         else:
             h = ops.grouped_gemm(rows, lw.w13, rr, gather=True, e_lo=0)
             ops.grouped_gemm(ops.silu_mul(h), lw.w2, rr, gather=False, e_lo=0, combine_out=y)

@@ -67,15 +67,17 @@ def dense_logits(model: TransformerLM, tokens: list[int], fp32: bool = False) ->
         if lw.router is not None:
             w, e = route(_lin(x, lw.router), cfg.num_experts_per_tok)
             out = torch.zeros(T, x.shape[1], dtype=torch.float32, device=dev)
+            # (the stored experts, or the untiled / dequantised tiles of an expert-tiles-only model)
+            w13, w2 = model.expert_weight(lw, "w13"), model.expert_weight(lw, "w2")
             for j in range(cfg.num_experts):
                 sel = (e == j)
                 rows = sel.any(-1).nonzero().flatten()
                 if rows.numel() == 0:
                     continue
-                gu = _lin(x[rows], lw.w13[j])
+                gu = _lin(x[rows], w13[j])
                 Fh = gu.shape[-1] // 2
                 a = (F.silu(gu[:, :Fh].float()) * gu[:, Fh:].float()).to(x.dtype)
-                y = _lin(a, lw.w2[j]).float()
+                y = _lin(a, w2[j]).float()
                 out[rows] += y * (w * sel)[rows].sum(-1, keepdim=True)
             delta = out.to(h.dtype)
         else:

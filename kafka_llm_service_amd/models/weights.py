@@ -245,10 +245,12 @@ def save_safetensors(model: TransformerLM, path: str | Path) -> None:
         out[n["o"]] = o
         if cfg.num_experts:
             out[n["router"]] = lw.router
+            # (expert-tiles-only models keep just the expert tiles: untiled / dequantised for export)
+            w13, w2 = model.expert_weight(lw, "w13"), model.expert_weight(lw, "w2")
             for e in range(cfg.num_experts):
-                out[n["expert"].format(e=e, w="w1")] = lw.w13[e, :F]
-                out[n["expert"].format(e=e, w="w3")] = lw.w13[e, F:]
-                out[n["expert"].format(e=e, w="w2")] = lw.w2[e]
+                out[n["expert"].format(e=e, w="w1")] = w13[e, :F]
+                out[n["expert"].format(e=e, w="w3")] = w13[e, F:]
+                out[n["expert"].format(e=e, w="w2")] = w2[e]
         else:
             gu = dense(lw, "gate_up")
             out[n["gate"]], out[n["up"]] = gu[:F], gu[F:]

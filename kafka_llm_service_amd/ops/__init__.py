@@ -1034,6 +1034,47 @@ def grouped_stream_combine(a: torch.Tensor, wt: torch.Tensor, r: "MoERouting", T
     return out
 
 
+# Prefill-sized steps on the SAME expert tiles (csrc/grouped_tile_gemm.hip): 256-row tiles of each expert's segment, both
+# operands through an LDS ring, quantised tiles dequantised per fragment. A model in expert-tiles-only mode
+# (enable_stream_weights(expert_tiles_only=True)) runs these above MOE_STREAM_MAX_T instead of grouped_gemm on a
+# row-major copy. GT_BM is the kernel's row tile.
+GT_BM = 256
+
+
+def grouped_tiles_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: int = 0,
+                      scale: torch.Tensor | None = None) -> torch.Tensor:
+    """``grouped_stream_glu`` for segments of hundreds to thousands of rows per expert: silu(gate) * up for every routed
+    (token, local expert) entry [n_ent, F] on GLU-tiled expert weights of any tile format (``scale`` as there)."""
+    f, scale = _expert_format("grouped_tiles_glu", wt, scale)
+    n_ent = r.perm_tok.numel()
+    F = wt.shape[1] * 16  # (N / 32 tiles of 32 rows, N = 2 F: every tile format)
+    y = torch.empty(n_ent, F, dtype=x.dtype, device=x.device)
+    if _gpu(x):
+        if f.raw:
+            wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
+        ext().grouped_tile_gemm(x, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), True, y, None)
+        return y
+    h = ref_grouped(x, untile_experts_as(wt, scale, glu=True), r, e_lo, gather=True)
+    y.copy_(ref.silu_mul(h))
+    return y
+
+
+def grouped_tiles_combine(a: torch.Tensor, wt: torch.Tensor, r: "MoERouting", T: int, out: torch.Tensor,
+                          e_lo: int = 0, scale: torch.Tensor | None = None) -> torch.Tensor:
+    """``grouped_stream_combine`` for prefill-sized steps: out[token] += w * (a[entry] @ W_e^T) over the local experts'
+    entries (out f32 [T, N], zeroed by the caller)."""
+    f, scale = _expert_format("grouped_tiles_combine", wt, scale)
+    if out.shape[0] != T:
+        raise ValueError("grouped_tiles_combine: out must have one row per token")
+    if _gpu(a):
+        if f.raw:
+            wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
+        ext().grouped_tile_gemm(a, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), False, None, out)
+        return out
+    ref.grouped_gemm(a, untile_experts_as(wt, scale), r.perm_tok, r.perm_w, r.expert_off, e_lo, False, None, out)
+    return out
+
+
 def ref_grouped(x, w, r, e_lo, gather):
     y = torch.zeros(r.perm_tok.numel(), w.shape[1], dtype=x.dtype)
     ref.grouped_gemm(x, w, r.perm_tok, r.perm_w, r.expert_off, e_lo, gather, y, None)

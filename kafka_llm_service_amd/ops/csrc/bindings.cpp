@@ -901,6 +901,51 @@ static void wstream_grouped(at::Tensor x, at::Tensor wt, c10::optional<at::Tenso
                                          cur_stream()));
 }
 
+// Expert MLP halves of prefill-sized steps on the same expert tiles (csrc/grouped_tile_gemm.hip): wt, scale and fmt as
+// for wstream_grouped. glu: x [T, K] token rows gathered through perm_tok, SwiGLU fused, into y [n_ent, N/2]; else x
+// [n_ent, K] expert-sorted rows and the weighted combine into out f32 [T, N].
+static void grouped_tile_gemm(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> scale, int64_t fmt,
+                              at::Tensor perm_tok, at::Tensor perm_w, at::Tensor expert_off, int64_t e_lo, bool glu,
+                              c10::optional<at::Tensor> y, c10::optional<at::Tensor> out) {
+  check_stream_x("grouped_tile_gemm", x);
+  const int vk = check_wfmt("grouped_tile_gemm", fmt, wt, scale, 1);
+  CHECK_CUDA(perm_tok); CHECK_CUDA(perm_w); CHECK_CUDA(expert_off);
+  CHECK_DT(perm_tok, at::kInt); CHECK_DT(perm_w, at::kFloat); CHECK_DT(expert_off, at::kInt);
+  const int E_local = wt.size(0), N = wt.size(1) * 32, K = wt.size(2) * vk;
+  TORCH_CHECK(x.size(1) == K, "grouped_tile_gemm: K mismatch (x has K = ", x.size(1), ", the tiles ", K, ")");
+  TORCH_CHECK(K % 256 == 0 && N % 64 == 0, "grouped_tile_gemm: needs K % 256 == 0 and N % 64 == 0");
+  const int64_t n_ent = perm_tok.numel();
+  TORCH_CHECK(perm_w.numel() == n_ent && perm_tok.is_contiguous() && perm_w.is_contiguous(),
+              "grouped_tile_gemm: perm");
+  TORCH_CHECK(expert_off.is_contiguous() && e_lo >= 0 && E_local <= 16 && expert_off.numel() >= e_lo + E_local + 1,
+              "grouped_tile_gemm: expert_off too short for the local experts (at most 16)");
+  bf16* yp = nullptr;
+  int64_t ldy = 0;
+  float* op = nullptr;
+  int64_t ldo = 0;
+  if (glu) {
+    TORCH_CHECK(y.has_value() && !out.has_value(), "grouped_tile_gemm: the GLU half writes y");
+    CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
+    TORCH_CHECK(y->dim() == 2 && y->size(0) >= n_ent && y->size(1) == N / 2 && y->stride(0) % 8 == 0,
+                "grouped_tile_gemm: y must be [n_ent, N/2] with 16-B rows");
+    yp = bptr(y.value());
+    ldy = y->stride(0);
+  } else {
+    TORCH_CHECK(out.has_value() && !y.has_value(), "grouped_tile_gemm: the combine half adds into out");
+    CHECK_CUDA(out.value()); CHECK_DT(out.value(), at::kFloat); CHECK_LASTDIM(out.value());
+    // (perm_tok < T = out's rows is the router's contract, as for wstream_grouped and grouped_gemm)
+    TORCH_CHECK(out->dim() == 2 && out->size(1) == N && x.size(0) >= n_ent,
+                "grouped_tile_gemm: out must be [T, N] and x hold one row per routed entry");
+    op = out->data_ptr<float>();
+    ldo = out->stride(0);
+  }
+  CHECK_HIP(kafka_launch_grouped_tile_gemm(bptr(x), x.stride(0), (int)fmt, wt.data_ptr(),
+                                           scale.has_value() ? scale->data_ptr() : nullptr, E_local, N, K,
+                                           perm_tok.data_ptr<int>(), perm_w.data_ptr<float>(),
+                                           expert_off.data_ptr<int>(), (int)e_lo, (int)n_ent, glu ? 1 : 0, yp, ldy, op,
+                                           ldo, cur_stream()));
+}
+
 // y [M, N] bf16 = sum over the slabs p [S, M, N]
 static void slab_reduce(at::Tensor p, at::Tensor y) {
   CHECK_CUDA(p); CHECK_DT(p, at::kFloat); CHECK_DT(y, at::kBFloat16); CHECK_LASTDIM(y);
@@ -1205,6 +1250,9 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("wstream_grouped", &wstream_grouped, py::arg("x"), py::arg("wt"), py::arg("scale"), py::arg("fmt"),
         py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("max_rows"),
         py::arg("gather"), py::arg("y"), py::arg("out"), py::arg("pin") = true);
+  m.def("grouped_tile_gemm", &grouped_tile_gemm, py::arg("x"), py::arg("wt"), py::arg("scale"), py::arg("fmt"),
+        py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("glu"), py::arg("y"),
+        py::arg("out"));
   m.def("moe_route", &moe_route);
   m.def("cu_mask_stream", &cu_mask_stream);
   m.def("stream_cu_mask", &stream_cu_mask);

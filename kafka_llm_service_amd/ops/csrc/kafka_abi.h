@@ -286,6 +286,18 @@ int kafka_skinny_plan(int M, int N, int K, int max_splits, int* splits);
 hipError_t kafka_launch_skinny_gemm(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale, int M,
                                     int N, int K, int splits, int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st);
 
+// ---- grouped_tile_gemm.hip
+// Expert MLP halves of prefill-sized steps on the expert tiles (see grouped_tile_gemm_kernel): 256-row tiles of each
+// local expert's routing segment, found on the device from expert_off (e_local <= 16). n_ent: routed entries (the
+// length of perm_tok / perm_w). glu: gate_up from X[perm_tok[entry]] with fused SwiGLU into Y [n_ent, N/2]; else down
+// from X[entry] with the weighted combine into out f32 [T, N] (zeroed by the caller). wfmt, Wt and scale as for
+// kafka_launch_wstream_grouped. hipErrorInvalidValue for N % 64 != 0 or K % 256 != 0, a quantised format without scales
+// and bf16 tiles with scales.
+hipError_t kafka_launch_grouped_tile_gemm(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale,
+                                          int e_local, int N, int K, const int* perm_tok, const float* perm_w,
+                                          const int* expert_off, int e_lo, int n_ent, int glu, bf16* Y, int64_t ldy,
+                                          float* out, int64_t ldo, hipStream_t st);
+
 // ---- moe.hip
 hipError_t kafka_launch_moe_route(const bf16* logits, int64_t ld, int T, int E, int K, int BM, float* topk_w,
                                   int* topk_e, int* perm_tok, float* perm_w, int* expert_off, int* tile_off,

@@ -26,6 +26,8 @@ def main() -> None:
         ap.add_argument("--" + flag.replace("_", "-"), default=None, help=f"overrides {env}")
     ap.add_argument("--ignore-eos", action="store_true", help="KAFKA_IGNORE_EOS=1 (benchmarks)")
     ap.add_argument("--mcp", action="store_true", help="KAFKA_MCP=1")
+    ap.add_argument("--expert-tiles-only", action="store_true",
+                    help="KAFKA_EXPERT_TILES_ONLY=1: MoE experts live in their (quantised) wave tiles alone")
     a = ap.parse_args()
     for flag, env in FLAGS.items():
         v = getattr(a, flag)
@@ -35,6 +37,8 @@ def main() -> None:
         os.environ["KAFKA_IGNORE_EOS"] = "1"
     if a.mcp:
         os.environ["KAFKA_MCP"] = "1"
+    if a.expert_tiles_only:  # (read by the engine itself, like KAFKA_WEIGHT_DTYPE)
+        os.environ["KAFKA_EXPERT_TILES_ONLY"] = "1"
     if a.log_json:
         os.environ["KAFKA_LOG_JSON"] = "1"
     import uvicorn
