@@ -74,7 +74,7 @@ def main():
     scale = D ** -0.5
     out = torch.empty(B, Hq, D, device=dev, dtype=torch.bfloat16)
     kv_bytes_tok = Hkv * D * 2 * 2 if args.kv_dtype == "bf16" else Hkv * (2 * D + 2)
-    variants = (0, 3) if args.kv_dtype == "bf16" else (0,)  # tile variant 3 reads bf16 pages only
+    variants = (0, 3)
 
     # cascade prefix pass, several chunk sizes
     for chunk in [int(x) for x in args.chunks.split(",")]:

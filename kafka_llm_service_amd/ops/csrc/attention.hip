@@ -1281,9 +1281,8 @@ extern "C" hipError_t kafka_launch_attn_prefill(const void* items, int n_items, 
                                                int S_total, float scale, int variant, int part_bf16, float* alt_part,
                                                float* alt_lse, int alt_S, int alt_tok_off, hipStream_t st) {
   if (n_items == 0) return hipSuccess;
-  if (variant == 3) {  // LDS-DMA ring, 8 waves, 256 rows (attn_tile.hip); bf16 pages only
-    if (fp8) return hipErrorInvalidValue;
-    return kafka_launch_attn_tile(items, n_items, q, q_stride, k_cache, v_cache, Hkv, G, D, block_tables, bt_stride,
+  if (variant == 3) {  // LDS-DMA ring, 8 waves, 256 rows (attn_tile.hip)
+    return kafka_launch_attn_tile(items, n_items, q, q_stride, k_cache, v_cache, fp8, Hkv, G, D, block_tables, bt_stride,
                                   q_limit, out, out_stride, out_part, lse_part, S_total, scale, part_bf16, alt_part,
                                   alt_lse, alt_S, alt_tok_off, st);
   }

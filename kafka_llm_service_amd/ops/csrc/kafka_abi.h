@@ -167,9 +167,9 @@ hipError_t kafka_launch_attn_merge(const float* part, const float* lse, int rows
                                    int64_t out_stride, float* lse_out, const bf16* pre, int npre, hipStream_t st);
 
 // ---- attn_tile.hip (called by kafka_launch_attn_prefill)
-// Host launcher (bf16 KV only; the fp8 cache keeps tile variant 0). Items: int32 [n, ITEM_INTS] AttnWorkItem records.
+// Host launcher (bf16 pages, or fp8 != 0: e4m3 pages). Items: int32 [n, ITEM_INTS] AttnWorkItem records.
 hipError_t kafka_launch_attn_tile(const void* items, int n_items, const bf16* q, int64_t q_stride,
-                                  const void* k_cache, const void* v_cache, int Hkv, int G, int D,
+                                  const void* k_cache, const void* v_cache, int fp8, int Hkv, int G, int D,
                                   const int* block_tables, int bt_stride, const int* q_limit, bf16* out,
                                   int64_t out_stride, float* out_part, float* lse_part, int S_total, float scale,
                                   int part_bf16, float* alt_part, float* alt_lse, int alt_S, int alt_tok_off,
