@@ -1,0 +1,93 @@
+"""Dense tile GEMM (csrc/tile_gemm.hip, ops.linear_tiles) on the Llama-3-8B / 70B projections at prefill row counts,
+in every tile format, against yardsticks from outside the code under test:
+  (a) blas_copy:   F.linear on the stored (dequantised) bf16 row-major copy (+ silu_mul for gate_up): a two-copy model;
+  (b) untile_blas: ops.untile_weight_as + F.linear (+ silu_mul): what a tiled-only model does today on such a step;
+  (c) grouped:     gate_up only, ops.grouped_tiles_glu with one expert and an identity routing (the 2 x 2-block kernel).
+Interleaved rounds: every round times all paths of a cell back to back, so a comparison holds only where it has the
+same sign in every round by more than the cell moves between rounds. Each timed call of a path reads another copy of
+the weight (>= 600 MB rotated, so the MALL does not serve repeats). One JSON line per (round, cell); TFLOP/s over
+2 M N K."""
+import argparse
+import json
+
+import torch
+import torch.nn.functional as F
+
+from kafka_llm_service_amd import ops
+
+# (name, N, K, glu) at TP = 1
+MODELS = {"8b": [("qkv", 6144, 4096, False), ("o", 4096, 4096, False), ("gate_up", 28672, 4096, True),
+                 ("down", 4096, 14336, False)],
+          "70b": [("qkv", 10240, 8192, False), ("o", 8192, 8192, False), ("gate_up", 57344, 8192, True),
+                  ("down", 8192, 28672, False)]}
+
+
+def timeit(fn, iters):
+    for i in range(2):
+        fn(i)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(iters):
+        fn(i)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters
+
+
+def identity_routing(M, dev):
+    """One expert that owns every row, each row routed to itself with weight 1 (the router's stable order)."""
+    return ops.moe_route(torch.zeros(M, 1, dtype=torch.bfloat16, device=dev), 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", default="8b,70b")
+    ap.add_argument("--formats", default="bf16,fp8,mxfp4")
+    ap.add_argument("--rows", default="512,1024,2048,4096,8192")
+    ap.add_argument("--gemms", default="qkv,o,gate_up,down")
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--iters", type=int, default=10)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tile_gemm_bench needs a GPU")
+    dev = "cuda"
+    rows = [int(m) for m in args.rows.split(",")]
+    for model in args.models.split(","):
+        for name, N, K, glu in MODELS[model]:
+            if name not in args.gemms.split(","):
+                continue
+            for fmt in args.formats.split(","):
+                copies = max(2, (600 << 20) // ops.tiled_weight_bytes((N, K), fmt) + 1)
+                qs, deqs = [], []
+                for _ in range(copies):
+                    w = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
+                    qs.append(ops.tile_weight_as(w, fmt, glu))
+                    deqs.append(ops.untile_weight_as(*qs[-1], glu))
+                    del w
+                act = ops.silu_mul if glu else (lambda y: y)
+                for M in rows:
+                    x = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+                    route = identity_routing(M, dev) if glu else None
+                    S = ops.tile_gemm_plan(M, N, K, 1 if glu else 8)
+                    paths = {"tiles": lambda i: ops.linear_tiles(x, qs[i % copies][0], glu=glu, scale=qs[i % copies][1]),
+                             "blas_copy": lambda i: act(F.linear(x, deqs[i % copies])),
+                             "untile_blas": lambda i: act(F.linear(x, ops.untile_weight_as(*qs[i % copies], glu)))}
+                    if glu:
+                        paths["grouped"] = lambda i: ops.grouped_tiles_glu(
+                            x, qs[i % copies][0][None], route, scale=None if qs[i % copies][1] is None
+                            else qs[i % copies][1][None])
+                    for rnd in range(args.rounds):
+                        us = {k: timeit(fn, args.iters) for k, fn in paths.items()}
+                        line = {"model": model, "gemm": name, "weight_dtype": fmt, "M": M, "N": N, "K": K, "splits": S,
+                                "round": rnd}
+                        for k, t in us.items():
+                            line[k + "_us"] = round(t, 1)
+                            line[k + "_TFLOP/s"] = round(2.0 * M * N * K / t / 1e6, 1)
+                        print(json.dumps(line), flush=True)
+                del qs, deqs
+                torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -76,6 +76,11 @@ class EngineConfig:
     # Mixtral-8x7B); steps above models/moe.py MOE_STREAM_MAX_T then run the grouped tile GEMM
     # (csrc/grouped_tile_gemm.hip) on the tiles. Needs the streaming decode GEMM; env KAFKA_EXPERT_TILES_ONLY=1 overrides
     expert_tiles_only: bool = False
+    # dense models in their wave tiles alone at every step size (tiled_only's memory layout, any weight_dtype): steps
+    # above the streaming kernel's rows run the dense tile GEMM (csrc/tile_gemm.hip) on the tiles instead of hipBLASLt
+    # on a row-major (dequantised) copy or on a transient untiled one. Needs the streaming decode GEMM; covers the
+    # attention projections and the lm_head of a MoE model; not with expert_tiles_only; env KAFKA_TILE_PREFILL=1 overrides
+    tile_prefill: bool = False
     # the default of SamplingParams.tool_grammar["mode"]: "program" (engine/constrained.py) or "automaton"
     # (engine/tool_automaton.py: the call body's automaton masked on the device); env KAFKA_TOOL_GRAMMAR overrides
     tool_grammar: str = "program"
@@ -152,9 +157,12 @@ class LLMEngine:
         if wdt != "bf16" and mode == "blas":
             raise ValueError(f"weight_dtype={wdt!r} needs the weight-streaming decode GEMM (decode_gemm auto | stream | "
                              "stream_only), not 'blas'")
+        tpf = os.environ.get("KAFKA_TILE_PREFILL")
+        tpf = cfg.tile_prefill if tpf is None else tpf == "1"
         if mode == "auto":
-            # quantised weights live in the streaming kernel's tiles on any device (the CPU runs the reference path)
-            mode = "stream" if self.device.type == "cuda" or wdt != "bf16" else "blas"
+            # quantised weights (and a tile-prefill model) live in the streaming kernel's tiles on any device (the CPU
+            # runs the reference path)
+            mode = "stream" if self.device.type == "cuda" or wdt != "bf16" or tpf else "blas"
         if self.model.stream and self.model.weight_dtype != wdt:
             raise ValueError(f"the model's streamed weights are {self.model.weight_dtype}, the engine asks for {wdt}")
         cfg.weight_dtype = wdt
@@ -166,7 +174,17 @@ class LLMEngine:
         if self.model.stream and self.model.expert_tiles_only != eto:
             raise ValueError(f"the model's expert_tiles_only is {self.model.expert_tiles_only}, the engine asks for {eto}")
         cfg.expert_tiles_only = eto
-        if mode == "stream" and not self.model.stream:
+        if tpf and (mode not in ("stream", "stream_only") or eto):
+            raise ValueError("tile_prefill needs decode_gemm auto | stream | stream_only (the model lives in the "
+                             "streaming kernels' tiles) and does not combine with expert_tiles_only")
+        if self.model.stream and self.model.tile_prefill != tpf:
+            raise ValueError(f"the model's tile_prefill is {self.model.tile_prefill}, the engine asks for {tpf}")
+        cfg.tile_prefill = tpf
+        if tpf and not self.model.stream:
+            # the dense projections need no second copy in this mode: nothing to fit next to the KV pool, which is sized
+            # below, after the row-major tensors are freed
+            self.model.enable_stream_weights(tiled_only=mode == "stream_only", weight_dtype=wdt, tile_prefill=True)
+        elif mode == "stream" and not self.model.stream:
             need = self.model.stream_weight_bytes(wdt, expert_tiles_only=eto)
             free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else max(need, 1) * 4
             if need <= 0.5 * free:
@@ -247,7 +265,8 @@ class LLMEngine:
         self._n_added = 0
         self.stop_checker_factory = None  # set by the frontend: (request params) -> incremental stop-string checker
         log.info("engine ready: %s tp=%d weights %s%s (%.1f GB) kv pages=%d (%s, %.1f GB) load %.1fs", mc.name, cfg.tp,
-                 self.model.weight_dtype, ", expert tiles only" if self.model.expert_tiles_only else "",
+                 self.model.weight_dtype, ", expert tiles only" if self.model.expert_tiles_only else
+                 (", tile prefill" if self.model.tile_prefill else ""),
                  self.model.weight_bytes() / 1e9, nb, cfg.kv_dtype, nb * page_bytes / 1e9, self.load_s)
 
     # ------------------------------------------------------------------------------------------------------------
@@ -266,7 +285,8 @@ class LLMEngine:
         # 128 rather than the kernel's 256: with two row tiles the streaming GEMM is slower per row, and splitting a
         # long new turn costs less (Llama-3-70B TP = 1: 1,516 vs 1,422 tok/s, TTFT 140 vs 119 ms,
         # profiles/r02/bench_70b_tp1_rowfit256_ab.jsonl)
-        return ops.STREAM_MAX_M if self.model.tiled_only else 0
+        # tile-prefill models run larger steps on the dense tile GEMM: nothing is untiled, so there is nothing to avoid
+        return ops.STREAM_MAX_M if self.model.tiled_only and not self.model.tile_prefill else 0
 
     def _json_table(self):
         """The JSON-mode token table of this model: its tokenizer's bytes per id and the engine's EOS ids."""

@@ -178,6 +178,7 @@ class ModelRunner:
         self.variant = int(os.environ.get("KAFKA_TILE_VARIANT", "3"))
         # mixed steps of 129..256 rows padded away from hipBLASLt's slow sizes (dense TP = 1 GPU models)
         self.pad_rows = (self.device.type == "cuda" and model.tp == 1 and not getattr(model, "tiled_only", False)
+                         and not getattr(model, "tile_prefill", False)  # (no hipBLASLt behind those rows)
                          and os.environ.get("KAFKA_PAD_ROWS", "1") == "1")
         self.tile = ops.tile_rows(self.variant) // self.G  # tokens per attention work item
         # the v3 cascade hands its prefix partials to the decode kernel as bf16 (normalised O, fp32 lse): ~33 MB

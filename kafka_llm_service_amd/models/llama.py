@@ -8,7 +8,8 @@ Per layer (SURVEY.md §3.2 "Target equivalent"):
 Decode-sized steps (T <= 128) run every projection on the weight-streaming MFMA kernel (``ops/csrc/wstream_gemm.hip``,
 wave-tiled weight copies, SwiGLU fused into gate_up; the grouped variant for Mixtral's experts); 129..256-row mixed
 steps run qkv / o / down on the skinny MFMA GEMM (``ops/csrc/skinny_gemm.hip``, SKINNY below; bf16, fp8 and mxfp4 tiles
-alike); other prefill-sized steps use hipBLASLt through ``torch.nn.functional.linear`` (bf16, fp32 accumulate). Norm /
+alike); other prefill-sized steps use hipBLASLt through ``torch.nn.functional.linear`` (bf16, fp32 accumulate), or, in
+the opt-in tile-prefill mode, the dense tile GEMM on the same tiles (``ops/csrc/tile_gemm.hip``). Norm /
 RoPE / attention / sampling run in the hand-written kernels of ``ops/csrc``.
 
 Weights are stored HF-style ``[out, in]`` so safetensors checkpoints load without transposes; random init (seeded,
@@ -128,6 +129,7 @@ class TransformerLM:
         self.stream = False  # decode GEMMs on the weight-streaming kernel (enable_stream_weights)
         self.tiled_only = False  # row-major dense weights dropped (enable_stream_weights(tiled_only=True))
         self.expert_tiles_only = False  # row-major experts dropped (enable_stream_weights(expert_tiles_only=True))
+        self.tile_prefill = False  # row-major dense weights dropped, prefill on ops.linear_tiles (tile_prefill=True)
         self.stream_max_m = ops.STREAM_MAX_M  # rows up to which a step's projections stream
         self._fused_shapes = None  # whether the fused decode layer applies to this model (decided on first use)
 
@@ -180,7 +182,7 @@ class TransformerLM:
         return weight_dtype if ops.weight_format(weight_dtype).experts else "bf16"
 
     def enable_stream_weights(self, tiled_only: bool = False, weight_dtype: str = "bf16",
-                              expert_tiles_only: bool = False) -> int:
+                              expert_tiles_only: bool = False, tile_prefill: bool = False) -> int:
         """Keep a wave-tiled copy of every dense projection and of the lm_head (ops.tile_weight) so decode-sized
         steps (T <= ops.STREAM_MAX_M) run the weight-streaming MFMA GEMM (csrc/wstream_gemm.hip) instead of
         hipBLASLt; prefill-sized steps keep the row-major weights. Costs one more copy of those weights (16 GB for
@@ -222,7 +224,26 @@ class TransformerLM:
         (csrc/grouped_tile_gemm.hip) on the same tiles; export and the dense oracle read ``expert_weight``. Mixtral-8x7B
         then holds 24 GB (mxfp4), 45 GB (fp8) or 90 GB (bf16) of experts instead of that plus 90 GB. Needs every expert
         matrix to pass ``ops.stream_moe_supported``; not together with ``tiled_only`` (which keeps row-major experts
-        and no tiles). The returned bytes count the freed copies (they can be negative)."""
+        and no tiles). The returned bytes count the freed copies (they can be negative).
+
+        ``tile_prefill``: the dense projections and the lm_head are tiled (and quantised) as above and then live in
+        their tiles alone at every step size, in any format: the memory layout is ``tiled_only``'s, but steps above
+        ``stream_max_m`` rows run the dense tile GEMM (``ops.linear_tiles``, csrc/tile_gemm.hip; gate_up with its fused
+        SwiGLU) on the same tiles instead of untiling for hipBLASLt, so nothing is untiled on the hot path and the
+        streaming kernel keeps its default row limit. Export, the dense oracle and ``dense_weight`` untile as in
+        tiled-only mode. Every streamed projection must pass ``ops.tile_gemm_supported``. MoE models: the flag covers
+        the attention projections and the lm_head (the experts follow ``tiled_only`` as before); not together with
+        ``expert_tiles_only``."""
+        if tile_prefill:
+            if expert_tiles_only:
+                raise ValueError("tile_prefill together with expert_tiles_only is not supported")
+            heads = [w for lw in self.layers for w in (getattr(lw, n) for n in LayerWeights.STREAMED)] + [self.lm_head]
+            for w in heads:
+                if w is not None and ops.stream_plan(1, w.shape[0], w.shape[1]) is not None and \
+                        not ops.tile_gemm_supported(w.shape[0], w.shape[1]):
+                    raise ValueError(f"tile_prefill: the projection [N, K] = {tuple(w.shape)} has no dense tile GEMM "
+                                     "(N % 64 == 0 and K % 256 == 0)")
+        drop = tiled_only or tile_prefill  # the dense projections and the lm_head keep no row-major tensor
         expert_dtype = self._expert_dtype(weight_dtype)  # (refuses an unknown weight_dtype)
         if expert_tiles_only:
             if tiled_only:
@@ -238,7 +259,7 @@ class TransformerLM:
         def tile(w, glu=False):
             """(tiles, scales or None, row-major tensor to keep, bytes of the tiled copy)"""
             wt, st = ops.tile_weight_as(w, weight_dtype, glu)
-            keep = w if st is None else (None if tiled_only else ops.untile_weight_as(wt, st, glu))
+            keep = w if st is None else (None if drop else ops.untile_weight_as(wt, st, glu))
             return wt, st, keep, ops.tiled_weight_bytes(w.shape, weight_dtype)
 
         for lw in self.layers:
@@ -252,7 +273,7 @@ class TransformerLM:
                     if name == "gate_up":
                         lw.glu = glu
                     del w
-                    if tiled_only:
+                    if drop:
                         setattr(lw, name, None)
                     else:
                         setattr(lw, name, keep)
@@ -276,7 +297,7 @@ class TransformerLM:
         if ops.stream_plan(1, self.lm_head.shape[0], self.lm_head.shape[1]) is not None:
             # (an lm_head that aliases the embedding gets a tensor of its own here: the embedding keeps its values)
             self.lm_head_t, self.lm_head_s, keep, nbytes = tile(self.lm_head)
-            if tiled_only:
+            if drop:
                 self.lm_head = None
             else:
                 self.lm_head = keep
@@ -284,12 +305,13 @@ class TransformerLM:
         self.stream = True
         self.tiled_only = tiled_only
         self.expert_tiles_only = expert_tiles_only
+        self.tile_prefill = tile_prefill
         self.weight_dtype = weight_dtype
         # tiled-only: any larger step would untile every projection for hipBLASLt, so the streaming kernel takes
         # steps up to its 256-row limit (two row tiles beyond 128) — slower than hipBLASLt there, far cheaper than
         # untiling
         self.stream_max_m = ops.STREAM_KERNEL_MAX_M if tiled_only else ops.STREAM_MAX_M
-        if (tiled_only or expert_tiles_only) and self.device.type == "cuda":
+        if (drop or expert_tiles_only) and self.device.type == "cuda":
             torch.cuda.empty_cache()  # the dropped copies go back to the device before the KV pool is sized
         return added
 
@@ -304,6 +326,8 @@ class TransformerLM:
                 return ops.linear_stream(x, wt, max_splits, scale=st)
             if kind in SKINNY and ops.skinny_plan(M, wt.shape[0] * 32, x.shape[1], max_splits):
                 return ops.linear_skinny(x, wt, max_splits, scale=st)
+            if self.tile_prefill and M > 0:
+                return ops.linear_tiles(x, wt, max_splits, scale=st)
         return F.linear(x, self._dense(w, wt, st=st))
 
     @staticmethod
@@ -391,6 +415,11 @@ class TransformerLM:
                 a = ops.linear_skinny(x, lw.gate_up_t, glu=True, scale=lw.gate_up_s)
                 if ops.is_slab(a):
                     a = ops.silu_mul(a)
+            elif self.tile_prefill and lw.gate_up_t is not None and T > 0:
+                # the dense tile GEMM: SwiGLU in its epilogue on GLU-tiled weights, else gate | up through silu_mul
+                a = ops.linear_tiles(x, lw.gate_up_t, glu=bool(lw.glu), scale=lw.gate_up_s)
+                if not lw.glu:
+                    a = ops.silu_mul(a)
             else:
                 a = ops.silu_mul(F.linear(x, self._dense(lw.gate_up, lw.gate_up_t, bool(lw.glu), lw.gate_up_s)))
             if tp and self._can_overlap(T, lw.down_t) and i + 1 < len(self.layers):
@@ -477,6 +506,8 @@ class TransformerLM:
         long enough to pipeline its GEMM against it."""
         if PIPE_CHUNKS < 2 or T < 2 * PIPE_ROWS or (self.stream and T <= self.stream_max_m):
             return False
+        if w is None and self.tile_prefill:
+            return False  # no row-major weight for the pipelined GEMM: the seam's GEMM runs on the tiles
         car = pstate.custom_ar()
         n = (w.shape[0] if w is not None else wt.shape[0] * 32)
         return car is None or T * n * 2 > car.max_bytes

@@ -712,6 +712,68 @@ def linear_skinny(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: b
     return p
 
 
+TG_BM = TG_BN = 256  # row x column tile of one workgroup of the dense tile GEMM (csrc/tile_gemm.hip)
+
+
+def tile_gemm_supported(N: int, K: int) -> bool:
+    """Whether the dense tile GEMM (``linear_tiles``) covers a [N, K] weight at every row count."""
+    return N > 0 and K > 0 and N % 64 == 0 and K % 256 == 0
+
+
+def tile_gemm_plan(M: int, N: int, K: int, max_splits: int = 8) -> int:
+    """Splits of the dense tile GEMM (csrc/tile_gemm.hip kafka_tile_gemm_plan, mirrored for CPU runs); 0 = unsupported.
+    S doubles (<= 8, K / S a multiple of 256) while the doubled grid still fits one workgroup per CU; the weight format
+    plays no part and a GLU call never splits (``linear_tiles`` plans it with max_splits = 1)."""
+    if M < 1 or not tile_gemm_supported(N, K):
+        return 0
+    wgs, s = -(-M // TG_BM) * -(-N // TG_BN), 1
+    while s * 2 <= max_splits and s * 2 <= 8 and K % (256 * s * 2) == 0 and wgs * s * 2 <= 256:
+        s *= 2
+    return s
+
+
+def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bool = False,
+                 scale: torch.Tensor | None = None) -> torch.Tensor:
+    """y = x @ W^T for any number of rows from the wave-tiled weight (prefill-sized steps of a model that lives in its
+    tiles alone): bf16 [M, N] for one split, or with ``glu`` (GLU-tiled gate_up, never split) the activated
+    silu(gate) * up [M, N/2]; else the fp32 split-K slabs [S, M, N], split s the K range [s K / S, (s + 1) K / S).
+    Tiles of every format: fp8 ones need their row scales ``scale``, MXFP4 ones their e8m0 block-scale image; the kernel
+    dequantises next to its MFMAs, with the plan, outputs and bits of the same call on the bf16 tiles of the
+    dequantised weight. N % 64 == 0 and K % 256 == 0 (``tile_gemm_supported``)."""
+    M, K = x.shape
+    f = WEIGHT_FORMATS.get(wt.dtype)
+    if f is None:
+        raise ValueError(f"linear_tiles: no weight tile format has dtype {wt.dtype}")
+    if f.scale_dtype is None:
+        if scale is not None:
+            raise ValueError(f"linear_tiles: {f.name} weight tiles take no scale")
+    else:
+        _check_scale("linear_tiles", f, wt, scale)
+    N = wt.shape[0] * 32
+    if wt.shape[1] * f.vk != K:
+        raise ValueError(f"linear_tiles: x has K={K}, the {f.name} tiles K={wt.shape[1] * f.vk}")
+    S = tile_gemm_plan(M, N, K, 1 if glu else max_splits)
+    if S == 0:
+        raise ValueError(f"linear_tiles: unsupported shape M={M} N={N} K={K} (N % 64 == 0, K % 256 == 0)")
+    if _gpu(x):
+        y = p = None
+        if S == 1:
+            y = torch.empty(M, N // 2 if glu else N, dtype=x.dtype, device=x.device)
+        else:
+            p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
+        if f.raw:
+            wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
+        ext().tile_gemm(x, wt, y, p, int(S), bool(glu), scale, f.abi)
+        return y if S == 1 else p
+    w = f.untile(wt, scale, glu).float()
+    xf = x.float()
+    if S == 1:
+        y = xf @ w.t()
+        return (ref.silu_mul(y) if glu else y).to(x.dtype)
+    ks = K // S
+    return torch.stack([xf[:, s * ks:(s + 1) * ks] @ w[:, s * ks:(s + 1) * ks].t() for s in range(S)])
+
+
 def linear_stream(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, nt: bool = True,
                   glu: bool = False, scale: torch.Tensor | None = None) -> torch.Tensor:
     """y = x @ W^T for decode-sized M (<= 128) from the wave-tiled weight ``wt``: the weight-streaming MFMA kernel.

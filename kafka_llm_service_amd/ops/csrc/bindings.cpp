@@ -833,6 +833,47 @@ static void skinny_gemm(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> y
                                      glu ? 1 : 0, yp, ldy, pp, cur_stream()));
 }
 
+// Dense tile GEMM (csrc/tile_gemm.hip) for any M >= 1 on the wave-tiled weights: y bf16 for one split ([M, N/2]
+// activated with glu), else fp32 slabs p [splits, M, N]. 0 = unsupported shape
+static int64_t tile_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t max_splits) {
+  int s = 0;
+  TORCH_CHECK(M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31), "tile_gemm_plan: dimensions beyond int32");
+  return kafka_tile_gemm_plan((int)M, (int)N, (int)K, (int)max_splits, &s) == 0 ? s : 0;
+}
+
+static void tile_gemm(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> y, c10::optional<at::Tensor> p,
+                      int64_t splits, bool glu, c10::optional<at::Tensor> scale, int64_t fmt) {
+  check_stream_x("tile_gemm", x);
+  const int vk = check_wfmt("tile_gemm", fmt, wt, scale, 0);
+  const int64_t M = x.size(0), K = x.size(1), N = wt.size(0) * 32;
+  TORCH_CHECK(wt.size(1) * vk == K, "tile_gemm: K mismatch (x has K = ", K, ", the tiles ", wt.size(1) * vk, ")");
+  TORCH_CHECK(x.device() == wt.device(), "tile_gemm: x and wt on different devices");
+  TORCH_CHECK(M >= 1 && M < (1LL << 31) && N % 64 == 0 && K % 256 == 0,
+              "tile_gemm: needs M >= 1, N % 64 == 0 and K % 256 == 0");
+  TORCH_CHECK(splits >= 1 && splits <= 8 && K % (256 * splits) == 0, "tile_gemm: splits must divide K into multiples of 256");
+  TORCH_CHECK(!glu || splits == 1, "tile_gemm: the GLU epilogue needs one split");
+  bf16* yp = nullptr;
+  int64_t ldy = 0;
+  float* pp = nullptr;
+  if (splits == 1) {
+    TORCH_CHECK(y.has_value(), "tile_gemm: y required for one split");
+    CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == M && y->size(1) == (glu ? N / 2 : N) && y->stride(0) % 8 == 0 &&
+                    y->device() == x.device(), "tile_gemm: y must be [M, N] (glu: [M, N/2]) with 16-B rows");
+    yp = bptr(y.value());
+    ldy = y->stride(0);
+  } else {
+    TORCH_CHECK(p.has_value(), "tile_gemm: slab output required");
+    CHECK_CUDA(p.value()); CHECK_DT(p.value(), at::kFloat);
+    TORCH_CHECK(p->is_contiguous() && p->dim() == 3 && p->size(0) == splits && p->size(1) == M && p->size(2) == N &&
+                    p->device() == x.device(), "tile_gemm: slab shape must be [splits, M, N]");
+    pp = p->data_ptr<float>();
+  }
+  CHECK_HIP(kafka_launch_tile_gemm(bptr(x), x.stride(0), (int)fmt, wt.data_ptr(),
+                                   scale.has_value() ? scale->data_ptr() : nullptr, (int)M, (int)N, (int)K, (int)splits,
+                                   glu ? 1 : 0, yp, ldy, pp, cur_stream()));
+}
+
 // explicit-configuration variant (microbenchmark sweeps): (mt, kc, splits) as given, no planning
 static void wstream_gemm_cfg(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> y, c10::optional<at::Tensor> p,
                              int64_t mt, int64_t kc, int64_t s, bool nt, int64_t kw, int64_t pin) {
@@ -1244,6 +1285,9 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("stamps") = py::none());
   m.def("skinny_plan", &skinny_plan);
   m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"), py::arg("splits"),
+        py::arg("glu"), py::arg("scale") = py::none(), py::arg("fmt") = (int64_t)kafka::WF_BF16);
+  m.def("tile_gemm_plan", &tile_gemm_plan);
+  m.def("tile_gemm", &tile_gemm, py::arg("x"), py::arg("wt"), py::arg("y"), py::arg("p"), py::arg("splits"),
         py::arg("glu"), py::arg("scale") = py::none(), py::arg("fmt") = (int64_t)kafka::WF_BF16);
   m.def("wstream_gemm_cfg", &wstream_gemm_cfg);
   m.def("slab_reduce", &slab_reduce);

@@ -298,6 +298,19 @@ hipError_t kafka_launch_grouped_tile_gemm(const bf16* X, int64_t ldx, int wfmt, 
                                           const int* expert_off, int e_lo, int n_ent, int glu, bf16* Y, int64_t ldy,
                                           float* out, int64_t ldo, hipStream_t st);
 
+// ---- tile_gemm.hip
+// Split plan of the dense tile GEMM for a shape (mirrored by ops.tile_gemm_plan): 0 if supported (M >= 1, N % 64 == 0,
+// K % 256 == 0). S doubles, up to min(8, max_splits) with K / S a multiple of 256, while the doubled grid of
+// ceil(M / 256) * ceil(N / 256) * S workgroups still fits one per CU (256). The weight format plays no part.
+int kafka_tile_gemm_plan(int M, int N, int K, int max_splits, int* splits);
+// Y = X . W^T from the dense wave tiles for any M >= 1 (see tile_gemm_kernel): splits == 1 writes Y bf16 [M, N], or with
+// glu (GLU-interleaved tiles) the activated [M, N/2]; splits > 1 (not with glu) writes P fp32 [splits, M, N], split s
+// the K range [s K / splits, +K / splits). wfmt, Wt and scale as for kafka_launch_wstream_gemm. hipErrorInvalidValue
+// for an unsupported shape, ldx % 8 != 0, K % (256 splits) != 0, glu with splits > 1, a quantised format without
+// scales and bf16 tiles with scales.
+hipError_t kafka_launch_tile_gemm(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale, int M, int N,
+                                  int K, int splits, int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st);
+
 // ---- moe.hip
 hipError_t kafka_launch_moe_route(const bf16* logits, int64_t ld, int T, int E, int K, int BM, float* topk_w,
                                   int* topk_e, int* perm_tok, float* perm_w, int* expert_off, int* tile_off,

@@ -28,6 +28,8 @@ def main() -> None:
     ap.add_argument("--mcp", action="store_true", help="KAFKA_MCP=1")
     ap.add_argument("--expert-tiles-only", action="store_true",
                     help="KAFKA_EXPERT_TILES_ONLY=1: MoE experts live in their (quantised) wave tiles alone")
+    ap.add_argument("--tile-prefill", action="store_true",
+                    help="KAFKA_TILE_PREFILL=1: dense projections live in their wave tiles alone at every step size")
     a = ap.parse_args()
     for flag, env in FLAGS.items():
         v = getattr(a, flag)
@@ -39,6 +41,8 @@ def main() -> None:
         os.environ["KAFKA_MCP"] = "1"
     if a.expert_tiles_only:  # (read by the engine itself, like KAFKA_WEIGHT_DTYPE)
         os.environ["KAFKA_EXPERT_TILES_ONLY"] = "1"
+    if a.tile_prefill:
+        os.environ["KAFKA_TILE_PREFILL"] = "1"
     if a.log_json:
         os.environ["KAFKA_LOG_JSON"] = "1"
     import uvicorn
