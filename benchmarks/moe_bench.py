@@ -13,7 +13,12 @@ effective TB/s over the bytes actually streamed (tiles + scales of the experts w
 ``--tiles-only`` times prefill-sized steps (T = 1024 .. 8192) on the grouped tile GEMM (ops.grouped_tiles_*, the tiles of
 ``--weight-dtype``) beside ops.grouped_gemm + silu_mul on the dequantised row-major experts, two interleaved rounds.
 
+``--fused-router`` times the router alone — ``ops.moe_gate_route`` (one launch) beside ``F.linear`` + ``ops.moe_route``
+(two) — and the whole layer with either router (the streaming kernel up to T = 640, the LDS-tiled grouped GEMM above),
+two interleaved rounds; ``--d`` sets the model width (6144 = Mixtral-8x22B), ``--router-only`` skips the layer.
+
   python benchmarks/moe_bench.py            # T = 1, 16, 64, 128, 512, 2048
+  python benchmarks/moe_bench.py --fused-router --d 6144 --router-only
   python benchmarks/moe_bench.py --tiles-only --weight-dtype mxfp4
   python benchmarks/moe_bench.py 1,64,256 --weight-dtype fp8
   python benchmarks/moe_bench.py 64,128,256,512 --compare bf16,fp8,mxfp4
@@ -116,6 +121,25 @@ def tiles_only(Ts, wd, dev, E, K, d, F, router, w13, w2, rounds=2):
                           "max_rel_diff": round(diff, 5)}), flush=True)
 
 
+def fused_router(Ts, dev, E, K, d, router, layer_of, rounds=2):
+    """Router alone and whole layer, fused launch beside F.linear + moe_route, interleaved round by round; every round's
+    us is printed. ``layer_of(x, route)`` runs the experts on a routing, or is None (router only)."""
+    for T in Ts:
+        x = torch.randn(T, d, device=dev, dtype=torch.bfloat16)
+        routes = {"two_launch": lambda: ops.moe_route(torch.nn.functional.linear(x, router), K),
+                  "fused": lambda: ops.moe_gate_route(x, router, K)}
+        a, b = routes["two_launch"](), routes["fused"]()
+        same = all(torch.equal(getattr(a, f), getattr(b, f)) for f in ("topk_e", "perm_tok", "expert_off", "tile_off"))
+        res = {k + sfx: [] for k in routes for sfx in ("_router_us", "_layer_us")}
+        for _ in range(rounds):
+            for k, fn in routes.items():
+                res[k + "_router_us"].append(round(timeit(fn, iters=50, rounds=5), 2))
+            for k, fn in routes.items():
+                if layer_of is not None:
+                    res[k + "_layer_us"].append(round(timeit(lambda: layer_of(x, fn()), iters=10, rounds=3), 1))
+        print(json.dumps({"T": T, "d": d, "E": E, "k": K, "same_routing": same, **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("Ts", nargs="?", default="1,16,64,128,512,2048", help="comma-separated token counts")
@@ -124,15 +148,24 @@ def main():
     ap.add_argument("--tiles-only", action="store_true",
                     help="prefill sizes (default T = 1024, 2048, 4096, 8192): the grouped tile GEMM on the expert tiles "
                          "of --weight-dtype beside grouped_gemm on the dequantised row-major experts")
+    ap.add_argument("--fused-router", action="store_true",
+                    help="the router alone and the whole layer: ops.moe_gate_route beside F.linear + ops.moe_route "
+                         "(default T = 1, 16, 64, 128, 256, 640, 2048, 8192)")
+    ap.add_argument("--router-only", action="store_true", help="with --fused-router: no expert weights, no layer timing")
+    ap.add_argument("--d", type=int, default=4096, help="model width (Mixtral-8x7B 4096, 8x22B 6144)")
     args = ap.parse_args()
+    if args.fused_router and args.Ts == ap.get_default("Ts"):
+        args.Ts = "1,16,64,128,256,640,2048,8192"
     if args.tiles_only and args.Ts == ap.get_default("Ts"):
         args.Ts = "1024,2048,4096,8192"
     Ts = [int(x) for x in args.Ts.split(",")]
     wd = args.weight_dtype
     dev = torch.device("cuda:0")
-    E, K, d, F = 8, 2, 4096, 14336
+    E, K, d, F = 8, 2, args.d, 14336
     torch.manual_seed(0)
     router = (torch.randn(E, d, device=dev) * d ** -0.5).to(torch.bfloat16)
+    if args.fused_router and args.router_only:
+        return fused_router(Ts, dev, E, K, d, router, None)
     w13 = (torch.randn(E, 2 * F, d, device=dev) * d ** -0.5).to(torch.bfloat16)
     w2 = (torch.randn(E, d, F, device=dev) * F ** -0.5).to(torch.bfloat16)
     if args.compare:
@@ -147,6 +180,17 @@ def main():
     (w13t, w13s), (w2t, w2s) = ops.tile_experts_as(w13, wd, True), ops.tile_experts_as(w2, wd)
     if w13s is not None:
         w13, w2 = ops.untile_experts_as(w13t, w13s, True), ops.untile_experts_as(w2t, w2s)
+    if args.fused_router:
+        def layer_of(x, r):
+            T = x.shape[0]
+            out = torch.zeros(T, d, dtype=torch.float32, device=dev)
+            if T <= 640:
+                a = ops.grouped_stream_glu(x, w13t, r, scale=w13s)
+                return ops.grouped_stream_combine(a, w2t, r, T, out, scale=w2s)
+            a = ops.silu_mul(ops.grouped_gemm(x, w13, r, gather=True))
+            return ops.grouped_gemm(a, w2, r, gather=False, combine_out=out)
+
+        return fused_router(Ts, dev, E, K, d, router, layer_of)
     for T in Ts:
         x = torch.randn(T, d, device=dev, dtype=torch.bfloat16)
 

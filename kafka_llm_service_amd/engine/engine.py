@@ -81,6 +81,9 @@ class EngineConfig:
     # on a row-major (dequantised) copy or on a transient untiled one. Needs the streaming decode GEMM; covers the
     # attention projections and the lm_head of a MoE model; not with expert_tiles_only; env KAFKA_TILE_PREFILL=1 overrides
     tile_prefill: bool = False
+    # MoE models: every layer's routing (router GEMM + softmax / top-k + expert sort) from the one launch of
+    # ops.moe_gate_route (csrc/moe_router.hip) instead of F.linear + ops.moe_route; env KAFKA_FUSED_ROUTER=1 overrides
+    fused_router: bool = False
     # the default of SamplingParams.tool_grammar["mode"]: "program" (engine/constrained.py) or "automaton"
     # (engine/tool_automaton.py: the call body's automaton masked on the device); env KAFKA_TOOL_GRAMMAR overrides
     tool_grammar: str = "program"
@@ -199,6 +202,18 @@ class LLMEngine:
                 self.model.enable_stream_weights(tiled_only=True, weight_dtype=wdt)
         elif mode == "stream_only" and not self.model.stream:
             self.model.enable_stream_weights(tiled_only=True, weight_dtype=wdt)
+        fr = os.environ.get("KAFKA_FUSED_ROUTER")
+        fr = cfg.fused_router if fr is None else fr == "1"
+        if fr:
+            if not mc.num_experts:
+                raise ValueError(f"fused_router needs a MoE model, {mc.name} is dense")
+            if not ops.moe_gate_route_supported(mc.hidden_size, mc.num_experts, mc.num_experts_per_tok):
+                raise ValueError(f"fused_router: hidden size {mc.hidden_size}, {mc.num_experts} experts, top-"
+                                 f"{mc.num_experts_per_tok} is outside ops.moe_gate_route (hidden size a multiple of "
+                                 "64, at most 16 experts, top-4)")
+            if self.device.type == "cuda":  # the workspace of the largest step, so that a graph capture never allocates
+                ops.moe_gate_route_reserve(self.device, cfg.max_num_batched_tokens)
+        cfg.fused_router = self.model.fused_router = fr
         if self.model.tiled_only and cfg.max_num_seqs > self.model.stream_max_m:
             # decode batches beyond the streaming kernel's rows would untile every projection every step
             log.info("tiled-only weights: max_num_seqs %d -> %d", cfg.max_num_seqs, self.model.stream_max_m)

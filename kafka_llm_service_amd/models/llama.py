@@ -130,6 +130,7 @@ class TransformerLM:
         self.tiled_only = False  # row-major dense weights dropped (enable_stream_weights(tiled_only=True))
         self.expert_tiles_only = False  # row-major experts dropped (enable_stream_weights(expert_tiles_only=True))
         self.tile_prefill = False  # row-major dense weights dropped, prefill on ops.linear_tiles (tile_prefill=True)
+        self.fused_router = False  # MoE routing from ops.moe_gate_route (EngineConfig.fused_router; models/moe.py)
         self.stream_max_m = ops.STREAM_MAX_M  # rows up to which a step's projections stream
         self._fused_shapes = None  # whether the fused decode layer applies to this model (decided on first use)
 

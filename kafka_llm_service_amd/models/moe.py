@@ -6,8 +6,9 @@ its own experts over the tokens routed to them and the per-rank partial outputs 
 that a dense row-parallel MLP would use (one collective per layer, [T, d] bf16). With ep = 1 the whole block is
 local (Mixtral 8x7B bf16 = 93 GB fits one 288 GB MI355X).
 
-Per layer: router GEMM (hipBLASLt) -> ``ops.moe_route`` (HIP, one workgroup: softmax + top-k + renormalise + stable
-expert sort, no host sync) -> ``ops.grouped_gemm`` gate_up (HIP MFMA, A rows gathered through the permutation) ->
+Per layer: router GEMM (``F.linear``: hipBLASLt on the GPU) -> ``ops.moe_route`` (HIP, one workgroup: softmax + top-k +
+renormalise + stable expert sort, no host sync) — or, with ``model.fused_router`` (``EngineConfig.fused_router``), both
+in the one launch of ``ops.moe_gate_route`` (csrc/moe_router.hip), on every path below — -> ``ops.grouped_gemm`` gate_up (HIP MFMA, A rows gathered through the permutation) ->
 ``ops.silu_mul`` -> ``ops.grouped_gemm`` down with the routing-weighted scatter-combine fused into its epilogue
 (fp32 atomics onto a zeroed [T, d] buffer). On CPU the same calls run the fp32 references of ``ops/reference.py``.
 
@@ -65,8 +66,11 @@ class MoEBlock:
 
     def __call__(self, x: torch.Tensor, lw) -> torch.Tensor:
         T, d = x.shape
-        logits = F.linear(x, lw.router)
-        r = ops.moe_route(logits, self.k)
+        if self.model.fused_router:
+            r = ops.moe_gate_route(x, lw.router, self.k)
+        else:
+            logits = F.linear(x, lw.router)
+            r = ops.moe_route(logits, self.k)
         if self.ep > 1 and self.a2a:
             return self._a2a(x, lw, r)
         if self.model.stream and lw.w13_t is not None and T <= MOE_STREAM_MAX_T:

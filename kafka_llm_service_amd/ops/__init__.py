@@ -11,6 +11,7 @@ Kernel inventory:
   schema_mask / schema_advance (json_schema)    csrc/table_grammar.hip
   tool_mask / tool_advance (tool automaton)     csrc/table_grammar.hip
   moe_* / grouped GEMM                          csrc/moe.hip
+  moe_gate_route (router GEMM + moe_route)      csrc/moe_router.hip
   custom all-reduce                             csrc/allreduce.hip
 """
 from __future__ import annotations
@@ -1188,6 +1189,62 @@ def moe_route(logits: torch.Tensor, k: int) -> MoERouting:
         ext().moe_route(logits, int(k), GG_BM, tw, te, pt, pw, eo, to)
         return MoERouting(tw, te, pt, pw, eo, to, E)
     tw, te, pt, pw, eo, to = ref.moe_route(logits, k, GG_BM)
+    return MoERouting(tw, te, pt, pw, eo, to, E)
+
+
+# ---- fused router (csrc/moe_router.hip): gate GEMM + moe_route in one launch -------------------------------------
+_ROUTER_WS: dict = {}
+_CUS: dict = {}
+
+
+def _cus(dev: torch.device) -> int:
+    n = _CUS.get(dev)
+    if n is None:
+        n = _CUS[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return n
+
+
+def moe_gate_route_supported(d: int, E: int, k: int) -> bool:
+    """Shapes ``moe_gate_route`` serves: ``moe_route``'s E <= 16 and k <= 4, and a width of whole 64-column chunks."""
+    return 1 <= k <= min(4, E) and E <= 16 and d >= 64 and d % 64 == 0
+
+
+def moe_gate_route_reserve(dev: torch.device, T: int) -> torch.Tensor:
+    """The fused router's per-device workspace (ticket word + fp32 split-K slabs), large enough for steps of up to
+    ``T`` tokens at any width: zeroed once, when allocated (the kernel re-arms its ticket). The engine reserves its
+    largest step at start-up so that a graph capture never allocates."""
+    # splits <= ceil(CUs / row tiles) and a row tile is 64 tokens: splits * t <= 64 * (CUs + row tiles) for every t <= T
+    need = 64 + 16 * 64 * (_cus(dev) + (int(T) + 63) // 64)
+    ws = _ROUTER_WS.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _ROUTER_WS[dev] = torch.zeros(need, dtype=torch.int32, device=dev)
+    return ws
+
+
+def moe_gate_route(x: torch.Tensor, w: torch.Tensor, k: int, logits_out: torch.Tensor | None = None) -> MoERouting:
+    """``moe_route(F.linear(x, w), k)`` in one launch: x bf16 [T, d] (any row stride), w bf16 [E, d] (the router).
+    ``logits_out`` (bf16 [T, E]) receives the logits the routing was computed on."""
+    T, d = x.shape
+    E = w.shape[0]
+    dev = x.device
+    if not _gpu(x):
+        logits = torch.nn.functional.linear(x, w)
+        if logits_out is not None:
+            logits_out.copy_(logits)
+        tw, te, pt, pw, eo, to = ref.moe_route(logits, k, GG_BM)
+        return MoERouting(tw, te, pt, pw, eo, to, E)
+    if not moe_gate_route_supported(d, E, k):
+        raise ValueError(f"moe_gate_route: unsupported d = {d}, E = {E}, k = {k} (d % 64 == 0, E <= 16, k <= 4)")
+    if logits_out is None:
+        logits_out = torch.empty(T, E, dtype=torch.bfloat16, device=dev)
+    tw = torch.empty(T, k, dtype=torch.float32, device=dev)
+    te = torch.empty(T, k, dtype=torch.int32, device=dev)
+    pt = torch.empty(T * k, dtype=torch.int32, device=dev)
+    pw = torch.empty(T * k, dtype=torch.float32, device=dev)
+    eo = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    to = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    ext().moe_gate_route(x, w, int(k), GG_BM, _cus(dev), moe_gate_route_reserve(dev, T), logits_out, tw, te, pt, pw,
+                         eo, to)
     return MoERouting(tw, te, pt, pw, eo, to, E)
 
 

@@ -1016,6 +1016,54 @@ static void moe_route(at::Tensor logits, int64_t k, int64_t bm, at::Tensor topk_
                                    expert_off.data_ptr<int>(), tile_off.data_ptr<int>(), cur_stream()));
 }
 
+// (K splits, workspace words) of the fused router for a step shape; (0, 0) if unsupported
+static std::tuple<int64_t, int64_t> moe_gate_route_plan(int64_t T, int64_t d, int64_t cus) {
+  int s = 0;
+  int64_t words = 0;
+  if (T < 1 || T >= (1LL << 31) || d < 1 || d >= (1LL << 31) || cus < 1 || cus >= (1LL << 31) ||
+      kafka_moe_gate_route_plan((int)T, (int)d, (int)cus, &s, &words) != 0)
+    return {0, 0};
+  return {s, words};
+}
+
+// router GEMM + softmax -> top-k -> renormalise + stable expert sort in one launch (csrc/moe_router.hip)
+static void moe_gate_route(at::Tensor x, at::Tensor w, int64_t k, int64_t bm, int64_t cus, at::Tensor ws,
+                           at::Tensor logits, at::Tensor topk_w, at::Tensor topk_e, at::Tensor perm_tok,
+                           at::Tensor perm_w, at::Tensor expert_off, at::Tensor tile_off) {
+  CHECK_CUDA(x); CHECK_CUDA(w); CHECK_CUDA(ws); CHECK_CUDA(logits);
+  CHECK_DT(x, at::kBFloat16); CHECK_DT(w, at::kBFloat16); CHECK_DT(logits, at::kBFloat16); CHECK_DT(ws, at::kInt);
+  CHECK_DT(topk_w, at::kFloat); CHECK_DT(perm_w, at::kFloat);
+  CHECK_DT(topk_e, at::kInt); CHECK_DT(perm_tok, at::kInt); CHECK_DT(expert_off, at::kInt); CHECK_DT(tile_off, at::kInt);
+  CHECK_LASTDIM(x); CHECK_LASTDIM(logits);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && logits.dim() == 2 && w.is_contiguous() && ws.is_contiguous(),
+              "moe_gate_route: x [T, d], contiguous w [E, d], logits [T, E]");
+  const int64_t T = x.size(0), d = x.size(1), E = w.size(0);
+  TORCH_CHECK(T >= 1 && T < (1LL << 31) && w.size(1) == d && E >= 1 && E <= 16 && k >= 1 && k <= 4 && k <= E &&
+                  d % 64 == 0 && d < (1LL << 31) && bm >= 1,
+              "moe_gate_route: unsupported T/d/E/k");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(0) >= d && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "moe_gate_route: x rows must be 16-byte aligned");
+  TORCH_CHECK(logits.size(0) == T && logits.size(1) == E && logits.stride(0) >= E, "moe_gate_route: logits [T, E]");
+  TORCH_CHECK(topk_w.numel() == T * k && topk_e.numel() == T * k && perm_tok.numel() == T * k &&
+                  perm_w.numel() == T * k && expert_off.numel() == E + 1 && tile_off.numel() == E + 1,
+              "moe_gate_route: output sizes");
+  TORCH_CHECK(topk_w.is_contiguous() && topk_e.is_contiguous() && perm_tok.is_contiguous() && perm_w.is_contiguous() &&
+                  expert_off.is_contiguous() && tile_off.is_contiguous(),
+              "moe_gate_route: contiguous outputs");
+  for (const at::Tensor* t : {&w, &ws, &logits, &topk_w, &topk_e, &perm_tok, &perm_w, &expert_off, &tile_off})
+    TORCH_CHECK(t->is_cuda() && t->device() == x.device(), "moe_gate_route: every tensor on x's device");
+  int splits = 0;
+  int64_t words = 0;
+  TORCH_CHECK(cus >= 1 && cus < (1LL << 31) &&
+                  kafka_moe_gate_route_plan((int)T, (int)d, (int)cus, &splits, &words) == 0,
+              "moe_gate_route: no split plan for this shape");
+  TORCH_CHECK(ws.numel() >= words, "moe_gate_route: workspace of ", ws.numel(), " words, the step needs ", words);
+  CHECK_HIP(kafka_launch_moe_gate_route(bptr(x), x.stride(0), bptr(w), (int)T, (int)d, (int)E, (int)k, (int)bm, splits,
+                                        ws.data_ptr<int>(), bptr(logits), logits.stride(0), topk_w.data_ptr<float>(),
+                                        topk_e.data_ptr<int>(), perm_tok.data_ptr<int>(), perm_w.data_ptr<float>(),
+                                        expert_off.data_ptr<int>(), tile_off.data_ptr<int>(), cur_stream()));
+}
+
 // Y (or out += w * Y) = X_e . W_e^T per expert segment of the routed entries; W = [e_n, N, K] local experts
 static void grouped_gemm(at::Tensor x, at::Tensor w, at::Tensor perm_tok, at::Tensor perm_w, at::Tensor expert_off,
                          at::Tensor tile_off, int64_t e_lo, int64_t max_tiles, bool gather,
@@ -1298,6 +1346,8 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("glu"), py::arg("y"),
         py::arg("out"));
   m.def("moe_route", &moe_route);
+  m.def("moe_gate_route_plan", &moe_gate_route_plan);
+  m.def("moe_gate_route", &moe_gate_route);
   m.def("cu_mask_stream", &cu_mask_stream);
   m.def("stream_cu_mask", &stream_cu_mask);
   m.def("car_alloc", &car_alloc);

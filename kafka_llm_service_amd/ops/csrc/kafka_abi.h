@@ -326,6 +326,20 @@ hipError_t kafka_launch_ep_recv_route(const bf16* img, int ep, int C, int MR, in
 hipError_t kafka_launch_ep_combine(const bf16* back, const int* slot_map, const float* topk_w, int lo, int n_own,
                                    int k, int d, bf16* out, int64_t ldo, hipStream_t st);
 
+// ---- moe_router.hip
+// K splits of the fused router for T tokens at width d on a device of `cus` compute units, and the 4-byte words of
+// workspace one launch needs (header with the ticket + fp32 slabs [splits][T][16]). 0 if supported (d % 64 == 0). The
+// rule: one workgroup per CU (row tiles of 64 tokens x splits), at most one split per 256 columns, one split once the
+// row tiles alone fill the machine.
+int kafka_moe_gate_route_plan(int T, int d, int cus, int* splits, int64_t* ws_words);
+// Gate GEMM + routing in one launch (see moe_gate_route_kernel): logits bf16 [T, E] (row stride ldl) = X [T, d] . W^T
+// (W contiguous [E, d]), then moe_route's six outputs on those logits. ws: the per-device workspace, zeroed once when
+// allocated (the kernel re-arms its ticket), at least the plan's ws_words. hipErrorInvalidValue for E > 16, K > 4,
+// d % 64 != 0, ldx % 8 != 0, unaligned X / W / ws, or a split count that leaves a split empty.
+hipError_t kafka_launch_moe_gate_route(const bf16* X, int64_t ldx, const bf16* W, int T, int d, int E, int K, int BM,
+                                       int splits, int* ws, bf16* logits, int64_t ldl, float* topk_w, int* topk_e,
+                                       int* perm_tok, float* perm_w, int* expert_off, int* tile_off, hipStream_t st);
+
 // ---- allreduce.hip
 hipError_t kafka_car_alloc(int64_t bytes, void** out);
 // Host copy of the timing ring ([AR_TIME_SLOTS][2] uint64 = 2 KB) and of block 0's epoch (the call count), on a

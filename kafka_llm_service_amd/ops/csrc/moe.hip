@@ -36,12 +36,9 @@
 //                        expert_off[El]).
 //   ep_combine_kernel    grid (owned tokens): out[t] = sum_j w[t, j] * back[slot_map[t k + j]] (fp32, bf16 store).
 #include "common.h"
+#include "moe_route.h"  // the two routing phases (shared with moe_router.hip), MOE_MAXE / MOE_MAXK / MOE_NT
 
 namespace kafka {
-
-constexpr int MOE_MAXE = 16;
-constexpr int MOE_MAXK = 4;
-constexpr int MOE_NT = 1024;
 
 __global__ __launch_bounds__(MOE_NT) void moe_route_kernel(const bf16* __restrict__ logits, int64_t ld, int T, int E,
                                                             int K, int BM, float* __restrict__ topk_w,
@@ -49,82 +46,10 @@ __global__ __launch_bounds__(MOE_NT) void moe_route_kernel(const bf16* __restric
                                                             float* __restrict__ perm_w, int* __restrict__ expert_off,
                                                             int* __restrict__ tile_off) {
   __shared__ int wsum[MOE_NT / 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int per = (T + MOE_NT - 1) / MOE_NT;  // tokens owned by this thread: [t0, t1)
-  const int t0 = min(T, tid * per), t1 = min(T, t0 + per);
-  // ---- phase 1: softmax + top-k + renormalise for the owned tokens
-  for (int t = t0; t < t1; ++t) {
-    float p[MOE_MAXE];
-    float m = -INFINITY;
-    for (int e = 0; e < E; ++e) {
-      p[e] = (float)logits[(int64_t)t * ld + e];
-      m = fmaxf(m, p[e]);
-    }
-    float s = 0.f;
-    for (int e = 0; e < E; ++e) {
-      p[e] = __expf(p[e] - m);
-      s += p[e];
-    }
-    float tot = 0.f;
-    int sel[MOE_MAXK];
-    float sw[MOE_MAXK];
-    for (int j = 0; j < K; ++j) {
-      int best = 0;
-      float bv = -1.f;
-      for (int e = 0; e < E; ++e)
-        if (p[e] > bv) {  // strict: lowest index wins ties (torch.topk order on equal values is unspecified)
-          bv = p[e];
-          best = e;
-        }
-      sel[j] = best;
-      sw[j] = bv / s;
-      tot += sw[j];
-      p[best] = -2.f;
-    }
-    for (int j = 0; j < K; ++j) {
-      topk_w[(int64_t)t * K + j] = sw[j] / tot;
-      topk_e[(int64_t)t * K + j] = sel[j];
-    }
-  }
-  // ---- phase 2: stable sort of the entries [t0*K, t1*K) by expert (each thread re-reads its own writes)
-  int base = 0, tbase = 0;
-  for (int e = 0; e < E; ++e) {
-    int c = 0;
-    for (int i = t0 * K; i < t1 * K; ++i) c += topk_e[i] == e;
-    // block exclusive scan of c
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += v;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int wpre = 0, total = 0;
-    for (int i = 0; i < MOE_NT / 64; ++i) {
-      const int v = wsum[i];
-      wpre += i < w ? v : 0;
-      total += v;
-    }
-    int pos = base + wpre + incl - c;
-    for (int i = t0 * K; i < t1 * K; ++i)
-      if (topk_e[i] == e) {
-        perm_tok[pos] = i / K;
-        perm_w[pos] = topk_w[i];
-        ++pos;
-      }
-    base += total;
-    tbase += (total + BM - 1) / BM;
-    if (tid == 0) {
-      expert_off[e + 1] = base;
-      tile_off[e + 1] = tbase;
-    }
-    __syncthreads();  // wsum is reused by the next expert
-  }
-  if (tid == 0) {
-    expert_off[0] = 0;
-    tile_off[0] = 0;
-  }
+  int t0, t1;  // tokens owned by this thread
+  route_span(T, t0, t1);
+  route_topk(logits, ld, t0, t1, E, K, topk_w, topk_e);
+  route_sort(t0, t1, E, K, BM, topk_w, topk_e, perm_tok, perm_w, expert_off, tile_off, wsum);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -30,6 +30,8 @@ def main() -> None:
                     help="KAFKA_EXPERT_TILES_ONLY=1: MoE experts live in their (quantised) wave tiles alone")
     ap.add_argument("--tile-prefill", action="store_true",
                     help="KAFKA_TILE_PREFILL=1: dense projections live in their wave tiles alone at every step size")
+    ap.add_argument("--fused-router", action="store_true",
+                    help="KAFKA_FUSED_ROUTER=1: MoE routing (router GEMM, top-k, expert sort) in one HIP launch")
     a = ap.parse_args()
     for flag, env in FLAGS.items():
         v = getattr(a, flag)
@@ -43,6 +45,8 @@ def main() -> None:
         os.environ["KAFKA_EXPERT_TILES_ONLY"] = "1"
     if a.tile_prefill:
         os.environ["KAFKA_TILE_PREFILL"] = "1"
+    if a.fused_router:
+        os.environ["KAFKA_FUSED_ROUTER"] = "1"
     if a.log_json:
         os.environ["KAFKA_LOG_JSON"] = "1"
     import uvicorn
