@@ -4,7 +4,9 @@ in every tile format, against yardsticks from outside the code under test:
   (b) untile_blas: ops.untile_weight_as + F.linear (+ silu_mul): what a tiled-only model does today on such a step;
   (c) grouped:     gate_up only, ops.grouped_tiles_glu with one expert and an identity routing (the 2 x 2-block kernel).
 Interleaved rounds: every round times all paths of a cell back to back, so a comparison holds only where it has the
-same sign in every round by more than the cell moves between rounds. Each timed call of a path reads another copy of
+same sign in every round by more than the cell moves between rounds. ``--act-dtype mxfp8`` (MXFP4 tiles only) adds the
+scaled-MFMA path of csrc/tile_gemm_mx.hip: ``mx`` = ops.linear_tiles(act="mxfp8"), the quantiser's launch included,
+``mx_gemm`` = the GEMM alone on activations quantised beforehand, ``quant`` = the quantiser alone. Each timed call of a path reads another copy of
 the weight (>= 600 MB rotated, so the MALL does not serve repeats). One JSON line per (round, cell); TFLOP/s over
 2 M N K."""
 import argparse
@@ -48,7 +50,11 @@ def main():
     ap.add_argument("--gemms", default="qkv,o,gate_up,down")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--act-dtype", default="bf16", choices=ops.ACT_DTYPES)
     args = ap.parse_args()
+    mx = args.act_dtype == "mxfp8"
+    if mx:
+        args.formats = "mxfp4"
     if not torch.cuda.is_available():
         raise SystemExit("tile_gemm_bench needs a GPU")
     dev = "cuda"
@@ -73,7 +79,20 @@ def main():
                     paths = {"tiles": lambda i: ops.linear_tiles(x, qs[i % copies][0], glu=glu, scale=qs[i % copies][1]),
                              "blas_copy": lambda i: act(F.linear(x, deqs[i % copies])),
                              "untile_blas": lambda i: act(F.linear(x, ops.untile_weight_as(*qs[i % copies], glu)))}
-                    if glu:
+                    if mx:
+                        xq, xe = ops.mxfp8_quant(x)
+                        u8 = [(q[0].view(torch.uint8), q[1].view(torch.uint8)) for q in qs]
+
+                        def mx_gemm(i):
+                            y = torch.empty(M, N // 2 if glu else N, dtype=x.dtype, device=dev) if S == 1 else None
+                            p = torch.empty(S, M, N, dtype=torch.float32, device=dev) if S > 1 else None
+                            ops.ext().tile_gemm_mx(xq, xe.view(torch.uint8), *u8[i % copies], y, p, S, glu)
+
+                        paths = {"tiles": paths["tiles"], "blas_copy": paths["blas_copy"], "mx_gemm": mx_gemm,
+                                 "mx": lambda i: ops.linear_tiles(x, qs[i % copies][0], glu=glu, scale=qs[i % copies][1],
+                                                                  act="mxfp8"),
+                                 "quant": lambda i: ops.mxfp8_quant(x)}
+                    elif glu:
                         paths["grouped"] = lambda i: ops.grouped_tiles_glu(
                             x, qs[i % copies][0][None], route, scale=None if qs[i % copies][1] is None
                             else qs[i % copies][1][None])
@@ -83,7 +102,8 @@ def main():
                                 "round": rnd}
                         for k, t in us.items():
                             line[k + "_us"] = round(t, 1)
-                            line[k + "_TFLOP/s"] = round(2.0 * M * N * K / t / 1e6, 1)
+                            if k != "quant":
+                                line[k + "_TFLOP/s"] = round(2.0 * M * N * K / t / 1e6, 1)
                         print(json.dumps(line), flush=True)
                 del qs, deqs
                 torch.cuda.empty_cache()

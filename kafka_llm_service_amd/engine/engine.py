@@ -81,6 +81,11 @@ class EngineConfig:
     # on a row-major (dequantised) copy or on a transient untiled one. Needs the streaming decode GEMM; covers the
     # attention projections and the lm_head of a MoE model; not with expert_tiles_only; env KAFKA_TILE_PREFILL=1 overrides
     tile_prefill: bool = False
+    # activations of the dense tile GEMM: "bf16", or "mxfp8" = the layer projections of steps above 256 rows quantise
+    # their input to MXFP8 (e4m3, one e8m0 exponent per 32 columns) and run on the scaled fp8 x fp4 MFMA
+    # (csrc/tile_gemm_mx.hip). Needs weight_dtype "mxfp4" and tile_prefill; the lm_head and decode-sized steps keep bf16
+    # activations, so prefill and decode rows differ in numerics; env KAFKA_ACT_DTYPE overrides
+    act_dtype: str = "bf16"             # bf16 | mxfp8
     # MoE models: every layer's routing (router GEMM + softmax / top-k + expert sort) from the one launch of
     # ops.moe_gate_route (csrc/moe_router.hip) instead of F.linear + ops.moe_route; env KAFKA_FUSED_ROUTER=1 overrides
     fused_router: bool = False
@@ -183,10 +188,20 @@ class LLMEngine:
         if self.model.stream and self.model.tile_prefill != tpf:
             raise ValueError(f"the model's tile_prefill is {self.model.tile_prefill}, the engine asks for {tpf}")
         cfg.tile_prefill = tpf
+        adt = os.environ.get("KAFKA_ACT_DTYPE") or cfg.act_dtype
+        if adt not in ("bf16", "mxfp8"):
+            raise ValueError(f"act_dtype must be bf16 or mxfp8, not {adt!r}")
+        if adt == "mxfp8" and not (wdt == "mxfp4" and tpf):
+            raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill (the scaled MFMA reads the "
+                             f"MXFP4 tiles), not weight_dtype={wdt!r}, tile_prefill={tpf}")
+        if self.model.stream and getattr(self.model, "act_dtype", "bf16") != adt:
+            raise ValueError(f"the model's act_dtype is {getattr(self.model, 'act_dtype', 'bf16')}, the engine asks for {adt}")
+        cfg.act_dtype = adt
         if tpf and not self.model.stream:
             # the dense projections need no second copy in this mode: nothing to fit next to the KV pool, which is sized
             # below, after the row-major tensors are freed
-            self.model.enable_stream_weights(tiled_only=mode == "stream_only", weight_dtype=wdt, tile_prefill=True)
+            self.model.enable_stream_weights(tiled_only=mode == "stream_only", weight_dtype=wdt, tile_prefill=True,
+                                             act_dtype=adt)
         elif mode == "stream" and not self.model.stream:
             need = self.model.stream_weight_bytes(wdt, expert_tiles_only=eto)
             free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else max(need, 1) * 4
@@ -281,7 +296,8 @@ class LLMEngine:
         self.stop_checker_factory = None  # set by the frontend: (request params) -> incremental stop-string checker
         log.info("engine ready: %s tp=%d weights %s%s (%.1f GB) kv pages=%d (%s, %.1f GB) load %.1fs", mc.name, cfg.tp,
                  self.model.weight_dtype, ", expert tiles only" if self.model.expert_tiles_only else
-                 (", tile prefill" if self.model.tile_prefill else ""),
+                 (", tile prefill" if self.model.tile_prefill else "") +
+                 (", mxfp8 activations" if cfg.act_dtype == "mxfp8" else ""),
                  self.model.weight_bytes() / 1e9, nb, cfg.kv_dtype, nb * page_bytes / 1e9, self.load_s)
 
     # ------------------------------------------------------------------------------------------------------------

@@ -130,6 +130,7 @@ class TransformerLM:
         self.tiled_only = False  # row-major dense weights dropped (enable_stream_weights(tiled_only=True))
         self.expert_tiles_only = False  # row-major experts dropped (enable_stream_weights(expert_tiles_only=True))
         self.tile_prefill = False  # row-major dense weights dropped, prefill on ops.linear_tiles (tile_prefill=True)
+        self.act_dtype = "bf16"  # activations of the layers' linear_tiles calls (enable_stream_weights(act_dtype=))
         self.fused_router = False  # MoE routing from ops.moe_gate_route (EngineConfig.fused_router; models/moe.py)
         self.stream_max_m = ops.STREAM_MAX_M  # rows up to which a step's projections stream
         self._fused_shapes = None  # whether the fused decode layer applies to this model (decided on first use)
@@ -183,7 +184,8 @@ class TransformerLM:
         return weight_dtype if ops.weight_format(weight_dtype).experts else "bf16"
 
     def enable_stream_weights(self, tiled_only: bool = False, weight_dtype: str = "bf16",
-                              expert_tiles_only: bool = False, tile_prefill: bool = False) -> int:
+                              expert_tiles_only: bool = False, tile_prefill: bool = False,
+                              act_dtype: str = "bf16") -> int:
         """Keep a wave-tiled copy of every dense projection and of the lm_head (ops.tile_weight) so decode-sized
         steps (T <= ops.STREAM_MAX_M) run the weight-streaming MFMA GEMM (csrc/wstream_gemm.hip) instead of
         hipBLASLt; prefill-sized steps keep the row-major weights. Costs one more copy of those weights (16 GB for
@@ -234,7 +236,18 @@ class TransformerLM:
         streaming kernel keeps its default row limit. Export, the dense oracle and ``dense_weight`` untile as in
         tiled-only mode. Every streamed projection must pass ``ops.tile_gemm_supported``. MoE models: the flag covers
         the attention projections and the lm_head (the experts follow ``tiled_only`` as before); not together with
-        ``expert_tiles_only``."""
+        ``expert_tiles_only``.
+
+        ``act_dtype="mxfp8"`` (with ``weight_dtype="mxfp4"`` and ``tile_prefill``): the layer projections that go through
+        ``ops.linear_tiles`` (qkv, o, gate_up, down on steps above 256 rows) quantise their input to MXFP8 — e4m3 in
+        32-column blocks with an e8m0 exponent each — and run on the scaled fp8 x fp4 MFMA (csrc/tile_gemm_mx.hip).
+        The lm_head and the streamed / skinny steps keep bf16 activations, so the model's numerics then differ by step
+        size: prefill rows see quantised activations, decode rows do not."""
+        if act_dtype not in ops.ACT_DTYPES:
+            raise ValueError(f"act_dtype must be {', '.join(ops.ACT_DTYPES)}, not {act_dtype!r}")
+        if act_dtype == "mxfp8" and not (weight_dtype == "mxfp4" and tile_prefill):
+            raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill (the scaled MFMA reads the "
+                             f"MXFP4 tiles), not weight_dtype={weight_dtype!r}, tile_prefill={tile_prefill}")
         if tile_prefill:
             if expert_tiles_only:
                 raise ValueError("tile_prefill together with expert_tiles_only is not supported")
@@ -307,6 +320,7 @@ class TransformerLM:
         self.tiled_only = tiled_only
         self.expert_tiles_only = expert_tiles_only
         self.tile_prefill = tile_prefill
+        self.act_dtype = act_dtype
         self.weight_dtype = weight_dtype
         # tiled-only: any larger step would untile every projection for hipBLASLt, so the streaming kernel takes
         # steps up to its 256-row limit (two row tiles beyond 128) — slower than hipBLASLt there, far cheaper than
@@ -328,7 +342,8 @@ class TransformerLM:
             if kind in SKINNY and ops.skinny_plan(M, wt.shape[0] * 32, x.shape[1], max_splits):
                 return ops.linear_skinny(x, wt, max_splits, scale=st)
             if self.tile_prefill and M > 0:
-                return ops.linear_tiles(x, wt, max_splits, scale=st)
+                # (the lm_head, kind "", keeps bf16 activations: logits are what the sampler and logprobs read)
+                return ops.linear_tiles(x, wt, max_splits, scale=st, act=self.act_dtype if kind else "bf16")
         return F.linear(x, self._dense(w, wt, st=st))
 
     @staticmethod
@@ -418,7 +433,7 @@ class TransformerLM:
                     a = ops.silu_mul(a)
             elif self.tile_prefill and lw.gate_up_t is not None and T > 0:
                 # the dense tile GEMM: SwiGLU in its epilogue on GLU-tiled weights, else gate | up through silu_mul
-                a = ops.linear_tiles(x, lw.gate_up_t, glu=bool(lw.glu), scale=lw.gate_up_s)
+                a = ops.linear_tiles(x, lw.gate_up_t, glu=bool(lw.glu), scale=lw.gate_up_s, act=self.act_dtype)
                 if not lw.glu:
                     a = ops.silu_mul(a)
             else:

@@ -733,18 +733,43 @@ def tile_gemm_plan(M: int, N: int, K: int, max_splits: int = 8) -> int:
     return s
 
 
+ACT_DTYPES = ("bf16", "mxfp8")  # activations of the dense tile GEMM (EngineConfig.act_dtype)
+mxfp8_dequant = ref.mxfp8_dequant
+
+
+def mxfp8_quant(x: torch.Tensor):
+    """bf16 activations [M, K] -> (xq uint8 [M, K] e4m3 bytes in natural K order, xe float8_e8m0fnu [M, K/32]): MXFP8,
+    one e8m0 exponent per (row, 32-column block), by ``reference.mxfp8_quant``'s rule. A GPU tensor (16-B aligned rows,
+    K % 256 == 0) runs the HIP quantiser of csrc/tile_gemm_mx.hip, whose bytes and exponents equal the reference's."""
+    if not _gpu(x):
+        return ref.mxfp8_quant(x)
+    M, K = x.shape
+    xq = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    xe = torch.empty(M, K // 32, dtype=torch.uint8, device=x.device)
+    ext().act_quant_mxfp8(x, xq, xe)
+    return xq, xe.view(torch.float8_e8m0fnu)
+
+
 def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bool = False,
-                 scale: torch.Tensor | None = None) -> torch.Tensor:
+                 scale: torch.Tensor | None = None, act: str = "bf16") -> torch.Tensor:
     """y = x @ W^T for any number of rows from the wave-tiled weight (prefill-sized steps of a model that lives in its
     tiles alone): bf16 [M, N] for one split, or with ``glu`` (GLU-tiled gate_up, never split) the activated
     silu(gate) * up [M, N/2]; else the fp32 split-K slabs [S, M, N], split s the K range [s K / S, (s + 1) K / S).
     Tiles of every format: fp8 ones need their row scales ``scale``, MXFP4 ones their e8m0 block-scale image; the kernel
     dequantises next to its MFMAs, with the plan, outputs and bits of the same call on the bf16 tiles of the
-    dequantised weight. N % 64 == 0 and K % 256 == 0 (``tile_gemm_supported``)."""
+    dequantised weight. N % 64 == 0 and K % 256 == 0 (``tile_gemm_supported``).
+    ``act="mxfp8"`` (MXFP4 tiles only): x is quantised by ``mxfp8_quant`` and the product runs on the scaled fp8 x fp4
+    MFMA (csrc/tile_gemm_mx.hip) with both block scales as the instruction's operands; plan, output shapes and slab
+    contract are unchanged. On CPU tensors it is ``mxfp8_dequant(mxfp8_quant(x))`` times the dequantised weight."""
     M, K = x.shape
     f = WEIGHT_FORMATS.get(wt.dtype)
     if f is None:
         raise ValueError(f"linear_tiles: no weight tile format has dtype {wt.dtype}")
+    if act not in ACT_DTYPES:
+        raise ValueError(f"linear_tiles: act must be {', '.join(ACT_DTYPES)}, not {act!r}")
+    mx = act == "mxfp8"
+    if mx and f.name != "mxfp4":
+        raise ValueError(f"linear_tiles: act='mxfp8' needs mxfp4 weight tiles, not {f.name} ones")
     if f.scale_dtype is None:
         if scale is not None:
             raise ValueError(f"linear_tiles: {f.name} weight tiles take no scale")
@@ -764,10 +789,14 @@ def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bo
             p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
         if f.raw:
             wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
-        ext().tile_gemm(x, wt, y, p, int(S), bool(glu), scale, f.abi)
+        if mx:
+            xq, xe = mxfp8_quant(x)
+            ext().tile_gemm_mx(xq, xe.view(torch.uint8), wt, scale, y, p, int(S), bool(glu))
+        else:
+            ext().tile_gemm(x, wt, y, p, int(S), bool(glu), scale, f.abi)
         return y if S == 1 else p
     w = f.untile(wt, scale, glu).float()
-    xf = x.float()
+    xf = ref.mxfp8_dequant(*ref.mxfp8_quant(x)) if mx else x.float()
     if S == 1:
         y = xf @ w.t()
         return (ref.silu_mul(y) if glu else y).to(x.dtype)

@@ -311,6 +311,19 @@ int kafka_tile_gemm_plan(int M, int N, int K, int max_splits, int* splits);
 hipError_t kafka_launch_tile_gemm(const bf16* X, int64_t ldx, int wfmt, const void* Wt, const void* scale, int M, int N,
                                   int K, int splits, int glu, bf16* Y, int64_t ldy, float* P, hipStream_t st);
 
+// ---- tile_gemm_mx.hip
+// MXFP8 quantiser of the activations: X bf16 [M, K] with row stride ldx -> Xq e4m3 bytes [M, K] in natural K order and
+// Xe e8m0 bytes [M, K/32], both contiguous (the rule: ops.reference.mxfp8_quant). hipErrorInvalidValue for M < 1,
+// K % 256 != 0, ldx % 8 != 0 or ldx < K, and null pointers.
+hipError_t kafka_launch_act_quant_mxfp8(const bf16* X, int64_t ldx, int M, int K, uint8_t* Xq, uint8_t* Xe,
+                                        hipStream_t st);
+// Y = Xq . W^T on the scaled fp8 x fp4 MFMA (see tile_gemm_mx_kernel): Xq / Xe as the quantiser leaves them (row stride
+// ldxq % 16 == 0), Wt4 / Se the WF_MXFP4 tiles and their block-scale image. M, N, K, splits, glu, Y, ldy and P as for
+// kafka_launch_tile_gemm, with its refusals.
+hipError_t kafka_launch_tile_gemm_mx(const uint8_t* Xq, int64_t ldxq, const uint8_t* Xe, const void* Wt4, const void* Se,
+                                     int M, int N, int K, int splits, int glu, bf16* Y, int64_t ldy, float* P,
+                                     hipStream_t st);
+
 // ---- moe.hip
 hipError_t kafka_launch_moe_route(const bf16* logits, int64_t ld, int T, int E, int K, int BM, float* topk_w,
                                   int* topk_e, int* perm_tok, float* perm_w, int* expert_off, int* tile_off,

@@ -36,6 +36,7 @@
 //     ordinary vector stores: plain bf16 a whole 128-B line per row and wave, GLU 64 B, slabs 256 B.
 // Registers and occupancy per instantiation: profiles/tile_prefill/resource_usage.txt.
 #include "common.h"
+#include "tile_epilogue.h"  // EPI_*, tile_epilogue, dma16 / dma4 (shared with tile_gemm_mx.hip)
 
 namespace kafka {
 
@@ -43,7 +44,6 @@ namespace tlg {
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int NW = 8;                // waves
 constexpr int NT_B = BN / 32;        // column tiles of a block
-enum { EPI_PLAIN = 0, EPI_GLU = 1, EPI_SLAB = 2 };
 template <int WF>
 struct Cfg {
   static constexpr bool WQ = WF != WF_BF16;
@@ -73,13 +73,6 @@ struct Scale<WF_MXFP4> {
   typedef const char* type;   // Se [N/32][K/64][32][2] e8m0 bytes
 };
 
-typedef __attribute__((address_space(3))) void lds_t;
-__device__ __forceinline__ void dma16(const void* g, char* lds) {
-  __builtin_amdgcn_global_load_lds(g, (lds_t*)lds, 16, 0, 0);
-}
-__device__ __forceinline__ void dma4(const void* g, char* lds) {
-  __builtin_amdgcn_global_load_lds(g, (lds_t*)lds, 4, 0, 0);
-}
 }  // namespace tlg
 
 // rts: row tiles of the grid (blockIdx.x = cb * rts + row tile); kper: K columns of one split (a multiple of 256)
@@ -223,63 +216,11 @@ __global__ __launch_bounds__(512, 1) void tile_gemm_kernel(const bf16* __restric
     }
   }
 
-  // epilogues. C lane layout (lanes along N): acc[a][b][i] -> row 128 rh + 32 a + (i & 3) + 8 (i >> 2) + 4 h of the
-  // tile, column (NT_B cb + 2 cg + b) * 32 + r. Each 32-row group a goes through the wave's own 8 KB LDS tile (the ring
-  // is dead once every wave is past its last stage; one wave's LDS accesses complete in order, so its reads see its
-  // writes and the next group's writes follow the reads)
+  // epilogues (tile_epilogue.h): each wave through its own 8 KB LDS tile once the ring is dead
   __syncthreads();
   if (2 * cg >= nbt) return;  // wave-uniform: the column group lies past N
-  char* tp = smem + w * 8192;
-  const int mw = 128 * rh;          // the wave's first row of the tile
-  const int nw = cb * BN + 64 * cg;  // its first column of W
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    if constexpr (EPI == EPI_GLU) {
-      // (gate, up) = (tile 2 cg, 2 cg + 1): 32 output columns at nw / 2; [32 rows][32] bf16, 4 lanes a row
-      bf16* t = reinterpret_cast<bf16*>(tp);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float g = acc[a][0][i], u = acc[a][1][i];
-        t[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = (bf16)(g / (1.0f + __expf(-g)) * u);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int qi = j * 64 + lane, row = qi >> 2, c8 = qi & 3;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(t + row * 32 + 8 * c8);
-        const int m = mw + 32 * a + row;
-        if (m < rows) store_bf16x8(Y + (int64_t)(row0 + m) * ldy + (nw >> 1) + 8 * c8, v);
-      }
-    } else if constexpr (EPI == EPI_PLAIN) {
-      // [32 rows][64] bf16, 8 lanes a row: one 128-B line per row
-      bf16* t = reinterpret_cast<bf16*>(tp);
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) t[((i & 3) + 8 * (i >> 2) + 4 * h) * 64 + 32 * b + r] = (bf16)acc[a][b][i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int qi = j * 64 + lane, row = qi >> 3, c8 = qi & 7;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(t + row * 64 + 8 * c8);
-        const int m = mw + 32 * a + row;
-        if (m < rows) store_bf16x8(Y + (int64_t)(row0 + m) * ldy + nw + 8 * c8, v);
-      }
-    } else {
-      // [32 rows][64] fp32, 16 lanes a row, into this split's slab
-      float* t = reinterpret_cast<float*>(tp);
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) t[((i & 3) + 8 * (i >> 2) + 4 * h) * 64 + 32 * b + r] = acc[a][b][i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int qi = j * 64 + lane, row = qi >> 4, c4 = qi & 15;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(t + row * 64 + 4 * c4);
-        const int m = mw + 32 * a + row;
-        if (m < rows)
-          *reinterpret_cast<f32x4*>(P + ((int64_t)blockIdx.y * M + row0 + m) * N + nw + 4 * c4) = v;
-      }
-    }
-  }
+  // the wave's first row of the tile / its first column of W
+  tile_epilogue<EPI>(acc, smem + w * 8192, lane, 128 * rh, cb * BN + 64 * cg, row0, rows, M, N, blockIdx.y, Y, ldy, P);
 }
 
 // Split plan (mirrored by ops.tile_gemm_plan): S doubles (S <= 8 and <= max_splits, K / S a multiple of 256) while the

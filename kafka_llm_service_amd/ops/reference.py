@@ -164,6 +164,31 @@ def mxfp4_dequant(codes: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
     return torch.ldexp(v, (e.int() - 127)[..., None]).reshape(N, -1)
 
 
+def mxfp8_quant(x: torch.Tensor):
+    """Activations [M, K] (K % 32 == 0) -> (xq uint8 [M, K], xe float8_e8m0fnu [M, K/32]): MXFP8, OCP e4m3fn elements in
+    32-column blocks along K with one e8m0 exponent per (row, block). ``fp8_quant``'s rule per block, so nothing clips:
+    e = the frexp exponent of amax / 448 (amax / 2^e lies in [224, 448)), stored biased by 127 and clamped to the MXFP4
+    image's range [7, 247] (127 for an all-zero block); elements x / 2^e rounded to nearest-even."""
+    M, K = x.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"mxfp8_quant: K={K} must be a multiple of {MXFP4_BLOCK}")
+    xb = x.float().reshape(M, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = xb.abs().amax(-1)
+    _, e = torch.frexp(amax / FP8_MAX)
+    e = torch.where(amax > 0, e + 127, torch.full_like(e, 127)).clamp(MXFP4_EXP_MIN, MXFP4_EXP_MAX)
+    y = torch.ldexp(xb, (127 - e)[..., None]).clamp(-FP8_MAX, FP8_MAX)
+    return (y.to(torch.float8_e4m3fn).view(torch.uint8).reshape(M, K),
+            e.to(torch.uint8).view(torch.float8_e8m0fnu))
+
+
+def mxfp8_dequant(xq: torch.Tensor, xe: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(xq, xe) of ``mxfp8_quant`` -> the values e4m3 * 2^(e - 127), [M, K] in fp32 (or float64), where they are
+    exact (bf16 would round: e4m3 has 3 mantissa bits, but the blocks' exponents differ)."""
+    M, K = xq.shape
+    v = xq.view(torch.float8_e4m3fn).to(dtype).reshape(M, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    return torch.ldexp(v, (xe.view(torch.uint8).int() - 127)[..., None]).reshape(M, K)
+
+
 def _glu_tiles(t: torch.Tensor, inverse: bool = False) -> torch.Tensor:
     """Tile rows [N/32, ...] between natural order and the gate_0, up_0, gate_1, ... interleave of ``tile_weight``."""
     nb = t.shape[0]
