@@ -12,6 +12,9 @@ effective TB/s over the bytes actually streamed (tiles + scales of the experts w
 
 ``--tiles-only`` times prefill-sized steps (T = 1024 .. 8192) on the grouped tile GEMM (ops.grouped_tiles_*, the tiles of
 ``--weight-dtype``) beside ops.grouped_gemm + silu_mul on the dequantised row-major experts, two interleaved rounds.
+With ``--weight-dtype mxfp4 --act-dtype mxfp8`` it times instead the MXFP8-activation layer on the grouped scaled-MFMA
+kernel (csrc/grouped_tile_gemm_mx.hip, quantiser launch included) beside the bf16-MFMA grouped tile kernel and beside
+itself with ``quant_out`` off.
 
 ``--fused-router`` times the router alone — ``ops.moe_gate_route`` (one launch) beside ``F.linear`` + ``ops.moe_route``
 (two) — and the whole layer with either router (the streaming kernel up to T = 640, the LDS-tiled grouped GEMM above),
@@ -86,7 +89,8 @@ def compare(Ts, fmts, dev, E, K, d, F, router, w13, w2, iters=20, rounds=5):
 def tiles_only(Ts, wd, dev, E, K, d, F, router, w13, w2, rounds=2):
     """Prefill-sized steps: the layer on the grouped tile GEMM (ops.grouped_tiles_*, the experts' tiles of format ``wd``)
     beside ops.grouped_gemm + silu_mul on the dequantised row-major experts, interleaved round by round; every round's
-    us per layer is printed, with the achieved TFLOP/s of the medians. Also the largest output difference of the two."""
+    us per layer is printed, with the achieved TFLOP/s of the medians. Also the largest output difference of the two.
+    (``--act-dtype mxfp8``: tiles_act_mx below instead.)"""
     (w13t, w13s), (w2t, w2s) = ops.tile_experts_as(w13, wd, True), ops.tile_experts_as(w2, wd)
     if w13s is not None:
         w13, w2 = ops.untile_experts_as(w13t, w13s, True), ops.untile_experts_as(w2t, w2s)
@@ -121,6 +125,39 @@ def tiles_only(Ts, wd, dev, E, K, d, F, router, w13, w2, rounds=2):
                           "max_rel_diff": round(diff, 5)}), flush=True)
 
 
+def tiles_act_mx(Ts, dev, E, K, d, F, router, w13, w2, rounds=2):
+    """Prefill-sized steps on the MXFP4 expert tiles, three layers interleaved round by round: ``mx`` = MXFP8 activations
+    on the grouped scaled-MFMA kernel with the quantising GLU epilogue (ops.grouped_tiles_*(act="mxfp8"), the quantiser's
+    launch included), ``tiles`` = the bf16-MFMA grouped tile kernel, ``mx_bf16_mid`` = ``mx`` with ``quant_out`` off (a
+    bf16 intermediate and a second quantiser launch: what the fused epilogue buys). Every round's us is printed."""
+    (w13t, w13s), (w2t, w2s) = ops.tile_experts_as(w13, "mxfp4", True), ops.tile_experts_as(w2, "mxfp4")
+    del w13, w2
+    for T in Ts:
+        x = torch.randn(T, d, device=dev, dtype=torch.bfloat16)
+
+        def layer(act, quant_out):
+            r = ops.moe_route(torch.nn.functional.linear(x, router), K)
+            a = ops.grouped_tiles_glu(x, w13t, r, scale=w13s, act=act, quant_out=quant_out)
+            out = torch.zeros(T, d, dtype=torch.float32, device=dev)
+            return ops.grouped_tiles_combine(a, w2t, r, T, out, scale=w2s, act=act)
+
+        paths = {"mx": lambda: layer("mxfp8", True), "tiles": lambda: layer("bf16", False),
+                 "mx_bf16_mid": lambda: layer("mxfp8", False)}
+        o_t, o_m = paths["tiles"](), paths["mx"]()
+        diff = float((o_t - o_m).abs().max() / o_t.abs().max())
+        res = {k: [] for k in paths}
+        for _ in range(rounds):
+            for k, fn in paths.items():
+                res[k].append(timeit(fn, iters=10, rounds=3))
+        flop = 2 * T * K * 3 * F * d
+        row = {"weight_dtype": "mxfp4", "act_dtype": "mxfp8", "T": T}
+        for k, v in res.items():
+            row[k + "_us_per_layer"] = [round(u, 1) for u in v]
+            row[k + "_TFLOP/s"] = round(flop / statistics.median(v) / 1e6, 1)
+        row["mx_vs_tiles_max_rel_diff"] = round(diff, 5)
+        print(json.dumps(row), flush=True)
+
+
 def fused_router(Ts, dev, E, K, d, router, layer_of, rounds=2):
     """Router alone and whole layer, fused launch beside F.linear + moe_route, interleaved round by round; every round's
     us is printed. ``layer_of(x, route)`` runs the experts on a routing, or is None (router only)."""
@@ -148,6 +185,9 @@ def main():
     ap.add_argument("--tiles-only", action="store_true",
                     help="prefill sizes (default T = 1024, 2048, 4096, 8192): the grouped tile GEMM on the expert tiles "
                          "of --weight-dtype beside grouped_gemm on the dequantised row-major experts")
+    ap.add_argument("--act-dtype", default="bf16", choices=list(ops.ACT_DTYPES),
+                    help="with --tiles-only --weight-dtype mxfp4: mxfp8 times the grouped scaled-MFMA kernel beside the "
+                         "bf16-MFMA grouped tile kernel and beside itself without the quantising epilogue")
     ap.add_argument("--fused-router", action="store_true",
                     help="the router alone and the whole layer: ops.moe_gate_route beside F.linear + ops.moe_route "
                          "(default T = 1, 16, 64, 128, 256, 640, 2048, 8192)")
@@ -173,6 +213,10 @@ def main():
         if any(T > 512 for T in Ts):
             ap.error("--compare times the streaming kernel: T <= 512")
         return compare(Ts, fmts, dev, E, K, d, F, router, w13, w2)
+    if args.act_dtype == "mxfp8":
+        if not (args.tiles_only and wd == "mxfp4"):
+            ap.error("--act-dtype mxfp8 needs --tiles-only --weight-dtype mxfp4")
+        return tiles_act_mx(Ts, dev, E, K, d, F, router, w13, w2)
     if args.tiles_only:
         return tiles_only(Ts, wd, dev, E, K, d, F, router, w13, w2)
     # (tiles, scales or None) in the grouped weight-streaming layout; quantised: w13 / w2 become the dequantised experts

@@ -84,7 +84,9 @@ class EngineConfig:
     # activations of the dense tile GEMM: "bf16", or "mxfp8" = the layer projections of steps above 256 rows quantise
     # their input to MXFP8 (e4m3, one e8m0 exponent per 32 columns) and run on the scaled fp8 x fp4 MFMA
     # (csrc/tile_gemm_mx.hip). Needs weight_dtype "mxfp4" and tile_prefill; the lm_head and decode-sized steps keep bf16
-    # activations, so prefill and decode rows differ in numerics; env KAFKA_ACT_DTYPE overrides
+    # activations, so prefill and decode rows differ in numerics. With expert_tiles_only in tile_prefill's place it is the
+    # expert MLPs of steps above MOE_STREAM_MAX_T that run on MXFP8 activations (csrc/grouped_tile_gemm_mx.hip), the
+    # intermediate between their halves included; env KAFKA_ACT_DTYPE overrides
     act_dtype: str = "bf16"             # bf16 | mxfp8
     # MoE models: every layer's routing (router GEMM + softmax / top-k + expert sort) from the one launch of
     # ops.moe_gate_route (csrc/moe_router.hip) instead of F.linear + ops.moe_route; env KAFKA_FUSED_ROUTER=1 overrides
@@ -191,9 +193,10 @@ class LLMEngine:
         adt = os.environ.get("KAFKA_ACT_DTYPE") or cfg.act_dtype
         if adt not in ("bf16", "mxfp8"):
             raise ValueError(f"act_dtype must be bf16 or mxfp8, not {adt!r}")
-        if adt == "mxfp8" and not (wdt == "mxfp4" and tpf):
-            raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill (the scaled MFMA reads the "
-                             f"MXFP4 tiles), not weight_dtype={wdt!r}, tile_prefill={tpf}")
+        if adt == "mxfp8" and not (wdt == "mxfp4" and (tpf or eto)):
+            raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill or expert_tiles_only (the "
+                             f"scaled MFMA reads the MXFP4 tiles), not weight_dtype={wdt!r}, tile_prefill={tpf}, "
+                             f"expert_tiles_only={eto}")
         if self.model.stream and getattr(self.model, "act_dtype", "bf16") != adt:
             raise ValueError(f"the model's act_dtype is {getattr(self.model, 'act_dtype', 'bf16')}, the engine asks for {adt}")
         cfg.act_dtype = adt
@@ -207,7 +210,7 @@ class LLMEngine:
             free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else max(need, 1) * 4
             if need <= 0.5 * free:
                 # before the KV pool is sized from the free memory
-                self.model.enable_stream_weights(weight_dtype=wdt, expert_tiles_only=eto)
+                self.model.enable_stream_weights(weight_dtype=wdt, expert_tiles_only=eto, act_dtype=adt)
             elif eto:
                 raise ValueError(f"expert_tiles_only: the tiled copies need {need / 1e9:.1f} GB more than the row-major "
                                  f"experts they replace, {free / 1e9:.1f} GB are free")

@@ -242,12 +242,16 @@ class TransformerLM:
         ``ops.linear_tiles`` (qkv, o, gate_up, down on steps above 256 rows) quantise their input to MXFP8 — e4m3 in
         32-column blocks with an e8m0 exponent each — and run on the scaled fp8 x fp4 MFMA (csrc/tile_gemm_mx.hip).
         The lm_head and the streamed / skinny steps keep bf16 activations, so the model's numerics then differ by step
-        size: prefill rows see quantised activations, decode rows do not."""
+        size: prefill rows see quantised activations, decode rows do not. With ``expert_tiles_only`` instead of
+        ``tile_prefill`` the mode covers the experts: steps above ``moe.MOE_STREAM_MAX_T`` quantise the MoE block's input
+        once and run both expert halves on the grouped scaled-MFMA kernel (csrc/grouped_tile_gemm_mx.hip), whose GLU
+        epilogue emits MXFP8 for the down half; smaller steps keep the streaming kernel and bf16 activations."""
         if act_dtype not in ops.ACT_DTYPES:
             raise ValueError(f"act_dtype must be {', '.join(ops.ACT_DTYPES)}, not {act_dtype!r}")
-        if act_dtype == "mxfp8" and not (weight_dtype == "mxfp4" and tile_prefill):
-            raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill (the scaled MFMA reads the "
-                             f"MXFP4 tiles), not weight_dtype={weight_dtype!r}, tile_prefill={tile_prefill}")
+        if act_dtype == "mxfp8" and not (weight_dtype == "mxfp4" and (tile_prefill or expert_tiles_only)):
+            raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill or expert_tiles_only (the "
+                             f"scaled MFMA reads the MXFP4 tiles), not weight_dtype={weight_dtype!r}, "
+                             f"tile_prefill={tile_prefill}, expert_tiles_only={expert_tiles_only}")
         if tile_prefill:
             if expert_tiles_only:
                 raise ValueError("tile_prefill together with expert_tiles_only is not supported")

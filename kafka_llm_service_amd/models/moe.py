@@ -20,7 +20,10 @@ tiles with their e8m0 block-scale images in the same slots (4.25 / 16 of the byt
 
 An expert-tiles-only model (``enable_stream_weights(expert_tiles_only=True)``: ``w13`` / ``w2`` are None) has no
 row-major experts: its larger steps run ``ops.grouped_tiles_glu`` / ``ops.grouped_tiles_combine``
-(csrc/grouped_tile_gemm.hip), a compute-oriented grouped MFMA GEMM on the same tiles of any format.
+(csrc/grouped_tile_gemm.hip), a compute-oriented grouped MFMA GEMM on the same tiles of any format. With
+``act_dtype="mxfp8"`` (MXFP4 tiles) those steps quantise the layer input to MXFP8 once and run both halves on the scaled
+fp8 x fp4 MFMA (csrc/grouped_tile_gemm_mx.hip), the GLU half writing its result as MXFP8 for the down half; steps at or
+below ``MOE_STREAM_MAX_T`` keep the streaming kernel and bf16 activations.
 """
 from __future__ import annotations
 
@@ -82,10 +85,8 @@ class MoEBlock:
             ops.grouped_stream_combine(a, lw.w2_t, r, T, out, e_lo=self.e0, scale=lw.w2_s)
             return self._finish(out, x.dtype)
         if lw.w13 is None:
-            # expert-tiles-only model: prefill-sized steps read the same tiles (csrc/grouped_tile_gemm.hip)
-            a = ops.grouped_tiles_glu(x, lw.w13_t, r, e_lo=self.e0, scale=lw.w13_s)
             out = torch.zeros(T, d, dtype=torch.float32, device=x.device)
-            ops.grouped_tiles_combine(a, lw.w2_t, r, T, out, e_lo=self.e0, scale=lw.w2_s)
+            self._tiles_mlp(x, lw, r, self.e0, out)
             return self._finish(out, x.dtype)
         # gate_up for every (token, expert) entry routed to a local expert, rows gathered from x by the kernel
         h = ops.grouped_gemm(x, lw.w13, r, gather=True, e_lo=self.e0)
@@ -94,6 +95,18 @@ class MoEBlock:
         out = torch.zeros(T, d, dtype=torch.float32, device=x.device)
         ops.grouped_gemm(a, lw.w2, r, gather=False, e_lo=self.e0, combine_out=out)
         return self._finish(out, x.dtype)
+
+    def _tiles_mlp(self, x: torch.Tensor, lw, r, e_lo: int, out: torch.Tensor) -> None:
+        """Expert-tiles-only model, a step above MOE_STREAM_MAX_T: both MLP halves on the expert tiles, added into the
+        zeroed ``out`` f32 [rows of x, d] (csrc/grouped_tile_gemm.hip). With ``model.act_dtype == "mxfp8"`` they run on
+        the scaled fp8 x fp4 MFMA (csrc/grouped_tile_gemm_mx.hip): x is quantised once, the GLU epilogue hands its result
+        on as an MXFP8 pair and the bf16 intermediate [n_ent, F] never exists."""
+        if getattr(self.model, "act_dtype", "bf16") == "mxfp8":
+            a = ops.grouped_tiles_glu(x, lw.w13_t, r, e_lo=e_lo, scale=lw.w13_s, act="mxfp8", quant_out=True)
+            ops.grouped_tiles_combine(a, lw.w2_t, r, x.shape[0], out, e_lo=e_lo, scale=lw.w2_s, act="mxfp8")
+            return
+        a = ops.grouped_tiles_glu(x, lw.w13_t, r, e_lo=e_lo, scale=lw.w13_s)
+        ops.grouped_tiles_combine(a, lw.w2_t, r, x.shape[0], out, e_lo=e_lo, scale=lw.w2_s)
 
     def _finish(self, out: torch.Tensor, dtype) -> torch.Tensor:
         """The fp32 combine buffer [T, d] as the layer's delta, handed on as a one-split slab [1, T, d] (the next add +
@@ -156,9 +169,8 @@ class MoEBlock:
         if self.model.stream and lw.w13_t is not None and rows.shape[0] <= MOE_STREAM_MAX_T:
             a = ops.grouped_stream_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
             ops.grouped_stream_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
-        elif lw.w13 is None:  # expert-tiles-only model
-            a = ops.grouped_tiles_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
-            ops.grouped_tiles_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
+        elif lw.w13 is None:
+            self._tiles_mlp(rows, lw, rr, 0, y)
         else:
             h = ops.grouped_gemm(rows, lw.w13, rr, gather=True, e_lo=0)
             ops.grouped_gemm(ops.silu_mul(h), lw.w2, rr, gather=False, e_lo=0, combine_out=y)
@@ -203,9 +215,8 @@ class MoEBlock:
         if self.model.stream and lw.w13_t is not None and rows.shape[0] <= MOE_STREAM_MAX_T:
             a = ops.grouped_stream_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
             ops.grouped_stream_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
-        elif lw.w13 is None:  # expert-tiles-only model
-            a = ops.grouped_tiles_glu(rows, lw.w13_t, rr, e_lo=0, scale=lw.w13_s)
-            ops.grouped_tiles_combine(a, lw.w2_t, rr, rows.shape[0], y, e_lo=0, scale=lw.w2_s)
+        elif lw.w13 is None:
+            self._tiles_mlp(rows, lw, rr, 0, y)
         else:
             h = ops.grouped_gemm(rows, lw.w13, rr, gather=True, e_lo=0)
             ops.grouped_gemm(ops.silu_mul(h), lw.w2, rr, gather=False, e_lo=0, combine_out=y)

@@ -1133,36 +1133,79 @@ def grouped_stream_combine(a: torch.Tensor, wt: torch.Tensor, r: "MoERouting", T
 GT_BM = 256
 
 
+def _grouped_act(fn: str, f, act: str) -> bool:
+    """Whether a grouped tile call runs with MXFP8 activations (MXFP4 expert tiles only, as ``linear_tiles``)."""
+    if act not in ACT_DTYPES:
+        raise ValueError(f"{fn}: act must be {', '.join(ACT_DTYPES)}, not {act!r}")
+    if act == "mxfp8" and f.name != "mxfp4":
+        raise ValueError(f"{fn}: act='mxfp8' needs mxfp4 weight tiles, not {f.name} ones")
+    return act == "mxfp8"
+
+
 def grouped_tiles_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: int = 0,
-                      scale: torch.Tensor | None = None) -> torch.Tensor:
+                      scale: torch.Tensor | None = None, act: str = "bf16", quant_out: bool = False):
     """``grouped_stream_glu`` for segments of hundreds to thousands of rows per expert: silu(gate) * up for every routed
-    (token, local expert) entry [n_ent, F] on GLU-tiled expert weights of any tile format (``scale`` as there)."""
+    (token, local expert) entry [n_ent, F] on GLU-tiled expert weights of any tile format (``scale`` as there).
+    ``act="mxfp8"`` (MXFP4 tiles only): x [T, K] is quantised ONCE, before the gather, by ``mxfp8_quant`` and the
+    product runs on the scaled fp8 x fp4 MFMA (csrc/grouped_tile_gemm_mx.hip). With ``quant_out`` (needs
+    ``act="mxfp8"``) the epilogue quantises its bf16 result itself and the call returns the pair (aq uint8 [n_ent, F],
+    ae float8_e8m0fnu [n_ent, F/32]) = ``reference.mxfp8_quant`` of the bf16 output bit for bit, which
+    ``grouped_tiles_combine(act="mxfp8")`` takes: no bf16 intermediate is written. On CPU tensors the reference path
+    runs on ``mxfp8_dequant(mxfp8_quant(x))``."""
     f, scale = _expert_format("grouped_tiles_glu", wt, scale)
+    mx = _grouped_act("grouped_tiles_glu", f, act)
     n_ent = r.perm_tok.numel()
     F = wt.shape[1] * 16  # (N / 32 tiles of 32 rows, N = 2 F: every tile format)
-    y = torch.empty(n_ent, F, dtype=x.dtype, device=x.device)
+    if quant_out and not (mx and F % 32 == 0):
+        raise ValueError("grouped_tiles_glu: quant_out needs act='mxfp8' and F % 32 == 0")
     if _gpu(x):
         if f.raw:
             wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
+        y = aq = ae = None
+        if quant_out:
+            aq = torch.empty(n_ent, F, dtype=torch.uint8, device=x.device)
+            ae = torch.empty(n_ent, F // 32, dtype=torch.uint8, device=x.device)
+        else:
+            y = torch.empty(n_ent, F, dtype=x.dtype, device=x.device)
+        if mx:
+            xq, xe = mxfp8_quant(x)
+            ext().grouped_tile_gemm_mx(xq, xe.view(torch.uint8), wt, scale, r.perm_tok, r.perm_w, r.expert_off,
+                                       int(e_lo), True, y, aq, ae, None)
+            return (aq, ae.view(torch.float8_e8m0fnu)) if quant_out else y
         ext().grouped_tile_gemm(x, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), True, y, None)
         return y
+    y = torch.empty(n_ent, F, dtype=x.dtype, device=x.device)
+    if mx:
+        x = ref.mxfp8_dequant(*ref.mxfp8_quant(x))  # (fp32: the exact quantised values)
     h = ref_grouped(x, untile_experts_as(wt, scale, glu=True), r, e_lo, gather=True)
     y.copy_(ref.silu_mul(h))
-    return y
+    return ref.mxfp8_quant(y) if quant_out else y
 
 
-def grouped_tiles_combine(a: torch.Tensor, wt: torch.Tensor, r: "MoERouting", T: int, out: torch.Tensor,
-                          e_lo: int = 0, scale: torch.Tensor | None = None) -> torch.Tensor:
+def grouped_tiles_combine(a, wt: torch.Tensor, r: "MoERouting", T: int, out: torch.Tensor,
+                          e_lo: int = 0, scale: torch.Tensor | None = None, act: str = "bf16") -> torch.Tensor:
     """``grouped_stream_combine`` for prefill-sized steps: out[token] += w * (a[entry] @ W_e^T) over the local experts'
-    entries (out f32 [T, N], zeroed by the caller)."""
+    entries (out f32 [T, N], zeroed by the caller). ``act="mxfp8"`` (MXFP4 tiles only): ``a`` is bf16 [n_ent, K],
+    quantised here by ``mxfp8_quant``, or the pair (aq, ae) of ``grouped_tiles_glu(quant_out=True)``."""
     f, scale = _expert_format("grouped_tiles_combine", wt, scale)
+    mx = _grouped_act("grouped_tiles_combine", f, act)
     if out.shape[0] != T:
         raise ValueError("grouped_tiles_combine: out must have one row per token")
-    if _gpu(a):
+    pair = isinstance(a, (tuple, list))
+    if pair and not mx:
+        raise ValueError("grouped_tiles_combine: an (aq, ae) pair needs act='mxfp8'")
+    if _gpu(out):
         if f.raw:
             wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
+        if mx:
+            aq, ae = a if pair else mxfp8_quant(a)
+            ext().grouped_tile_gemm_mx(aq, ae.view(torch.uint8), wt, scale, r.perm_tok, r.perm_w, r.expert_off,
+                                       int(e_lo), False, None, None, None, out)
+            return out
         ext().grouped_tile_gemm(a, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), False, None, out)
         return out
+    if mx:
+        a = ref.mxfp8_dequant(*(a if pair else ref.mxfp8_quant(a)))
     ref.grouped_gemm(a, untile_experts_as(wt, scale), r.perm_tok, r.perm_w, r.expert_off, e_lo, False, None, out)
     return out
 

@@ -1042,6 +1042,73 @@ static void grouped_tile_gemm(at::Tensor x, at::Tensor wt, c10::optional<at::Ten
                                            ldo, cur_stream()));
 }
 
+// grouped_tile_gemm with MXFP8 activations on the MXFP4 expert tiles (csrc/grouped_tile_gemm_mx.hip): xq uint8 [rows, K]
+// (16-B rows) / xe uint8 [rows, K/32] as act_quant_mxfp8 leaves them, token rows with glu (gathered through perm_tok),
+// one row per routed entry otherwise; wt / scale the expert tiles and their block-scale images as uint8. glu writes y
+// bf16 [n_ent, N/2], or instead of it the MXFP8 pair aq uint8 [n_ent, N/2] / ae uint8 [n_ent, N/64] (contiguous); else
+// the weighted combine adds into out f32 [T, N].
+static void grouped_tile_gemm_mx(at::Tensor xq, at::Tensor xe, at::Tensor wt, at::Tensor scale, at::Tensor perm_tok,
+                                 at::Tensor perm_w, at::Tensor expert_off, int64_t e_lo, bool glu,
+                                 c10::optional<at::Tensor> y, c10::optional<at::Tensor> aq,
+                                 c10::optional<at::Tensor> ae, c10::optional<at::Tensor> out) {
+  const char* fn = "grouped_tile_gemm_mx";
+  CHECK_CUDA(xq); CHECK_DT(xq, at::kByte); CHECK_LASTDIM(xq);
+  TORCH_CHECK(xq.dim() == 2 && xq.stride(0) % 16 == 0, fn, ": xq must be uint8 [rows, K] with 16-B rows");
+  const int vk = check_wfmt(fn, kafka::WF_MXFP4, wt, scale, 1);
+  CHECK_CUDA(perm_tok); CHECK_CUDA(perm_w); CHECK_CUDA(expert_off);
+  CHECK_DT(perm_tok, at::kInt); CHECK_DT(perm_w, at::kFloat); CHECK_DT(expert_off, at::kInt);
+  const int64_t E_local = wt.size(0), N = wt.size(1) * 32, K = wt.size(2) * vk, R = xq.size(0);
+  TORCH_CHECK(xq.size(1) == K, fn, ": K mismatch (xq has K = ", xq.size(1), ", the tiles ", K, ")");
+  TORCH_CHECK(xq.device() == wt.device(), fn, ": xq and wt on different devices");
+  TORCH_CHECK(K % 256 == 0 && N % 64 == 0 && K < (1LL << 31) && N < (1LL << 31), fn,
+              ": needs K % 256 == 0 and N % 64 == 0");
+  CHECK_CUDA(xe); CHECK_DT(xe, at::kByte);
+  TORCH_CHECK(xe.is_contiguous() && xe.dim() == 2 && xe.size(0) == R && xe.size(1) == K / 32 &&
+                  xe.device() == xq.device(), fn, ": xe must be contiguous uint8 [rows, K/32]");
+  const int64_t n_ent = perm_tok.numel();
+  TORCH_CHECK(perm_w.numel() == n_ent && n_ent < (1LL << 31) && perm_tok.is_contiguous() && perm_w.is_contiguous(), fn,
+              ": perm");
+  TORCH_CHECK(expert_off.is_contiguous() && e_lo >= 0 && E_local <= 16 && expert_off.numel() >= e_lo + E_local + 1, fn,
+              ": expert_off too short for the local experts (at most 16)");
+  bf16* yp = nullptr;
+  int64_t ldy = 0, ldo = 0;
+  uint8_t *aqp = nullptr, *aep = nullptr;
+  float* op = nullptr;
+  if (glu) {
+    TORCH_CHECK(!out.has_value() && y.has_value() != aq.has_value() && aq.has_value() == ae.has_value(), fn,
+                ": the GLU half writes either y or the pair (aq, ae)");
+    if (y.has_value()) {
+      CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
+      TORCH_CHECK(y->dim() == 2 && y->size(0) >= n_ent && y->size(1) == N / 2 && y->stride(0) % 8 == 0 &&
+                      y->device() == xq.device(), fn, ": y must be [n_ent, N/2] with 16-B rows");
+      yp = bptr(y.value());
+      ldy = y->stride(0);
+    } else {
+      CHECK_CUDA(aq.value()); CHECK_DT(aq.value(), at::kByte); CHECK_CUDA(ae.value()); CHECK_DT(ae.value(), at::kByte);
+      TORCH_CHECK(aq->is_contiguous() && aq->dim() == 2 && aq->size(0) >= n_ent && aq->size(1) == N / 2 &&
+                      aq->device() == xq.device(), fn, ": aq must be contiguous uint8 [n_ent, N/2]");
+      TORCH_CHECK(ae->is_contiguous() && ae->dim() == 2 && ae->size(0) == aq->size(0) && ae->size(1) == N / 64 &&
+                      ae->device() == xq.device(), fn, ": ae must be contiguous uint8 [n_ent, N/64]");
+      aqp = aq->data_ptr<uint8_t>();
+      aep = ae->data_ptr<uint8_t>();
+    }
+  } else {
+    TORCH_CHECK(out.has_value() && !y.has_value() && !aq.has_value() && !ae.has_value(), fn,
+                ": the combine half adds into out");
+    CHECK_CUDA(out.value()); CHECK_DT(out.value(), at::kFloat); CHECK_LASTDIM(out.value());
+    // (perm_tok < T = out's rows is the router's contract, as for grouped_tile_gemm)
+    TORCH_CHECK(out->dim() == 2 && out->size(1) == N && R >= n_ent && out->device() == xq.device(), fn,
+                ": out must be [T, N] and xq hold one row per routed entry");
+    op = out->data_ptr<float>();
+    ldo = out->stride(0);
+  }
+  CHECK_HIP(kafka_launch_grouped_tile_gemm_mx(xq.data_ptr<uint8_t>(), xq.stride(0), xe.data_ptr<uint8_t>(),
+                                              wt.data_ptr(), scale.data_ptr(), (int)E_local, (int)N, (int)K,
+                                              perm_tok.data_ptr<int>(), perm_w.data_ptr<float>(),
+                                              expert_off.data_ptr<int>(), (int)e_lo, (int)n_ent, glu ? 1 : 0, yp, ldy,
+                                              aqp, aep, op, ldo, cur_stream()));
+}
+
 // y [M, N] bf16 = sum over the slabs p [S, M, N]
 static void slab_reduce(at::Tensor p, at::Tensor y) {
   CHECK_CUDA(p); CHECK_DT(p, at::kFloat); CHECK_DT(y, at::kBFloat16); CHECK_LASTDIM(y);
@@ -1403,6 +1470,9 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("grouped_tile_gemm", &grouped_tile_gemm, py::arg("x"), py::arg("wt"), py::arg("scale"), py::arg("fmt"),
         py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("glu"), py::arg("y"),
         py::arg("out"));
+  m.def("grouped_tile_gemm_mx", &grouped_tile_gemm_mx, py::arg("xq"), py::arg("xe"), py::arg("wt"), py::arg("scale"),
+        py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("glu"), py::arg("y"),
+        py::arg("aq"), py::arg("ae"), py::arg("out"));
   m.def("moe_route", &moe_route);
   m.def("moe_gate_route_plan", &moe_gate_route_plan);
   m.def("moe_gate_route", &moe_gate_route);

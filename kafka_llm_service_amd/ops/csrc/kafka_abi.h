@@ -324,6 +324,19 @@ hipError_t kafka_launch_tile_gemm_mx(const uint8_t* Xq, int64_t ldxq, const uint
                                      int M, int N, int K, int splits, int glu, bf16* Y, int64_t ldy, float* P,
                                      hipStream_t st);
 
+// ---- grouped_tile_gemm_mx.hip
+// kafka_launch_grouped_tile_gemm on the scaled fp8 x fp4 MFMA (see grouped_tile_gemm_mx_kernel): Xq / Xe MXFP8 rows as
+// the quantiser leaves them (row stride ldxq % 16 == 0; token rows with glu, one row per routed entry otherwise), Wt4 /
+// Se the WF_MXFP4 expert tiles and their block-scale images. glu writes Y bf16 [n_ent, N/2] or, where Aq / Ae are given
+// instead of Y, the MXFP8 form of the same rows (Aq e4m3 [n_ent, N/2], Ae e8m0 [n_ent, N/64], contiguous); else the
+// weighted combine into out. hipErrorInvalidValue for ldxq % 16 != 0, null pointers, e_local > 16, N % 64 != 0 and
+// K % 256 != 0; a no-op for n_ent < 1.
+hipError_t kafka_launch_grouped_tile_gemm_mx(const uint8_t* Xq, int64_t ldxq, const uint8_t* Xe, const void* Wt4,
+                                             const void* Se, int e_local, int N, int K, const int* perm_tok,
+                                             const float* perm_w, const int* expert_off, int e_lo, int n_ent, int glu,
+                                             bf16* Y, int64_t ldy, uint8_t* Aq, uint8_t* Ae, float* out, int64_t ldo,
+                                             hipStream_t st);
+
 // ---- moe.hip
 hipError_t kafka_launch_moe_route(const bf16* logits, int64_t ld, int T, int E, int K, int BM, float* topk_w,
                                   int* topk_e, int* perm_tok, float* perm_w, int* expert_off, int* tile_off,

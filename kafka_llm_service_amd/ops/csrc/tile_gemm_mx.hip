@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mx_quant.h"
 #include "tile_epilogue.h"
 
 namespace kafka {
@@ -194,26 +195,8 @@ __global__ __launch_bounds__(256) void act_quant_mxfp8_kernel(const bf16* __rest
   const int lane = threadIdx.x & 63;
   u32x4 raw = {0, 0, 0, 0};
   if (live) raw = *reinterpret_cast<const u32x4*>(X + row * ldx + 8 * c);
-  uint32_t am = 0;  // the largest |x| as a bf16 bit pattern
-#pragma unroll
-  for (int j = 0; j < 4; ++j) am = max(am, max(raw[j] & 0x7fffu, (raw[j] >> 16) & 0x7fffu));
-  am = max(am, (uint32_t)__shfl_xor((int)am, 1, 64));
-  am = max(am, (uint32_t)__shfl_xor((int)am, 2, 64));
-  // amax = 1.f * 2^(E - 127): amax / 448 = (1.f / 1.75) * 2^(E - 135), whose frexp exponent is E - 135 + (1.f >= 1.75)
-  int eb = am == 0 ? 127 : (int)(am >> 7) - 8 + ((am & 0x7f) >= 0x60 ? 1 : 0);
-  eb = min(max(eb, 7), 247);
-  const float sc = __uint_as_float((uint32_t)eb << 23);
-  typedef short i16x2 __attribute__((ext_vector_type(2)));
   uint32_t o[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const float f0 = __uint_as_float(raw[2 * j] << 16), f1 = __uint_as_float(raw[2 * j] & 0xffff0000u);
-    const float f2 = __uint_as_float(raw[2 * j + 1] << 16), f3 = __uint_as_float(raw[2 * j + 1] & 0xffff0000u);
-    i16x2 v = {0, 0};
-    v = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(v, f0, f1, sc, false);
-    v = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(v, f2, f3, sc, true);
-    o[j] = __builtin_bit_cast(uint32_t, v);
-  }
+  const int eb = mxfp8_quant_lane(raw, o);  // (mx_quant.h: the block's amax over its 4 lanes, exponent rule, e4m3 bytes)
   // the 8 exponents of the half-wave's 256 columns: a dword per 16 lanes, then the pair
   uint32_t ev = (lane & 3) == 0 ? (uint32_t)eb << (8 * ((lane >> 2) & 3)) : 0u;
   ev |= (uint32_t)__shfl_xor((int)ev, 4, 64);

@@ -908,14 +908,15 @@ def moe_route(logits: torch.Tensor, k: int, bm: int = 64):
 def grouped_gemm(x, w, perm_tok, perm_w, expert_off, e_lo, gather, y, out):
     e_n = w.shape[0]
     eo = expert_off.tolist()
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32  # (float64 inputs: a float64 product)
     for j in range(e_n):
         a, b = eo[e_lo + j], eo[e_lo + j + 1]
         if a == b:
             continue
         rows = x[perm_tok[a:b].long()] if gather else x[a:b]
-        yy = rows.float() @ w[j].float().t()
+        yy = rows.to(acc) @ w[j].to(acc).t()
         if out is not None:
-            out.index_add_(0, perm_tok[a:b].long(), yy * perm_w[a:b, None])
+            out.index_add_(0, perm_tok[a:b].long(), (yy * perm_w[a:b, None]).to(out.dtype))
         else:
             y[a:b] = yy.to(y.dtype)
 
