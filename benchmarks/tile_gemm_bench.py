@@ -6,7 +6,9 @@ in every tile format, against yardsticks from outside the code under test:
 Interleaved rounds: every round times all paths of a cell back to back, so a comparison holds only where it has the
 same sign in every round by more than the cell moves between rounds. ``--act-dtype mxfp8`` (MXFP4 tiles only) adds the
 scaled-MFMA path of csrc/tile_gemm_mx.hip: ``mx`` = ops.linear_tiles(act="mxfp8"), the quantiser's launch included,
-``mx_gemm`` = the GEMM alone on activations quantised beforehand, ``quant`` = the quantiser alone. Each timed call of a path reads another copy of
+``mx_gemm`` = the GEMM alone on activations quantised beforehand, ``quant`` = the quantiser alone. ``--act-dtype fp8`` (fp8 tiles only) does the same for the e4m3 x e4m3 path of
+csrc/tile_gemm_f8.hip (``f8``, ``f8_gemm``, ``quant``), beside the bf16-MFMA kernel on the same fp8 tiles (``tiles``) and
+hipBLASLt on the dequantised copy (``blas_copy``). Each timed call of a path reads another copy of
 the weight (>= 600 MB rotated, so the MALL does not serve repeats). One JSON line per (round, cell); TFLOP/s over
 2 M N K."""
 import argparse
@@ -53,8 +55,10 @@ def main():
     ap.add_argument("--act-dtype", default="bf16", choices=ops.ACT_DTYPES)
     args = ap.parse_args()
     mx = args.act_dtype == "mxfp8"
-    if mx:
-        args.formats = "mxfp4"
+    qa = args.act_dtype != "bf16"  # quantised activations: "mx" on the mxfp4 tiles, "f8" on the fp8 tiles
+    tag = "mx" if mx else "f8"
+    if qa:
+        args.formats = ops.ACT_TILES[args.act_dtype]
     if not torch.cuda.is_available():
         raise SystemExit("tile_gemm_bench needs a GPU")
     dev = "cuda"
@@ -79,19 +83,21 @@ def main():
                     paths = {"tiles": lambda i: ops.linear_tiles(x, qs[i % copies][0], glu=glu, scale=qs[i % copies][1]),
                              "blas_copy": lambda i: act(F.linear(x, deqs[i % copies])),
                              "untile_blas": lambda i: act(F.linear(x, ops.untile_weight_as(*qs[i % copies], glu)))}
-                    if mx:
-                        xq, xe = ops.mxfp8_quant(x)
-                        u8 = [(q[0].view(torch.uint8), q[1].view(torch.uint8)) for q in qs]
+                    if qa:
+                        quant = ops.mxfp8_quant if mx else ops.fp8_act_quant
+                        xq, xe = quant(x)
+                        raw = [(q[0].view(torch.uint8), q[1].view(torch.uint8)) for q in qs] if mx else qs
+                        gemm = ops.ext().tile_gemm_mx if mx else ops.ext().tile_gemm_f8
 
-                        def mx_gemm(i):
+                        def q_gemm(i):
                             y = torch.empty(M, N // 2 if glu else N, dtype=x.dtype, device=dev) if S == 1 else None
                             p = torch.empty(S, M, N, dtype=torch.float32, device=dev) if S > 1 else None
-                            ops.ext().tile_gemm_mx(xq, xe.view(torch.uint8), *u8[i % copies], y, p, S, glu)
+                            gemm(xq, xe.view(torch.uint8) if mx else xe, *raw[i % copies], y, p, S, glu)
 
-                        paths = {"tiles": paths["tiles"], "blas_copy": paths["blas_copy"], "mx_gemm": mx_gemm,
-                                 "mx": lambda i: ops.linear_tiles(x, qs[i % copies][0], glu=glu, scale=qs[i % copies][1],
-                                                                  act="mxfp8"),
-                                 "quant": lambda i: ops.mxfp8_quant(x)}
+                        paths = {"tiles": paths["tiles"], "blas_copy": paths["blas_copy"], tag + "_gemm": q_gemm,
+                                 tag: lambda i: ops.linear_tiles(x, qs[i % copies][0], glu=glu, scale=qs[i % copies][1],
+                                                                 act=args.act_dtype),
+                                 "quant": lambda i: quant(x)}
                     elif glu:
                         paths["grouped"] = lambda i: ops.grouped_tiles_glu(
                             x, qs[i % copies][0][None], route, scale=None if qs[i % copies][1] is None

@@ -86,8 +86,12 @@ class EngineConfig:
     # (csrc/tile_gemm_mx.hip). Needs weight_dtype "mxfp4" and tile_prefill; the lm_head and decode-sized steps keep bf16
     # activations, so prefill and decode rows differ in numerics. With expert_tiles_only in tile_prefill's place it is the
     # expert MLPs of steps above MOE_STREAM_MAX_T that run on MXFP8 activations (csrc/grouped_tile_gemm_mx.hip), the
-    # intermediate between their halves included; env KAFKA_ACT_DTYPE overrides
-    act_dtype: str = "bf16"             # bf16 | mxfp8
+    # intermediate between their halves included. "fp8" = the same projections of the same steps quantise their input
+    # per row (e4m3, one power-of-two exponent per row) and run on the e4m3 x e4m3 MFMA (csrc/tile_gemm_f8.hip). Needs
+    # weight_dtype "fp8" and tile_prefill (not expert_tiles_only: the grouped expert kernel has no such path); here
+    # too the lm_head and decode-sized steps keep bf16 activations, so prefill rows and decode rows differ in
+    # numerics. env KAFKA_ACT_DTYPE overrides
+    act_dtype: str = "bf16"             # bf16 | mxfp8 | fp8
     # MoE models: every layer's routing (router GEMM + softmax / top-k + expert sort) from the one launch of
     # ops.moe_gate_route (csrc/moe_router.hip) instead of F.linear + ops.moe_route; env KAFKA_FUSED_ROUTER=1 overrides
     fused_router: bool = False
@@ -191,8 +195,12 @@ class LLMEngine:
             raise ValueError(f"the model's tile_prefill is {self.model.tile_prefill}, the engine asks for {tpf}")
         cfg.tile_prefill = tpf
         adt = os.environ.get("KAFKA_ACT_DTYPE") or cfg.act_dtype
-        if adt not in ("bf16", "mxfp8"):
-            raise ValueError(f"act_dtype must be bf16 or mxfp8, not {adt!r}")
+        if adt not in ops.ACT_DTYPES:
+            raise ValueError(f"act_dtype must be {', '.join(ops.ACT_DTYPES)}, not {adt!r}")
+        if adt == "fp8" and not (wdt == "fp8" and tpf):
+            raise ValueError("act_dtype='fp8' needs weight_dtype='fp8' and tile_prefill (the e4m3 x e4m3 MFMA reads the "
+                             f"fp8 tiles of the dense projections), not weight_dtype={wdt!r}, tile_prefill={tpf}, "
+                             f"expert_tiles_only={eto}")
         if adt == "mxfp8" and not (wdt == "mxfp4" and (tpf or eto)):
             raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill or expert_tiles_only (the "
                              f"scaled MFMA reads the MXFP4 tiles), not weight_dtype={wdt!r}, tile_prefill={tpf}, "
@@ -300,7 +308,7 @@ class LLMEngine:
         log.info("engine ready: %s tp=%d weights %s%s (%.1f GB) kv pages=%d (%s, %.1f GB) load %.1fs", mc.name, cfg.tp,
                  self.model.weight_dtype, ", expert tiles only" if self.model.expert_tiles_only else
                  (", tile prefill" if self.model.tile_prefill else "") +
-                 (", mxfp8 activations" if cfg.act_dtype == "mxfp8" else ""),
+                 (f", {cfg.act_dtype} activations" if cfg.act_dtype != "bf16" else ""),
                  self.model.weight_bytes() / 1e9, nb, cfg.kv_dtype, nb * page_bytes / 1e9, self.load_s)
 
     # ------------------------------------------------------------------------------------------------------------

@@ -245,9 +245,19 @@ class TransformerLM:
         size: prefill rows see quantised activations, decode rows do not. With ``expert_tiles_only`` instead of
         ``tile_prefill`` the mode covers the experts: steps above ``moe.MOE_STREAM_MAX_T`` quantise the MoE block's input
         once and run both expert halves on the grouped scaled-MFMA kernel (csrc/grouped_tile_gemm_mx.hip), whose GLU
-        epilogue emits MXFP8 for the down half; smaller steps keep the streaming kernel and bf16 activations."""
+        epilogue emits MXFP8 for the down half; smaller steps keep the streaming kernel and bf16 activations.
+
+        ``act_dtype="fp8"`` (with ``weight_dtype="fp8"`` and ``tile_prefill``, nothing else): the same projections of the
+        same steps quantise their input per row (``ops.fp8_act_quant``: e4m3, one power-of-two exponent per row) and run
+        on the e4m3 x e4m3 MFMA (csrc/tile_gemm_f8.hip); the lm_head and the streamed / skinny steps keep bf16
+        activations, with the same difference between prefill rows and decode rows. The grouped expert kernel has no
+        such path: ``expert_tiles_only`` is refused."""
         if act_dtype not in ops.ACT_DTYPES:
             raise ValueError(f"act_dtype must be {', '.join(ops.ACT_DTYPES)}, not {act_dtype!r}")
+        if act_dtype == "fp8" and not (weight_dtype == "fp8" and tile_prefill):
+            raise ValueError("act_dtype='fp8' needs weight_dtype='fp8' and tile_prefill (the e4m3 x e4m3 MFMA reads the "
+                             f"fp8 tiles of the dense projections), not weight_dtype={weight_dtype!r}, "
+                             f"tile_prefill={tile_prefill}, expert_tiles_only={expert_tiles_only}")
         if act_dtype == "mxfp8" and not (weight_dtype == "mxfp4" and (tile_prefill or expert_tiles_only)):
             raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill or expert_tiles_only (the "
                              f"scaled MFMA reads the MXFP4 tiles), not weight_dtype={weight_dtype!r}, "

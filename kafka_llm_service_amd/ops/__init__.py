@@ -733,8 +733,26 @@ def tile_gemm_plan(M: int, N: int, K: int, max_splits: int = 8) -> int:
     return s
 
 
-ACT_DTYPES = ("bf16", "mxfp8")  # activations of the dense tile GEMM (EngineConfig.act_dtype)
+ACT_DTYPES = ("bf16", "mxfp8", "fp8")  # activations of the dense tile GEMM (EngineConfig.act_dtype)
+ACT_TILES = {"mxfp8": "mxfp4", "fp8": "fp8"}  # the weight tile format a quantised activation format runs on
 mxfp8_dequant = ref.mxfp8_dequant
+fp8_act_order = ref.fp8_act_order
+
+
+def fp8_act_quant(x: torch.Tensor):
+    """bf16 activations [M, K] -> (xq uint8 [M, K], xe int32 [M]): e4m3 bytes with one power-of-two exponent per row,
+    ``reference.fp8_quant`` over the last dimension (x ~= e4m3(xq) * 2^xe). The bytes are in FP8-TILE K ORDER,
+    ``fp8_act_order`` of the natural one (its own inverse): the order in which the stored fp8 weight tiles hold a row,
+    so the e4m3 x e4m3 MFMA of csrc/tile_gemm_f8.hip reads both operands as they lie. A GPU tensor (16-B aligned rows,
+    K % 256 == 0) runs that unit's HIP quantiser, whose bytes and exponents equal the reference's."""
+    if not _gpu(x):
+        xq, xe = ref.fp8_quant(x)
+        return ref.fp8_act_order(xq), xe
+    M, K = x.shape
+    xq = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    xe = torch.empty(M, dtype=torch.int32, device=x.device)
+    ext().act_quant_fp8(x, xq, xe)
+    return xq, xe
 
 
 def mxfp8_quant(x: torch.Tensor):
@@ -760,7 +778,11 @@ def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bo
     dequantised weight. N % 64 == 0 and K % 256 == 0 (``tile_gemm_supported``).
     ``act="mxfp8"`` (MXFP4 tiles only): x is quantised by ``mxfp8_quant`` and the product runs on the scaled fp8 x fp4
     MFMA (csrc/tile_gemm_mx.hip) with both block scales as the instruction's operands; plan, output shapes and slab
-    contract are unchanged. On CPU tensors it is ``mxfp8_dequant(mxfp8_quant(x))`` times the dequantised weight."""
+    contract are unchanged. On CPU tensors it is ``mxfp8_dequant(mxfp8_quant(x))`` times the dequantised weight.
+    ``act="fp8"`` (fp8 tiles only): x is quantised per row by ``fp8_act_quant`` and the product runs on the e4m3 x e4m3
+    MFMA (csrc/tile_gemm_f8.hip), the row exponents and the weights' row scales applied to the fp32 accumulators; same
+    plan, shapes and slab contract. On CPU tensors it is the dequantised ``reference.fp8_quant(x)`` times the
+    dequantised weight."""
     M, K = x.shape
     f = WEIGHT_FORMATS.get(wt.dtype)
     if f is None:
@@ -768,8 +790,8 @@ def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bo
     if act not in ACT_DTYPES:
         raise ValueError(f"linear_tiles: act must be {', '.join(ACT_DTYPES)}, not {act!r}")
     mx = act == "mxfp8"
-    if mx and f.name != "mxfp4":
-        raise ValueError(f"linear_tiles: act='mxfp8' needs mxfp4 weight tiles, not {f.name} ones")
+    if act in ACT_TILES and f.name != ACT_TILES[act]:
+        raise ValueError(f"linear_tiles: act={act!r} needs {ACT_TILES[act]} weight tiles, not {f.name} ones")
     if f.scale_dtype is None:
         if scale is not None:
             raise ValueError(f"linear_tiles: {f.name} weight tiles take no scale")
@@ -792,11 +814,18 @@ def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bo
         if mx:
             xq, xe = mxfp8_quant(x)
             ext().tile_gemm_mx(xq, xe.view(torch.uint8), wt, scale, y, p, int(S), bool(glu))
+        elif act == "fp8":
+            xq, xe = fp8_act_quant(x)
+            ext().tile_gemm_f8(xq, xe, wt, scale, y, p, int(S), bool(glu))
         else:
             ext().tile_gemm(x, wt, y, p, int(S), bool(glu), scale, f.abi)
         return y if S == 1 else p
     w = f.untile(wt, scale, glu).float()
-    xf = ref.mxfp8_dequant(*ref.mxfp8_quant(x)) if mx else x.float()
+    if act == "fp8":
+        xq, xe = ref.fp8_quant(x)
+        xf = torch.ldexp(xq.view(torch.float8_e4m3fn).float(), xe[:, None])
+    else:
+        xf = ref.mxfp8_dequant(*ref.mxfp8_quant(x)) if mx else x.float()
     if S == 1:
         y = xf @ w.t()
         return (ref.silu_mul(y) if glu else y).to(x.dtype)
@@ -1139,6 +1168,8 @@ def _grouped_act(fn: str, f, act: str) -> bool:
         raise ValueError(f"{fn}: act must be {', '.join(ACT_DTYPES)}, not {act!r}")
     if act == "mxfp8" and f.name != "mxfp4":
         raise ValueError(f"{fn}: act='mxfp8' needs mxfp4 weight tiles, not {f.name} ones")
+    if act == "fp8":
+        raise ValueError(f"{fn}: act='fp8' is not built for the grouped expert kernels (dense linear_tiles only)")
     return act == "mxfp8"
 
 

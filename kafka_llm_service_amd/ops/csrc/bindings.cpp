@@ -929,6 +929,61 @@ static void tile_gemm_mx(at::Tensor xq, at::Tensor xe, at::Tensor wt, at::Tensor
                                       cur_stream()));
 }
 
+// Per-row fp8 quantiser of the activations (csrc/tile_gemm_f8.hip): x bf16 [M, K] with 16-B rows -> xq uint8 [M, K]
+// (e4m3 bytes in fp8-tile K order, ops.fp8_act_order) and xe int32 [M] (one exponent per row), both contiguous
+static void act_quant_fp8(at::Tensor x, at::Tensor xq, at::Tensor xe) {
+  check_stream_x("act_quant_fp8", x);
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && M < (1LL << 31) && K < (1LL << 31) && K % 256 == 0, "act_quant_fp8: needs M >= 1 and K % 256 == 0");
+  CHECK_CUDA(xq); CHECK_DT(xq, at::kByte); CHECK_CUDA(xe); CHECK_DT(xe, at::kInt);
+  TORCH_CHECK(xq.is_contiguous() && xq.dim() == 2 && xq.size(0) == M && xq.size(1) == K && xq.device() == x.device(),
+              "act_quant_fp8: xq must be contiguous uint8 [M, K]");
+  TORCH_CHECK(xe.is_contiguous() && xe.dim() == 1 && xe.size(0) == M && xe.device() == x.device(),
+              "act_quant_fp8: xe must be contiguous int32 [M]");
+  CHECK_HIP(kafka_launch_act_quant_fp8(bptr(x), x.stride(0), (int)M, (int)K, xq.data_ptr<uint8_t>(), xe.data_ptr<int>(),
+                                       cur_stream()));
+}
+
+// Dense tile GEMM with fp8 activations on the fp8 tiles (csrc/tile_gemm_f8.hip): xq / xe as act_quant_fp8 leaves them
+// (xq rows may be strided, 16-B aligned), wt / scale the fp8 tiles and their f32 row scales [N]; y, p, splits and glu
+// as for tile_gemm
+static void tile_gemm_f8(at::Tensor xq, at::Tensor xe, at::Tensor wt, at::Tensor scale, c10::optional<at::Tensor> y,
+                         c10::optional<at::Tensor> p, int64_t splits, bool glu) {
+  CHECK_CUDA(xq); CHECK_DT(xq, at::kByte); CHECK_LASTDIM(xq);
+  TORCH_CHECK(xq.dim() == 2 && xq.stride(0) % 16 == 0, "tile_gemm_f8: xq must be uint8 [M, K] with 16-B rows");
+  const int vk = check_wfmt("tile_gemm_f8", kafka::WF_FP8, wt, scale, 0);
+  const int64_t M = xq.size(0), K = xq.size(1), N = wt.size(0) * 32;
+  TORCH_CHECK(wt.size(1) * vk == K, "tile_gemm_f8: K mismatch (xq has K = ", K, ", the tiles ", wt.size(1) * vk, ")");
+  TORCH_CHECK(xq.device() == wt.device(), "tile_gemm_f8: xq and wt on different devices");
+  TORCH_CHECK(M >= 1 && M < (1LL << 31) && N % 64 == 0 && K % 256 == 0,
+              "tile_gemm_f8: needs M >= 1, N % 64 == 0 and K % 256 == 0");
+  CHECK_CUDA(xe); CHECK_DT(xe, at::kInt);
+  TORCH_CHECK(xe.is_contiguous() && xe.dim() == 1 && xe.size(0) == M && xe.device() == xq.device(),
+              "tile_gemm_f8: xe must be contiguous int32 [M]");
+  TORCH_CHECK(splits >= 1 && splits <= 8 && K % (256 * splits) == 0, "tile_gemm_f8: splits must divide K into multiples of 256");
+  TORCH_CHECK(!glu || splits == 1, "tile_gemm_f8: the GLU epilogue needs one split");
+  bf16* yp = nullptr;
+  int64_t ldy = 0;
+  float* pp = nullptr;
+  if (splits == 1) {
+    TORCH_CHECK(y.has_value(), "tile_gemm_f8: y required for one split");
+    CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == M && y->size(1) == (glu ? N / 2 : N) && y->stride(0) % 8 == 0 &&
+                    y->device() == xq.device(), "tile_gemm_f8: y must be [M, N] (glu: [M, N/2]) with 16-B rows");
+    yp = bptr(y.value());
+    ldy = y->stride(0);
+  } else {
+    TORCH_CHECK(p.has_value(), "tile_gemm_f8: slab output required");
+    CHECK_CUDA(p.value()); CHECK_DT(p.value(), at::kFloat);
+    TORCH_CHECK(p->is_contiguous() && p->dim() == 3 && p->size(0) == splits && p->size(1) == M && p->size(2) == N &&
+                    p->device() == xq.device(), "tile_gemm_f8: slab shape must be [splits, M, N]");
+    pp = p->data_ptr<float>();
+  }
+  CHECK_HIP(kafka_launch_tile_gemm_f8(xq.data_ptr<uint8_t>(), xq.stride(0), xe.data_ptr<int>(), wt.data_ptr(),
+                                      scale.data_ptr<float>(), (int)M, (int)N, (int)K, (int)splits, glu ? 1 : 0, yp, ldy,
+                                      pp, cur_stream()));
+}
+
 // explicit-configuration variant (microbenchmark sweeps): (mt, kc, splits) as given, no planning
 static void wstream_gemm_cfg(at::Tensor x, at::Tensor wt, c10::optional<at::Tensor> y, c10::optional<at::Tensor> p,
                              int64_t mt, int64_t kc, int64_t s, bool nt, int64_t kw, int64_t pin) {
@@ -1466,6 +1521,9 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("gather"), py::arg("y"), py::arg("out"), py::arg("pin") = true);
   m.def("act_quant_mxfp8", &act_quant_mxfp8, py::arg("x"), py::arg("xq"), py::arg("xe"));
   m.def("tile_gemm_mx", &tile_gemm_mx, py::arg("xq"), py::arg("xe"), py::arg("wt"), py::arg("scale"), py::arg("y"),
+        py::arg("p"), py::arg("splits"), py::arg("glu"));
+  m.def("act_quant_fp8", &act_quant_fp8, py::arg("x"), py::arg("xq"), py::arg("xe"));
+  m.def("tile_gemm_f8", &tile_gemm_f8, py::arg("xq"), py::arg("xe"), py::arg("wt"), py::arg("scale"), py::arg("y"),
         py::arg("p"), py::arg("splits"), py::arg("glu"));
   m.def("grouped_tile_gemm", &grouped_tile_gemm, py::arg("x"), py::arg("wt"), py::arg("scale"), py::arg("fmt"),
         py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("glu"), py::arg("y"),

@@ -324,6 +324,19 @@ hipError_t kafka_launch_tile_gemm_mx(const uint8_t* Xq, int64_t ldxq, const uint
                                      int M, int N, int K, int splits, int glu, bf16* Y, int64_t ldy, float* P,
                                      hipStream_t st);
 
+// ---- tile_gemm_f8.hip
+// Per-row fp8 quantiser of the activations: X bf16 [M, K] with row stride ldx -> Xq e4m3 bytes [M, K] in fp8-tile K
+// order (in every 32-byte group the two middle 8-byte runs trade places; ops.fp8_act_order) and Ea int32 [M], one
+// power-of-two exponent per row, both contiguous (the rule: ops.reference.fp8_quant). hipErrorInvalidValue for M < 1,
+// K % 256 != 0, ldx % 8 != 0 or ldx < K, and null pointers.
+hipError_t kafka_launch_act_quant_fp8(const bf16* X, int64_t ldx, int M, int K, uint8_t* Xq, int* Ea, hipStream_t st);
+// Y = (Xq . Wq^T) * 2^Ea[m] * St[n] on the e4m3 x e4m3 MFMA (see tile_gemm_f8_kernel): Xq / Ea as the quantiser leaves
+// them (row stride ldxq % 16 == 0), Wt8 / St the WF_FP8 tiles and their row scales in tile order. M, N, K, splits, glu,
+// Y, ldy and P as for kafka_launch_tile_gemm, with its refusals.
+hipError_t kafka_launch_tile_gemm_f8(const uint8_t* Xq, int64_t ldxq, const int* Ea, const void* Wt8, const float* St,
+                                     int M, int N, int K, int splits, int glu, bf16* Y, int64_t ldy, float* P,
+                                     hipStream_t st);
+
 // ---- grouped_tile_gemm_mx.hip
 // kafka_launch_grouped_tile_gemm on the scaled fp8 x fp4 MFMA (see grouped_tile_gemm_mx_kernel): Xq / Xe MXFP8 rows as
 // the quantiser leaves them (row stride ldxq % 16 == 0; token rows with glu, one row per routed entry otherwise), Wt4 /

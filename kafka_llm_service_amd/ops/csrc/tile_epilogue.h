@@ -1,5 +1,5 @@
-// The three epilogues of the dense tile GEMMs (tile_gemm.hip: bf16 MFMA; tile_gemm_mx.hip: scaled fp8 x fp4 MFMA). Both
-// kernels end with the same picture: 8 waves over a 256 x 256 tile, wave w = row half w & 1 (128 rows) x column group
+// The three epilogues of the dense tile GEMMs (tile_gemm.hip: bf16 MFMA; tile_gemm_mx.hip: scaled fp8 x fp4 MFMA;
+// tile_gemm_f8.hip: fp8 x fp8 MFMA, which scales its accumulators first). The kernels end with the same picture: 8 waves over a 256 x 256 tile, wave w = row half w & 1 (128 rows) x column group
 // w >> 1 (64 columns), a 4 x 2 block of 32 x 32 fp32 accumulators per wave, and an LDS ring that is dead by now.
 #pragma once
 #include "common.h"

@@ -38,8 +38,8 @@
 //     FP8 prologue has the reason).
 // Not built: a dword-granular DMA that would regroup the B blocks on the way in (64 DMA instructions per stage instead
 // of 16); a four-stage ring of 64-deep stages (twice the barriers); 256-deep stages (two would not leave the next
-// stage's DMA a free slot under 160 KB); fp8 weight tiles (their K order per lane differs); the quantiser fused into
-// the producers of X. Registers, LDS and occupancy: profiles/act_mxfp8/resource_usage.txt.
+// stage's DMA a free slot under 160 KB); the quantiser fused into the producers of X. fp8 weight tiles (their K order
+// per lane differs) have their own unit, tile_gemm_f8.hip, which permutes the activations instead. Registers, LDS and occupancy: profiles/act_mxfp8/resource_usage.txt.
 #include <type_traits>
 
 #include "common.h"

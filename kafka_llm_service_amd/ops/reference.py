@@ -68,6 +68,14 @@ def fp8_quant(x: torch.Tensor):
     return y.to(torch.float8_e4m3fn).view(torch.uint8), e
 
 
+def fp8_act_order(xq: torch.Tensor) -> torch.Tensor:
+    """Natural K order <-> the fp8-tile K order of quantised activations [..., K] (K % 32 == 0): in every 32-column
+    group the two middle 8-column runs trade places (columns 0-7, 16-23, 8-15, 24-31), so the 16-B chunk 2 g + h of a
+    row holds what lane (., h) of the stored fp8 weight tile g holds of a weight row (``tile_weight_fp8``). The map is
+    its own inverse."""
+    return xq.reshape(*xq.shape[:-1], -1, 2, 2, 8).transpose(-2, -3).reshape(xq.shape)
+
+
 def tile_weight_fp8(w: torch.Tensor, glu: bool = False):
     """Row-major weight [N, K] -> (wt8 uint8 [N/32, K/32, 64, 16], st fp32 [N]): every row quantised over its whole K
     by ``fp8_quant`` (e4m3 bytes, one power-of-two scale 2^e per row) and laid out for the fp8 weight-streaming GEMM
