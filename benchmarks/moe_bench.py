@@ -14,7 +14,9 @@ effective TB/s over the bytes actually streamed (tiles + scales of the experts w
 ``--weight-dtype``) beside ops.grouped_gemm + silu_mul on the dequantised row-major experts, two interleaved rounds.
 With ``--weight-dtype mxfp4 --act-dtype mxfp8`` it times instead the MXFP8-activation layer on the grouped scaled-MFMA
 kernel (csrc/grouped_tile_gemm_mx.hip, quantiser launch included) beside the bf16-MFMA grouped tile kernel and beside
-itself with ``quant_out`` off.
+itself with ``quant_out`` off. With ``--weight-dtype fp8 --act-dtype fp8`` it times the per-row-fp8-activation layer on
+the grouped e4m3 x e4m3 MFMA kernel (csrc/grouped_tile_gemm_f8.hip, both quantiser launches included) beside the
+bf16-MFMA grouped tile kernel on the same fp8 tiles.
 
 ``--fused-router`` times the router alone — ``ops.moe_gate_route`` (one launch) beside ``F.linear`` + ``ops.moe_route``
 (two) — and the whole layer with either router (the streaming kernel up to T = 640, the LDS-tiled grouped GEMM above),
@@ -158,6 +160,38 @@ def tiles_act_mx(Ts, dev, E, K, d, F, router, w13, w2, rounds=2):
         print(json.dumps(row), flush=True)
 
 
+def tiles_act_f8(Ts, dev, E, K, d, F, router, w13, w2, rounds=2):
+    """Prefill-sized steps on the fp8 expert tiles, two layers interleaved round by round: ``f8`` = per-row fp8
+    activations on the grouped e4m3 x e4m3 MFMA kernel (ops.grouped_tiles_*(act="fp8"): both quantiser launches, of x and
+    of the bf16 intermediate, included), ``tiles`` = the bf16-MFMA grouped tile kernel on the same tiles. Every round's us
+    is printed."""
+    (w13t, w13s), (w2t, w2s) = ops.tile_experts_as(w13, "fp8", True), ops.tile_experts_as(w2, "fp8")
+    del w13, w2
+    for T in Ts:
+        x = torch.randn(T, d, device=dev, dtype=torch.bfloat16)
+
+        def layer(act):
+            r = ops.moe_route(torch.nn.functional.linear(x, router), K)
+            a = ops.grouped_tiles_glu(x, w13t, r, scale=w13s, act=act)
+            out = torch.zeros(T, d, dtype=torch.float32, device=dev)
+            return ops.grouped_tiles_combine(a, w2t, r, T, out, scale=w2s, act=act)
+
+        paths = {"f8": lambda: layer("fp8"), "tiles": lambda: layer("bf16")}
+        o_t, o_f = paths["tiles"](), paths["f8"]()
+        diff = float((o_t - o_f).abs().max() / o_t.abs().max())
+        res = {k: [] for k in paths}
+        for _ in range(rounds):
+            for k, fn in paths.items():
+                res[k].append(timeit(fn, iters=10, rounds=3))
+        flop = 2 * T * K * 3 * F * d
+        row = {"weight_dtype": "fp8", "act_dtype": "fp8", "T": T}
+        for k, v in res.items():
+            row[k + "_us_per_layer"] = [round(u, 1) for u in v]
+            row[k + "_TFLOP/s"] = round(flop / statistics.median(v) / 1e6, 1)
+        row["f8_vs_tiles_max_rel_diff"] = round(diff, 5)
+        print(json.dumps(row), flush=True)
+
+
 def fused_router(Ts, dev, E, K, d, router, layer_of, rounds=2):
     """Router alone and whole layer, fused launch beside F.linear + moe_route, interleaved round by round; every round's
     us is printed. ``layer_of(x, route)`` runs the experts on a routing, or is None (router only)."""
@@ -187,7 +221,9 @@ def main():
                          "of --weight-dtype beside grouped_gemm on the dequantised row-major experts")
     ap.add_argument("--act-dtype", default="bf16", choices=list(ops.ACT_DTYPES),
                     help="with --tiles-only --weight-dtype mxfp4: mxfp8 times the grouped scaled-MFMA kernel beside the "
-                         "bf16-MFMA grouped tile kernel and beside itself without the quantising epilogue")
+                         "bf16-MFMA grouped tile kernel and beside itself without the quantising epilogue; with "
+                         "--tiles-only --weight-dtype fp8: fp8 times the grouped e4m3 x e4m3 MFMA kernel (both "
+                         "quantiser launches included) beside the bf16-MFMA grouped tile kernel on the same tiles")
     ap.add_argument("--fused-router", action="store_true",
                     help="the router alone and the whole layer: ops.moe_gate_route beside F.linear + ops.moe_route "
                          "(default T = 1, 16, 64, 128, 256, 640, 2048, 8192)")
@@ -217,6 +253,10 @@ def main():
         if not (args.tiles_only and wd == "mxfp4"):
             ap.error("--act-dtype mxfp8 needs --tiles-only --weight-dtype mxfp4")
         return tiles_act_mx(Ts, dev, E, K, d, F, router, w13, w2)
+    if args.act_dtype == "fp8":
+        if not (args.tiles_only and wd == "fp8"):
+            ap.error("--act-dtype fp8 needs --tiles-only --weight-dtype fp8")
+        return tiles_act_f8(Ts, dev, E, K, d, F, router, w13, w2)
     if args.tiles_only:
         return tiles_only(Ts, wd, dev, E, K, d, F, router, w13, w2)
     # (tiles, scales or None) in the grouped weight-streaming layout; quantised: w13 / w2 become the dequantised experts

@@ -23,6 +23,7 @@ from kafka_llm_service_amd.engine.model_runner import ModelRunner
 from kafka_llm_service_amd.engine.scheduler import NeedSync, Scheduler, SchedulerConfig
 from kafka_llm_service_amd.engine.sequence import PENDING, SamplingParams, Sequence, StepOutput
 from kafka_llm_service_amd.models.config import ModelConfig, get_config
+from kafka_llm_service_amd.models.llama import ACT_DTYPES as MODEL_ACT_DTYPES
 from kafka_llm_service_amd.models.weights import build_model
 from kafka_llm_service_amd.runtime import KVManager
 from kafka_llm_service_amd.obs import trace
@@ -88,10 +89,14 @@ class EngineConfig:
     # expert MLPs of steps above MOE_STREAM_MAX_T that run on MXFP8 activations (csrc/grouped_tile_gemm_mx.hip), the
     # intermediate between their halves included. "fp8" = the same projections of the same steps quantise their input
     # per row (e4m3, one power-of-two exponent per row) and run on the e4m3 x e4m3 MFMA (csrc/tile_gemm_f8.hip). Needs
-    # weight_dtype "fp8" and tile_prefill (not expert_tiles_only: the grouped expert kernel has no such path); here
+    # weight_dtype "fp8" and tile_prefill (not expert_tiles_only: that mode's value is "fp8_experts", below); here
     # too the lm_head and decode-sized steps keep bf16 activations, so prefill rows and decode rows differ in
-    # numerics. env KAFKA_ACT_DTYPE overrides
-    act_dtype: str = "bf16"             # bf16 | mxfp8 | fp8
+    # numerics. "fp8_experts" = the same per-row format on the experts of a MoE model: needs weight_dtype "fp8" and
+    # expert_tiles_only; the expert MLPs of steps above MOE_STREAM_MAX_T quantise the MoE block's input per row, run the
+    # GLU half on the grouped e4m3 x e4m3 MFMA kernel (csrc/grouped_tile_gemm_f8.hip), quantise its bf16 result per row
+    # again and run the combine half on the same kernel; smaller steps keep the streaming kernel and bf16 activations.
+    # env KAFKA_ACT_DTYPE overrides
+    act_dtype: str = "bf16"             # bf16 | mxfp8 | fp8 | fp8_experts
     # MoE models: every layer's routing (router GEMM + softmax / top-k + expert sort) from the one launch of
     # ops.moe_gate_route (csrc/moe_router.hip) instead of F.linear + ops.moe_route; env KAFKA_FUSED_ROUTER=1 overrides
     fused_router: bool = False
@@ -195,12 +200,17 @@ class LLMEngine:
             raise ValueError(f"the model's tile_prefill is {self.model.tile_prefill}, the engine asks for {tpf}")
         cfg.tile_prefill = tpf
         adt = os.environ.get("KAFKA_ACT_DTYPE") or cfg.act_dtype
-        if adt not in ops.ACT_DTYPES:
-            raise ValueError(f"act_dtype must be {', '.join(ops.ACT_DTYPES)}, not {adt!r}")
+        if adt not in MODEL_ACT_DTYPES:
+            raise ValueError(f"act_dtype must be {', '.join(MODEL_ACT_DTYPES)}, not {adt!r}")
         if adt == "fp8" and not (wdt == "fp8" and tpf):
             raise ValueError("act_dtype='fp8' needs weight_dtype='fp8' and tile_prefill (the e4m3 x e4m3 MFMA reads the "
                              f"fp8 tiles of the dense projections), not weight_dtype={wdt!r}, tile_prefill={tpf}, "
-                             f"expert_tiles_only={eto}")
+                             f"expert_tiles_only={eto}" +
+                             ("; the experts of an expert_tiles_only model take act_dtype='fp8_experts'" if eto else ""))
+        if adt == "fp8_experts" and not (mc.num_experts and wdt == "fp8" and eto):
+            raise ValueError("act_dtype='fp8_experts' needs a MoE model, weight_dtype='fp8' and expert_tiles_only (the "
+                             f"grouped e4m3 x e4m3 MFMA reads the fp8 expert tiles), not weight_dtype={wdt!r}, "
+                             f"tile_prefill={tpf}, expert_tiles_only={eto}")
         if adt == "mxfp8" and not (wdt == "mxfp4" and (tpf or eto)):
             raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill or expert_tiles_only (the "
                              f"scaled MFMA reads the MXFP4 tiles), not weight_dtype={wdt!r}, tile_prefill={tpf}, "

@@ -52,7 +52,10 @@ TP_OVERLAP = os.environ.get("KAFKA_TP_OVERLAP", "0") == "1"
 # 160 such seams of 32 MiB each; with the pipeline only the last block's all-reduce is left exposed.
 PIPE_CHUNKS = max(1, int(os.environ.get("KAFKA_TP_PIPE_CHUNKS", "4")))
 PIPE_ROWS = 256
-SKINNY = frozenset(p for p in os.environ.get("KAFKA_SKINNY", "qkv,o,down").replace("+", ",").split(",")
+# values of enable_stream_weights(act_dtype=) / EngineConfig.act_dtype: the kernel-level formats of ops.ACT_DTYPES and
+# "fp8_experts", the per-row fp8 format on the experts of an expert-tiles-only MoE model (moe.MoEBlock._tiles_mlp)
+ACT_DTYPES = ops.ACT_DTYPES + ("fp8_experts",)
+SKINNY =frozenset(p for p in os.environ.get("KAFKA_SKINNY", "qkv,o,down").replace("+", ",").split(",")
                    if p in ("qkv", "o", "down", "gate_up"))  # gate_up: fused SwiGLU epilogue (A/B, not default)
 # Fused decode layer (forward -> _forward_fused; env KAFKA_FUSED_DECODE=1): 6 launches per layer instead of 9 —
 # deferred RMSNorm and RoPE + KV write inside the streaming GEMMs' split-K finishers. Correct (fp32-reference and
@@ -250,13 +253,26 @@ class TransformerLM:
         ``act_dtype="fp8"`` (with ``weight_dtype="fp8"`` and ``tile_prefill``, nothing else): the same projections of the
         same steps quantise their input per row (``ops.fp8_act_quant``: e4m3, one power-of-two exponent per row) and run
         on the e4m3 x e4m3 MFMA (csrc/tile_gemm_f8.hip); the lm_head and the streamed / skinny steps keep bf16
-        activations, with the same difference between prefill rows and decode rows. The grouped expert kernel has no
-        such path: ``expert_tiles_only`` is refused."""
-        if act_dtype not in ops.ACT_DTYPES:
-            raise ValueError(f"act_dtype must be {', '.join(ops.ACT_DTYPES)}, not {act_dtype!r}")
+        activations, with the same difference between prefill rows and decode rows. With ``expert_tiles_only`` this
+        value is refused; that mode's value is the next one.
+
+        ``act_dtype="fp8_experts"`` (a MoE model with ``weight_dtype="fp8"`` and ``expert_tiles_only``, nothing else):
+        steps above ``moe.MOE_STREAM_MAX_T`` quantise the MoE block's input per row once, run the GLU half on the grouped
+        e4m3 x e4m3 MFMA kernel (csrc/grouped_tile_gemm_f8.hip), quantise its bf16 result [n_ent, F] per row (the amax
+        runs over the whole of F, so no GLU epilogue can do it) and run the combine half on the same kernel; smaller
+        steps keep the streaming kernel and bf16 activations. The attention projections of such a model have no
+        ``linear_tiles`` call site, so nothing else changes."""
+        if act_dtype not in ACT_DTYPES:
+            raise ValueError(f"act_dtype must be {', '.join(ACT_DTYPES)}, not {act_dtype!r}")
         if act_dtype == "fp8" and not (weight_dtype == "fp8" and tile_prefill):
             raise ValueError("act_dtype='fp8' needs weight_dtype='fp8' and tile_prefill (the e4m3 x e4m3 MFMA reads the "
                              f"fp8 tiles of the dense projections), not weight_dtype={weight_dtype!r}, "
+                             f"tile_prefill={tile_prefill}, expert_tiles_only={expert_tiles_only}" +
+                             ("; the experts of an expert_tiles_only model take act_dtype='fp8_experts'"
+                              if expert_tiles_only else ""))
+        if act_dtype == "fp8_experts" and not (self.cfg.num_experts and weight_dtype == "fp8" and expert_tiles_only):
+            raise ValueError("act_dtype='fp8_experts' needs a MoE model, weight_dtype='fp8' and expert_tiles_only (the "
+                             f"grouped e4m3 x e4m3 MFMA reads the fp8 expert tiles), not weight_dtype={weight_dtype!r}, "
                              f"tile_prefill={tile_prefill}, expert_tiles_only={expert_tiles_only}")
         if act_dtype == "mxfp8" and not (weight_dtype == "mxfp4" and (tile_prefill or expert_tiles_only)):
             raise ValueError("act_dtype='mxfp8' needs weight_dtype='mxfp4' and tile_prefill or expert_tiles_only (the "

@@ -22,8 +22,10 @@ An expert-tiles-only model (``enable_stream_weights(expert_tiles_only=True)``: `
 row-major experts: its larger steps run ``ops.grouped_tiles_glu`` / ``ops.grouped_tiles_combine``
 (csrc/grouped_tile_gemm.hip), a compute-oriented grouped MFMA GEMM on the same tiles of any format. With
 ``act_dtype="mxfp8"`` (MXFP4 tiles) those steps quantise the layer input to MXFP8 once and run both halves on the scaled
-fp8 x fp4 MFMA (csrc/grouped_tile_gemm_mx.hip), the GLU half writing its result as MXFP8 for the down half; steps at or
-below ``MOE_STREAM_MAX_T`` keep the streaming kernel and bf16 activations.
+fp8 x fp4 MFMA (csrc/grouped_tile_gemm_mx.hip), the GLU half writing its result as MXFP8 for the down half; with
+``act_dtype="fp8_experts"`` (fp8 tiles) they quantise it per row and run both halves on the e4m3 x e4m3 MFMA
+(csrc/grouped_tile_gemm_f8.hip), the bf16 intermediate quantised per row between them; steps at or below
+``MOE_STREAM_MAX_T`` keep the streaming kernel and bf16 activations.
 """
 from __future__ import annotations
 
@@ -100,10 +102,18 @@ class MoEBlock:
         """Expert-tiles-only model, a step above MOE_STREAM_MAX_T: both MLP halves on the expert tiles, added into the
         zeroed ``out`` f32 [rows of x, d] (csrc/grouped_tile_gemm.hip). With ``model.act_dtype == "mxfp8"`` they run on
         the scaled fp8 x fp4 MFMA (csrc/grouped_tile_gemm_mx.hip): x is quantised once, the GLU epilogue hands its result
-        on as an MXFP8 pair and the bf16 intermediate [n_ent, F] never exists."""
-        if getattr(self.model, "act_dtype", "bf16") == "mxfp8":
+        on as an MXFP8 pair and the bf16 intermediate [n_ent, F] never exists. With ``"fp8_experts"`` (fp8 tiles) they
+        run on the e4m3 x e4m3 MFMA (csrc/grouped_tile_gemm_f8.hip): x is quantised per row once, the intermediate stays
+        bf16 [n_ent, F] (a per-row exponent needs the amax over the whole of F) and is quantised per row for the
+        combine half."""
+        adt = getattr(self.model, "act_dtype", "bf16")
+        if adt == "mxfp8":
             a = ops.grouped_tiles_glu(x, lw.w13_t, r, e_lo=e_lo, scale=lw.w13_s, act="mxfp8", quant_out=True)
             ops.grouped_tiles_combine(a, lw.w2_t, r, x.shape[0], out, e_lo=e_lo, scale=lw.w2_s, act="mxfp8")
+            return
+        if adt == "fp8_experts":
+            a = ops.grouped_tiles_glu(x, lw.w13_t, r, e_lo=e_lo, scale=lw.w13_s, act="fp8")
+            ops.grouped_tiles_combine(a, lw.w2_t, r, x.shape[0], out, e_lo=e_lo, scale=lw.w2_s, act="fp8")
             return
         a = ops.grouped_tiles_glu(x, lw.w13_t, r, e_lo=e_lo, scale=lw.w13_s)
         ops.grouped_tiles_combine(a, lw.w2_t, r, x.shape[0], out, e_lo=e_lo, scale=lw.w2_s)

@@ -1162,15 +1162,21 @@ def grouped_stream_combine(a: torch.Tensor, wt: torch.Tensor, r: "MoERouting", T
 GT_BM = 256
 
 
-def _grouped_act(fn: str, f, act: str) -> bool:
-    """Whether a grouped tile call runs with MXFP8 activations (MXFP4 expert tiles only, as ``linear_tiles``)."""
+def _grouped_act(fn: str, f, act: str) -> str:
+    """The checked activation format of a grouped tile call: a quantised one needs its weight tile format (MXFP8 the
+    MXFP4 expert tiles, fp8 the fp8 ones, as ``linear_tiles``)."""
     if act not in ACT_DTYPES:
         raise ValueError(f"{fn}: act must be {', '.join(ACT_DTYPES)}, not {act!r}")
-    if act == "mxfp8" and f.name != "mxfp4":
-        raise ValueError(f"{fn}: act='mxfp8' needs mxfp4 weight tiles, not {f.name} ones")
-    if act == "fp8":
-        raise ValueError(f"{fn}: act='fp8' is not built for the grouped expert kernels (dense linear_tiles only)")
-    return act == "mxfp8"
+    if act in ACT_TILES and f.name != ACT_TILES[act]:
+        raise ValueError(f"{fn}: act={act!r} needs {ACT_TILES[act]} weight tiles, not {f.name} ones")
+    return act
+
+
+def _fp8_dequant(x: torch.Tensor) -> torch.Tensor:
+    """The exact values of ``reference.fp8_quant(x)`` (CPU reference paths): fp32, float64 for float64 inputs."""
+    xq, xe = ref.fp8_quant(x)
+    dt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    return torch.ldexp(xq.view(torch.float8_e4m3fn).to(dt), xe[:, None])
 
 
 def grouped_tiles_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: int = 0,
@@ -1182,11 +1188,20 @@ def grouped_tiles_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: 
     ``act="mxfp8"``) the epilogue quantises its bf16 result itself and the call returns the pair (aq uint8 [n_ent, F],
     ae float8_e8m0fnu [n_ent, F/32]) = ``reference.mxfp8_quant`` of the bf16 output bit for bit, which
     ``grouped_tiles_combine(act="mxfp8")`` takes: no bf16 intermediate is written. On CPU tensors the reference path
-    runs on ``mxfp8_dequant(mxfp8_quant(x))``."""
+    runs on ``mxfp8_dequant(mxfp8_quant(x))``.
+    ``act="fp8"`` (fp8 tiles only): x [T, K] is quantised once, before the gather, by ``fp8_act_quant`` and the product
+    runs on the e4m3 x e4m3 MFMA (csrc/grouped_tile_gemm_f8.hip), row exponents (gathered with the rows) and the
+    experts' row scales applied to the fp32 accumulators. ``quant_out`` is refused: a per-row exponent needs the amax
+    over the whole of F, so the intermediate stays bf16. On CPU tensors the reference path runs on the dequantised
+    ``reference.fp8_quant(x)``."""
     f, scale = _expert_format("grouped_tiles_glu", wt, scale)
-    mx = _grouped_act("grouped_tiles_glu", f, act)
+    act = _grouped_act("grouped_tiles_glu", f, act)
+    mx = act == "mxfp8"
     n_ent = r.perm_tok.numel()
     F = wt.shape[1] * 16  # (N / 32 tiles of 32 rows, N = 2 F: every tile format)
+    if quant_out and act == "fp8":
+        raise ValueError("grouped_tiles_glu: quant_out is not built for act='fp8': a per-row exponent needs the amax "
+                         "over the whole of F, which no 256-column tile of the GLU epilogue can know")
     if quant_out and not (mx and F % 32 == 0):
         raise ValueError("grouped_tiles_glu: quant_out needs act='mxfp8' and F % 32 == 0")
     if _gpu(x):
@@ -1203,11 +1218,17 @@ def grouped_tiles_glu(x: torch.Tensor, wt: torch.Tensor, r: "MoERouting", e_lo: 
             ext().grouped_tile_gemm_mx(xq, xe.view(torch.uint8), wt, scale, r.perm_tok, r.perm_w, r.expert_off,
                                        int(e_lo), True, y, aq, ae, None)
             return (aq, ae.view(torch.float8_e8m0fnu)) if quant_out else y
+        if act == "fp8":
+            xq, xe = fp8_act_quant(x)
+            ext().grouped_tile_gemm_f8(xq, xe, wt, scale, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), True, y, None)
+            return y
         ext().grouped_tile_gemm(x, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), True, y, None)
         return y
     y = torch.empty(n_ent, F, dtype=x.dtype, device=x.device)
     if mx:
         x = ref.mxfp8_dequant(*ref.mxfp8_quant(x))  # (fp32: the exact quantised values)
+    elif act == "fp8":
+        x = _fp8_dequant(x)
     h = ref_grouped(x, untile_experts_as(wt, scale, glu=True), r, e_lo, gather=True)
     y.copy_(ref.silu_mul(h))
     return ref.mxfp8_quant(y) if quant_out else y
@@ -1217,14 +1238,18 @@ def grouped_tiles_combine(a, wt: torch.Tensor, r: "MoERouting", T: int, out: tor
                           e_lo: int = 0, scale: torch.Tensor | None = None, act: str = "bf16") -> torch.Tensor:
     """``grouped_stream_combine`` for prefill-sized steps: out[token] += w * (a[entry] @ W_e^T) over the local experts'
     entries (out f32 [T, N], zeroed by the caller). ``act="mxfp8"`` (MXFP4 tiles only): ``a`` is bf16 [n_ent, K],
-    quantised here by ``mxfp8_quant``, or the pair (aq, ae) of ``grouped_tiles_glu(quant_out=True)``."""
+    quantised here by ``mxfp8_quant``, or the pair (aq, ae) of ``grouped_tiles_glu(quant_out=True)``. ``act="fp8"``
+    (fp8 tiles only): ``a`` is bf16 [n_ent, K], quantised here per row by ``fp8_act_quant`` (rows of other ranks'
+    experts are undefined, quantise to undefined bytes and are never read), or a pair (aq, ae) already in that form;
+    the product runs on csrc/grouped_tile_gemm_f8.hip."""
     f, scale = _expert_format("grouped_tiles_combine", wt, scale)
-    mx = _grouped_act("grouped_tiles_combine", f, act)
+    act = _grouped_act("grouped_tiles_combine", f, act)
+    mx = act == "mxfp8"
     if out.shape[0] != T:
         raise ValueError("grouped_tiles_combine: out must have one row per token")
     pair = isinstance(a, (tuple, list))
-    if pair and not mx:
-        raise ValueError("grouped_tiles_combine: an (aq, ae) pair needs act='mxfp8'")
+    if pair and act == "bf16":
+        raise ValueError("grouped_tiles_combine: an (aq, ae) pair needs act='mxfp8' or act='fp8'")
     if _gpu(out):
         if f.raw:
             wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
@@ -1233,10 +1258,18 @@ def grouped_tiles_combine(a, wt: torch.Tensor, r: "MoERouting", T: int, out: tor
             ext().grouped_tile_gemm_mx(aq, ae.view(torch.uint8), wt, scale, r.perm_tok, r.perm_w, r.expert_off,
                                        int(e_lo), False, None, None, None, out)
             return out
+        if act == "fp8":
+            aq, ae = a if pair else fp8_act_quant(a)
+            ext().grouped_tile_gemm_f8(aq, ae, wt, scale, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), False, None,
+                                       out)
+            return out
         ext().grouped_tile_gemm(a, wt, scale, f.abi, r.perm_tok, r.perm_w, r.expert_off, int(e_lo), False, None, out)
         return out
     if mx:
         a = ref.mxfp8_dequant(*(a if pair else ref.mxfp8_quant(a)))
+    elif act == "fp8":
+        a = (torch.ldexp(ref.fp8_act_order(a[0]).view(torch.float8_e4m3fn).float(), a[1][:, None]) if pair
+             else _fp8_dequant(a))
     ref.grouped_gemm(a, untile_experts_as(wt, scale), r.perm_tok, r.perm_w, r.expert_off, e_lo, False, None, out)
     return out
 

@@ -25,7 +25,8 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"skinny_gemm.hip": NO_PK_F32, "grouped_tile_gemm.hip": NO_PK_F32, "attn_tile_fp8.hip": NO_PK_F32,
               "tile_gemm.hip": NO_PK_F32, "moe_router.hip": NO_PK_F32, "tile_gemm_mx.hip": NO_PK_F32,
-              "grouped_tile_gemm_mx.hip": NO_PK_F32, "tile_gemm_f8.hip": NO_PK_F32}
+              "grouped_tile_gemm_mx.hip": NO_PK_F32, "tile_gemm_f8.hip": NO_PK_F32,
+              "grouped_tile_gemm_f8.hip": NO_PK_F32}
 
 
 def build(verbose: bool = False) -> Path:

@@ -1164,6 +1164,58 @@ static void grouped_tile_gemm_mx(at::Tensor xq, at::Tensor xe, at::Tensor wt, at
                                               aqp, aep, op, ldo, cur_stream()));
 }
 
+// grouped_tile_gemm with per-row fp8 activations on the fp8 expert tiles (csrc/grouped_tile_gemm_f8.hip): xq uint8
+// [rows, K] (16-B rows, fp8-tile K order) / xe int32 [rows] as act_quant_fp8 leaves them, token rows with glu (gathered
+// through perm_tok), one row per routed entry otherwise; wt / scale the fp8 expert tiles and their f32 row scales. glu
+// writes y bf16 [n_ent, N/2]; else the weighted combine adds into out f32 [T, N].
+static void grouped_tile_gemm_f8(at::Tensor xq, at::Tensor xe, at::Tensor wt, at::Tensor scale, at::Tensor perm_tok,
+                                 at::Tensor perm_w, at::Tensor expert_off, int64_t e_lo, bool glu,
+                                 c10::optional<at::Tensor> y, c10::optional<at::Tensor> out) {
+  const char* fn = "grouped_tile_gemm_f8";
+  CHECK_CUDA(xq); CHECK_DT(xq, at::kByte); CHECK_LASTDIM(xq);
+  TORCH_CHECK(xq.dim() == 2 && xq.stride(0) % 16 == 0, fn, ": xq must be uint8 [rows, K] with 16-B rows");
+  const int vk = check_wfmt(fn, kafka::WF_FP8, wt, scale, 1);
+  CHECK_CUDA(perm_tok); CHECK_CUDA(perm_w); CHECK_CUDA(expert_off);
+  CHECK_DT(perm_tok, at::kInt); CHECK_DT(perm_w, at::kFloat); CHECK_DT(expert_off, at::kInt);
+  const int64_t E_local = wt.size(0), N = wt.size(1) * 32, K = wt.size(2) * vk, R = xq.size(0);
+  TORCH_CHECK(xq.size(1) == K, fn, ": K mismatch (xq has K = ", xq.size(1), ", the tiles ", K, ")");
+  TORCH_CHECK(xq.device() == wt.device(), fn, ": xq and wt on different devices");
+  TORCH_CHECK(K % 256 == 0 && N % 64 == 0 && K < (1LL << 31) && N < (1LL << 31), fn,
+              ": needs K % 256 == 0 and N % 64 == 0");
+  CHECK_CUDA(xe); CHECK_DT(xe, at::kInt);
+  TORCH_CHECK(xe.is_contiguous() && xe.dim() == 1 && xe.size(0) == R && xe.device() == xq.device(), fn,
+              ": xe must be contiguous int32 [rows]");
+  const int64_t n_ent = perm_tok.numel();
+  TORCH_CHECK(perm_w.numel() == n_ent && n_ent < (1LL << 31) && perm_tok.is_contiguous() && perm_w.is_contiguous(), fn,
+              ": perm");
+  TORCH_CHECK(expert_off.is_contiguous() && e_lo >= 0 && E_local <= 16 && expert_off.numel() >= e_lo + E_local + 1, fn,
+              ": expert_off too short for the local experts (at most 16)");
+  bf16* yp = nullptr;
+  int64_t ldy = 0, ldo = 0;
+  float* op = nullptr;
+  if (glu) {
+    TORCH_CHECK(y.has_value() && !out.has_value(), fn, ": the GLU half writes y");
+    CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
+    TORCH_CHECK(y->dim() == 2 && y->size(0) >= n_ent && y->size(1) == N / 2 && y->stride(0) % 8 == 0 &&
+                    y->device() == xq.device(), fn, ": y must be [n_ent, N/2] with 16-B rows");
+    yp = bptr(y.value());
+    ldy = y->stride(0);
+  } else {
+    TORCH_CHECK(out.has_value() && !y.has_value(), fn, ": the combine half adds into out");
+    CHECK_CUDA(out.value()); CHECK_DT(out.value(), at::kFloat); CHECK_LASTDIM(out.value());
+    // (perm_tok < T = out's rows is the router's contract, as for grouped_tile_gemm)
+    TORCH_CHECK(out->dim() == 2 && out->size(1) == N && R >= n_ent && out->device() == xq.device(), fn,
+                ": out must be [T, N] and xq hold one row per routed entry");
+    op = out->data_ptr<float>();
+    ldo = out->stride(0);
+  }
+  CHECK_HIP(kafka_launch_grouped_tile_gemm_f8(xq.data_ptr<uint8_t>(), xq.stride(0), xe.data_ptr<int>(), wt.data_ptr(),
+                                              scale.data_ptr<float>(), (int)E_local, (int)N, (int)K,
+                                              perm_tok.data_ptr<int>(), perm_w.data_ptr<float>(),
+                                              expert_off.data_ptr<int>(), (int)e_lo, (int)n_ent, glu ? 1 : 0, yp, ldy, op,
+                                              ldo, cur_stream()));
+}
+
 // y [M, N] bf16 = sum over the slabs p [S, M, N]
 static void slab_reduce(at::Tensor p, at::Tensor y) {
   CHECK_CUDA(p); CHECK_DT(p, at::kFloat); CHECK_DT(y, at::kBFloat16); CHECK_LASTDIM(y);
@@ -1531,6 +1583,9 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.def("grouped_tile_gemm_mx", &grouped_tile_gemm_mx, py::arg("xq"), py::arg("xe"), py::arg("wt"), py::arg("scale"),
         py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("glu"), py::arg("y"),
         py::arg("aq"), py::arg("ae"), py::arg("out"));
+  m.def("grouped_tile_gemm_f8", &grouped_tile_gemm_f8, py::arg("xq"), py::arg("xe"), py::arg("wt"), py::arg("scale"),
+        py::arg("perm_tok"), py::arg("perm_w"), py::arg("expert_off"), py::arg("e_lo"), py::arg("glu"), py::arg("y"),
+        py::arg("out"));
   m.def("moe_route", &moe_route);
   m.def("moe_gate_route_plan", &moe_gate_route_plan);
   m.def("moe_gate_route", &moe_gate_route);

@@ -350,6 +350,18 @@ hipError_t kafka_launch_grouped_tile_gemm_mx(const uint8_t* Xq, int64_t ldxq, co
                                              bf16* Y, int64_t ldy, uint8_t* Aq, uint8_t* Ae, float* out, int64_t ldo,
                                              hipStream_t st);
 
+// ---- grouped_tile_gemm_f8.hip
+// kafka_launch_grouped_tile_gemm on the e4m3 x e4m3 MFMA (see grouped_tile_gemm_f8_kernel): Xq / Ea per-row fp8 rows as
+// kafka_launch_act_quant_fp8 leaves them (fp8-tile K order, row stride ldxq % 16 == 0; token rows with glu, one row per
+// routed entry otherwise), Wt8 / St the WF_FP8 expert tiles and their row scales in tile order, per local expert. glu
+// writes Y bf16 [n_ent, N/2] (ldy % 8 == 0); else the weighted combine into out f32 [T, N] (zeroed by the caller).
+// hipErrorInvalidValue for ldxq % 16 != 0 or ldxq < K, null pointers, e_local > 16, N % 64 != 0, K % 256 != 0, with glu
+// a null Y or ldy % 8 != 0, without it a null out; a no-op for n_ent < 1.
+hipError_t kafka_launch_grouped_tile_gemm_f8(const uint8_t* Xq, int64_t ldxq, const int* Ea, const void* Wt8,
+                                             const float* St, int e_local, int N, int K, const int* perm_tok,
+                                             const float* perm_w, const int* expert_off, int e_lo, int n_ent, int glu,
+                                             bf16* Y, int64_t ldy, float* out, int64_t ldo, hipStream_t st);
+
 // ---- moe.hip
 hipError_t kafka_launch_moe_route(const bf16* logits, int64_t ld, int T, int E, int K, int BM, float* topk_w,
                                   int* topk_e, int* perm_tok, float* perm_w, int* expert_off, int* tile_off,

@@ -43,8 +43,8 @@
 //     tiles, as integer exponents; the accumulators are scaled with v_ldexp_f32 (exact, and 2^ea * sw is never formed:
 //     it could leave fp32's range where the product does not).
 //   * LDS 160 KB, 1 workgroup per CU; VGPRs and the absence of scratch: profiles/act_fp8/resource_usage.txt.
-// Not built: the grouped expert kernel for fp8 Mixtral; the quantiser fused into RMSNorm or the attention epilogue;
-// fp8 activations on the streaming or skinny GEMMs; the lm_head.
+// Not built: the quantiser fused into RMSNorm or the attention epilogue; fp8 activations on the streaming or skinny
+// GEMMs; the lm_head. (The grouped expert kernel for fp8 Mixtral is grouped_tile_gemm_f8.hip.)
 #include "common.h"
 #include "tile_epilogue.h"
 
