@@ -10,7 +10,11 @@ scaled-MFMA path of csrc/tile_gemm_mx.hip: ``mx`` = ops.linear_tiles(act="mxfp8"
 csrc/tile_gemm_f8.hip (``f8``, ``f8_gemm``, ``quant``), beside the bf16-MFMA kernel on the same fp8 tiles (``tiles``) and
 hipBLASLt on the dequantised copy (``blas_copy``). Each timed call of a path reads another copy of
 the weight (>= 600 MB rotated, so the MALL does not serve repeats). One JSON line per (round, cell); TFLOP/s over
-2 M N K."""
+2 M N K.
+``--fused-quant`` (with ``--act-dtype mxfp8|fp8``) times instead the chains of a layer with and without the fused
+quantisers (models/llama.py FUSE_ACT_QUANT): ``norm_qkv`` / ``norm_gate_up`` = fused_add_rmsnorm -> quantiser -> GEMM
+against the quantising norm -> GEMM, and under mxfp8 ``glu_down`` = gate_up + GLU -> quantiser -> down against the
+quantising epilogue -> down. One JSON line per (round, cell) with ``unfused_us`` and ``fused_us``."""
 import argparse
 import json
 
@@ -44,6 +48,46 @@ def identity_routing(M, dev):
     return ops.moe_route(torch.zeros(M, 1, dtype=torch.bfloat16, device=dev), 1)
 
 
+def fused_quant(args, dev="cuda"):
+    act, fmt = args.act_dtype, ops.ACT_TILES[args.act_dtype]
+    quant = ops.mxfp8_quant if act == "mxfp8" else ops.fp8_act_quant
+
+    def tiles(N, K, glu):  # >= 600 MB of copies of one projection, rotated by the timed calls
+        n = max(2, (600 << 20) // ops.tiled_weight_bytes((N, K), fmt) + 1)
+        return [ops.tile_weight_as((torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16), fmt, glu) for _ in range(n)]
+
+    for model in args.models.split(","):
+        shp = {name: (N, K, glu) for name, N, K, glu in MODELS[model]}
+        d = shp["qkv"][1]
+        nw = torch.ones(d, dtype=torch.bfloat16, device=dev)
+        cells = [("norm_" + g, g) for g in ("qkv", "gate_up") if g in args.gemms.split(",")]
+        if act == "mxfp8" and "down" in args.gemms.split(","):
+            cells.append(("glu_down", "gate_up"))
+        for cell, g in cells:
+            N, K, glu = shp[g]
+            wts = tiles(N, K, glu)
+            dts = tiles(*shp["down"]) if cell == "glu_down" else None
+            for M in (int(m) for m in args.rows.split(",")):
+                delta, res = ((torch.randn(M, d, device=dev) * 0.5).to(torch.bfloat16) for _ in range(2))
+                lin = lambda x, w, **kw: ops.linear_tiles(x, w[0], scale=w[1], act=act, **kw)
+                if cell == "glu_down":
+                    xq, xe = quant(delta)
+                    paths = {"unfused": lambda i: lin(lin(xq, wts[i % len(wts)], glu=True, x_scale=xe), dts[i % len(dts)]),
+                             "fused": lambda i: (lambda a: lin(a[0], dts[i % len(dts)], x_scale=a[1]))(
+                                 lin(xq, wts[i % len(wts)], glu=True, x_scale=xe, quant_out=True))}
+                else:
+                    paths = {"unfused": lambda i: lin(ops.fused_add_rmsnorm(delta, res, nw, 1e-5), wts[i % len(wts)], glu=glu),
+                             "fused": lambda i: (lambda a: lin(a[0], wts[i % len(wts)], glu=glu, x_scale=a[1]))(
+                                 ops.fused_add_rmsnorm(delta, res, nw, 1e-5, quant=act))}
+                for rnd in range(args.rounds):
+                    us = {k: timeit(fn, args.iters) for k, fn in paths.items()}
+                    print(json.dumps({"model": model, "cell": cell, "act_dtype": act, "M": M, "N": N, "K": K, "round": rnd,
+                                      "unfused_us": round(us["unfused"], 1), "fused_us": round(us["fused"], 1),
+                                      "gain_pct": round(100 * (1 - us["fused"] / us["unfused"]), 2)}), flush=True)
+            del wts, dts
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="8b,70b")
@@ -53,7 +97,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--act-dtype", default="bf16", choices=ops.ACT_DTYPES)
+    ap.add_argument("--fused-quant", action="store_true")
     args = ap.parse_args()
+    if args.fused_quant:
+        if args.act_dtype == "bf16" or not torch.cuda.is_available():
+            raise SystemExit("--fused-quant needs --act-dtype mxfp8 or fp8 and a GPU")
+        return fused_quant(args)
     mx = args.act_dtype == "mxfp8"
     qa = args.act_dtype != "bf16"  # quantised activations: "mx" on the mxfp4 tiles, "f8" on the fp8 tiles
     tag = "mx" if mx else "f8"

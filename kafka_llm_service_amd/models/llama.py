@@ -64,6 +64,11 @@ SKINNY =frozenset(p for p in os.environ.get("KAFKA_SKINNY", "qkv,o,down").replac
 # more than the RMSNorm / RoPE launches it removes — headline 8,231 vs 8,671 tok/s same box
 # (profiles/r06/fused/README.md).
 FUSED = os.environ.get("KAFKA_FUSED_DECODE", "0") == "1"
+# Quantised activations (act_dtype "mxfp8" / "fp8", TP = 1): the RMSNorm in front of qkv and (dense layers) gate_up
+# emits the quantised rows itself, and under "mxfp8" so does gate_up's GLU epilogue for down, instead of a bf16 tensor
+# and a stand-alone quantiser launch each (bit-identical; only o keeps its quantiser, and down under "fp8"). No
+# environment variable: a switch for tests and A/B runs (profiles/act_quant_fused/).
+FUSE_ACT_QUANT = True
 _OVL: dict = {}
 _SEAM_DONE = object()  # forward(): the previous layer's overlapped seam already produced this layer's input
 
@@ -360,20 +365,40 @@ class TransformerLM:
             torch.cuda.empty_cache()  # the dropped copies go back to the device before the KV pool is sized
         return added
 
+    def _on_tiles(self, M: int, wt: torch.Tensor | None, kind: str, max_splits: int = 8, small: bool = True) -> bool:
+        """Whether an M-row step sends the projection ``kind`` to ``ops.linear_tiles``: a tile_prefill model past the
+        rows of the streaming kernel and of the skinny GEMM (``small`` False: a gate_up without GLU tiles, which has
+        neither). The one row test of ``_linear``, of forward's gate_up branch and of the producers that quantise for
+        them."""
+        if not (self.stream and self.tile_prefill and wt is not None and M > 0):
+            return False
+        if small and (M <= self.stream_max_m or (kind in SKINNY and ops.skinny_plan(M, *ops.tiled_dims(wt), max_splits))):
+            return False
+        return True
+
+    def _fuse_quant(self, M: int, wt: torch.Tensor | None, kind: str, small: bool = True) -> str | None:
+        """The ``quant`` of the norm (or GLU epilogue) that produces the input of projection ``kind`` on an M-row step:
+        the activation format where the fused path runs (FUSE_ACT_QUANT), else None."""
+        if FUSE_ACT_QUANT and self.tp == 1 and self.act_dtype in ops.ACT_TILES and self._on_tiles(M, wt, kind, small=small):
+            return self.act_dtype
+        return None
+
     def _linear(self, x: torch.Tensor, w: torch.Tensor, wt: torch.Tensor | None, max_splits: int = 8,
-                kind: str = "", st: torch.Tensor | None = None):
+                kind: str = "", st: torch.Tensor | None = None, xs: torch.Tensor | None = None):
         """x @ w^T: the weight-streaming kernel for decode-sized x (bf16 or a split-K slab out), the skinny MFMA GEMM
         for 129..256 rows of the projections in SKINNY (tiles of every format), else hipBLASLt. ``st``: the scales of
-        fp8 / mxfp4 tiles."""
+        fp8 / mxfp4 tiles. ``xs``: x is already quantised (``_fuse_quant``) and these are its exponents."""
         M = x.shape[0]
+        if self._on_tiles(M, wt, kind, max_splits):
+            # (the lm_head, kind "", keeps bf16 activations: logits are what the sampler and logprobs read)
+            kw = {} if xs is None else {"x_scale": xs}
+            return ops.linear_tiles(x, wt, max_splits, scale=st, act=self.act_dtype if kind else "bf16", **kw)
+        assert xs is None, "a quantised input whose consumer is not the tile GEMM"
         if self.stream and wt is not None:
             if 0 < M <= self.stream_max_m:
                 return ops.linear_stream(x, wt, max_splits, scale=st)
             if kind in SKINNY and ops.skinny_plan(M, wt.shape[0] * 32, x.shape[1], max_splits):
                 return ops.linear_skinny(x, wt, max_splits, scale=st)
-            if self.tile_prefill and M > 0:
-                # (the lm_head, kind "", keeps bf16 activations: logits are what the sampler and logprobs read)
-                return ops.linear_tiles(x, wt, max_splits, scale=st, act=self.act_dtype if kind else "bf16")
         return F.linear(x, self._dense(w, wt, st=st))
 
     @staticmethod
@@ -422,18 +447,25 @@ class TransformerLM:
         tp = self.tp > 1
         delta, pending = None, False
         for i, lw in enumerate(self.layers):
+            # xin / xs: the projection's input, x or (fused quantiser) the quantised rows and their exponents
+            xin, xs, qn = x, None, self._fuse_quant(T, lw.qkv_t, "qkv")
             if delta is _SEAM_DONE:
                 pass  # the previous layer's overlapped down seam already wrote residual and x
             elif delta is None:
-                ops.rmsnorm(h, lw.input_norm, eps, out=x)
+                if qn:
+                    xin, xs = ops.rmsnorm(h, lw.input_norm, eps, quant=qn)
+                else:
+                    ops.rmsnorm(h, lw.input_norm, eps, out=x)
                 # the embedding is a fresh tensor at TP = 1 (the residual stream can own it); under TP it may be the
                 # all-reduce's persistent buffer
                 residual = h if self.tp == 1 else h.clone()
             elif pending:
                 pstate.tp_all_reduce_add_rmsnorm(delta, residual, lw.input_norm, eps, out=x)
+            elif qn:
+                xin, xs = ops.fused_add_rmsnorm(delta, residual, lw.input_norm, eps, quant=qn)
             else:
                 ops.fused_add_rmsnorm(delta, residual, lw.input_norm, eps, out=x)
-            qkv = self._linear(x, lw.qkv, lw.qkv_t, kind="qkv", st=lw.qkv_s)
+            qkv = self._linear(xin, lw.qkv, lw.qkv_t, kind="qkv", st=lw.qkv_s, xs=xs)
             ops.rope_kv_write(qkv, inp.positions, self.cos_sin, q, k_caches[i], v_caches[i], inp.slot_mapping,
                               self.hq, self.hkv)
             paged_attention(q, k_caches[i], v_caches[i], inp.attn, attn_out)
@@ -445,10 +477,15 @@ class TransformerLM:
                 ops.fused_add_rmsnorm(o, residual, lw.post_norm, eps, out=x)
             else:
                 o = self._linear(attn_out.view(T, -1), lw.o, lw.o_t, kind="o", st=lw.o_s)
+                # (MoE layers keep the bf16 rows: the router and the MoE block read them)
+                qn = None if lw.router is not None else self._fuse_quant(T, lw.gate_up_t, "gate_up", bool(lw.glu))
                 if tp:
                     pstate.tp_all_reduce_add_rmsnorm(o, residual, lw.post_norm, eps, out=x)
+                elif qn:
+                    xin, xs = ops.fused_add_rmsnorm(o, residual, lw.post_norm, eps, quant=qn)
                 else:
                     ops.fused_add_rmsnorm(o, residual, lw.post_norm, eps, out=x)
+            a_s = None  # the exponents of a where gate_up's epilogue quantised it
             if lw.router is not None:
                 delta = self.moe(x, lw)
                 pending = tp and not self.moe.reduced
@@ -461,9 +498,15 @@ class TransformerLM:
                 a = ops.linear_skinny(x, lw.gate_up_t, glu=True, scale=lw.gate_up_s)
                 if ops.is_slab(a):
                     a = ops.silu_mul(a)
-            elif self.tile_prefill and lw.gate_up_t is not None and T > 0:
-                # the dense tile GEMM: SwiGLU in its epilogue on GLU-tiled weights, else gate | up through silu_mul
-                a = ops.linear_tiles(x, lw.gate_up_t, glu=bool(lw.glu), scale=lw.gate_up_s, act=self.act_dtype)
+            elif self._on_tiles(T, lw.gate_up_t, "gate_up", small=bool(lw.glu)):
+                # the dense tile GEMM: SwiGLU in its epilogue on GLU-tiled weights, else gate | up through silu_mul;
+                # quantised rows in from post_norm, and (MXFP8) out of the epilogue for down
+                kw = {} if xs is None else {"x_scale": xs}
+                if lw.glu and self._fuse_quant(T, lw.down_t, "down") == "mxfp8":
+                    kw["quant_out"] = True
+                a = ops.linear_tiles(xin, lw.gate_up_t, glu=bool(lw.glu), scale=lw.gate_up_s, act=self.act_dtype, **kw)
+                if kw.get("quant_out"):
+                    a, a_s = a
                 if not lw.glu:
                     a = ops.silu_mul(a)
             else:
@@ -477,7 +520,7 @@ class TransformerLM:
                                                     self._pipe_chunks(T))
                 pending = False  # already reduced: the next seam is a plain add + RMSNorm
             else:
-                delta = self._linear(a, lw.down, lw.down_t, kind="down", st=lw.down_s)
+                delta = self._linear(a, lw.down, lw.down_t, kind="down", st=lw.down_s, xs=a_s)
                 pending = tp
         if pending:
             delta = pstate.tp_all_reduce(delta)

@@ -46,7 +46,41 @@ def rows_of(t: torch.Tensor) -> int:
     return t.shape[1] if is_slab(t) else t.shape[0]
 
 
-def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, out: torch.Tensor | None = None) -> torch.Tensor:
+_NORM_QUANT = {"mxfp8": 1, "fp8": 2}  # rmsnorm_quant's codes (csrc/norm_act.hip Q_MXFP8 / Q_FP8)
+
+
+def _norm_quant(fn: str, x: torch.Tensor, residual: torch.Tensor | None, w: torch.Tensor, eps: float, out, quant: str):
+    """The quantising RMSNorm (csrc/norm_act.hip rmsnorm_quant_kernel): the pair ``mxfp8_quant`` / ``fp8_act_quant``
+    would make of the bf16 norm output, which is never written. ``x`` 2-D bf16 or a slab (then with a residual)."""
+    if quant not in _NORM_QUANT:
+        raise ValueError(f"{fn}: quant must be None, 'mxfp8' or 'fp8', not {quant!r}")
+    if out is not None:
+        raise ValueError(f"{fn}: quant={quant!r} returns (xq, xe); there is no bf16 output to put into out")
+    T, d = rows_of(x), x.shape[-1]
+    if x.dim() != (3 if is_slab(x) else 2) or d % 256 != 0:
+        raise ValueError(f"{fn}: quant={quant!r} needs 2-D rows (or a slab) with d % 256 == 0, not {tuple(x.shape)}")
+    if not _gpu(x):
+        if residual is None:
+            y = ref.rmsnorm(x, w, eps)
+        else:
+            y, s = ref.fused_add_rmsnorm(x.sum(0) if is_slab(x) else x, residual, w, eps)
+            residual.copy_(s)
+        return mxfp8_quant(y) if quant == "mxfp8" else fp8_act_quant(y)
+    xq = torch.empty(T, d, dtype=torch.uint8, device=x.device)
+    if quant == "mxfp8":
+        xe = torch.empty(T, d // 32, dtype=torch.uint8, device=x.device)
+    else:
+        xe = torch.empty(T, dtype=torch.int32, device=x.device)
+    ext().rmsnorm_quant(x, residual, w, float(eps), xq, xe, _NORM_QUANT[quant])
+    return xq, (xe.view(torch.float8_e8m0fnu) if quant == "mxfp8" else xe)
+
+
+def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, out: torch.Tensor | None = None, quant: str | None = None):
+    """rmsnorm(x) * w. ``quant="mxfp8"`` / ``"fp8"`` (x [T, d], d % 256 == 0, ``out`` None): returns instead the pair
+    (xq, xe) that ``mxfp8_quant`` / ``fp8_act_quant`` make of that bf16 result, from one HIP kernel that writes no bf16
+    row: the input of ``linear_tiles(xq, ..., act=quant, x_scale=xe)``."""
+    if quant is not None:
+        return _norm_quant("rmsnorm", x, None, w, eps, out, quant)
     if out is None:
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     if _gpu(x):
@@ -57,9 +91,14 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, out: torch.Tensor | No
 
 
 def fused_add_rmsnorm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: float,
-                      out: torch.Tensor | None = None) -> torch.Tensor:
+                      out: torch.Tensor | None = None, quant: str | None = None):
     """residual <- x + residual (in place); returns rmsnorm(residual) * w (into ``out`` or a new tensor).
-    ``x`` may be a split-K slab [S, T, d] (summed in fp32 before the add)."""
+    ``x`` may be a split-K slab [S, T, d] (summed in fp32 before the add). ``quant``: as for ``rmsnorm`` (the residual
+    update is unchanged; 2-D x and residual)."""
+    if quant is not None:
+        if residual.dim() != 2:
+            raise ValueError(f"fused_add_rmsnorm: quant={quant!r} needs a 2-D residual, not {tuple(residual.shape)}")
+        return _norm_quant("fused_add_rmsnorm", x, residual, w, eps, out, quant)
     slab = is_slab(x)
     if out is None:
         out = torch.empty(residual.shape, dtype=residual.dtype, device=x.device)
@@ -769,7 +808,8 @@ def mxfp8_quant(x: torch.Tensor):
 
 
 def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bool = False,
-                 scale: torch.Tensor | None = None, act: str = "bf16") -> torch.Tensor:
+                 scale: torch.Tensor | None = None, act: str = "bf16", x_scale: torch.Tensor | None = None,
+                 quant_out: bool = False):
     """y = x @ W^T for any number of rows from the wave-tiled weight (prefill-sized steps of a model that lives in its
     tiles alone): bf16 [M, N] for one split, or with ``glu`` (GLU-tiled gate_up, never split) the activated
     silu(gate) * up [M, N/2]; else the fp32 split-K slabs [S, M, N], split s the K range [s K / S, (s + 1) K / S).
@@ -782,7 +822,13 @@ def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bo
     ``act="fp8"`` (fp8 tiles only): x is quantised per row by ``fp8_act_quant`` and the product runs on the e4m3 x e4m3
     MFMA (csrc/tile_gemm_f8.hip), the row exponents and the weights' row scales applied to the fp32 accumulators; same
     plan, shapes and slab contract. On CPU tensors it is the dequantised ``reference.fp8_quant(x)`` times the
-    dequantised weight."""
+    dequantised weight.
+    ``x_scale`` (``act`` "mxfp8" or "fp8"): x is the already quantised uint8 [M, K] and ``x_scale`` its exponents, the
+    pair ``mxfp8_quant`` / ``fp8_act_quant`` (or a quantising producer: ``rmsnorm(..., quant=)``, ``quant_out``)
+    returns; no quantiser runs.
+    ``quant_out`` (``act="mxfp8"`` with ``glu``): returns (aq, ae) = ``mxfp8_quant`` of the bf16 silu(gate) * up, bit
+    for bit, written by the GEMM's epilogue (no bf16 [M, N/2] exists): the down projection's ``x`` / ``x_scale``. A row
+    of per-row fp8 has its amax spread over every column block of the grid, so ``act="fp8"`` cannot do this."""
     M, K = x.shape
     f = WEIGHT_FORMATS.get(wt.dtype)
     if f is None:
@@ -790,6 +836,20 @@ def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bo
     if act not in ACT_DTYPES:
         raise ValueError(f"linear_tiles: act must be {', '.join(ACT_DTYPES)}, not {act!r}")
     mx = act == "mxfp8"
+    if quant_out and not (mx and glu):
+        raise ValueError("linear_tiles: quant_out needs act='mxfp8' and glu" + (
+            " (a per-row fp8 exponent needs the row's amax over every column block; quantise the output with "
+            "fp8_act_quant)" if act == "fp8" else ""))
+    odt = x.dtype
+    if x_scale is not None:
+        if act not in ACT_TILES:
+            raise ValueError(f"linear_tiles: x_scale needs act 'mxfp8' or 'fp8', not {act!r}")
+        want = ((M, K // 32), (torch.float8_e8m0fnu, torch.uint8)) if mx else ((M,), (torch.int32,))
+        if x.dtype != torch.uint8 or tuple(x_scale.shape) != want[0] or x_scale.dtype not in want[1] \
+                or x_scale.device != x.device:
+            raise ValueError(f"linear_tiles: with act={act!r} x must be uint8 [M, K] and x_scale {want[1][0]} "
+                             f"{list(want[0])}, not {x.dtype} / {x_scale.dtype} {list(x_scale.shape)}")
+        odt = torch.bfloat16
     if act in ACT_TILES and f.name != ACT_TILES[act]:
         raise ValueError(f"linear_tiles: act={act!r} needs {ACT_TILES[act]} weight tiles, not {f.name} ones")
     if f.scale_dtype is None:
@@ -805,30 +865,39 @@ def linear_tiles(x: torch.Tensor, wt: torch.Tensor, max_splits: int = 8, glu: bo
         raise ValueError(f"linear_tiles: unsupported shape M={M} N={N} K={K} (N % 64 == 0, K % 256 == 0)")
     if _gpu(x):
         y = p = None
-        if S == 1:
-            y = torch.empty(M, N // 2 if glu else N, dtype=x.dtype, device=x.device)
+        if quant_out:
+            aq = torch.empty(M, N // 2, dtype=torch.uint8, device=x.device)
+            ae = torch.empty(M, N // 64, dtype=torch.uint8, device=x.device)
+        elif S == 1:
+            y = torch.empty(M, N // 2 if glu else N, dtype=odt, device=x.device)
         else:
             p = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
         if f.raw:
             wt, scale = wt.view(torch.uint8), scale.view(torch.uint8)
         if mx:
-            xq, xe = mxfp8_quant(x)
+            xq, xe = (x, x_scale) if x_scale is not None else mxfp8_quant(x)
+            if quant_out:
+                ext().tile_gemm_mx(xq, xe.view(torch.uint8), wt, scale, None, None, 1, True, aq, ae)
+                return aq, ae.view(torch.float8_e8m0fnu)
             ext().tile_gemm_mx(xq, xe.view(torch.uint8), wt, scale, y, p, int(S), bool(glu))
         elif act == "fp8":
-            xq, xe = fp8_act_quant(x)
+            xq, xe = (x, x_scale) if x_scale is not None else fp8_act_quant(x)
             ext().tile_gemm_f8(xq, xe, wt, scale, y, p, int(S), bool(glu))
         else:
             ext().tile_gemm(x, wt, y, p, int(S), bool(glu), scale, f.abi)
         return y if S == 1 else p
     w = f.untile(wt, scale, glu).float()
     if act == "fp8":
-        xq, xe = ref.fp8_quant(x)
+        xq, xe = (ref.fp8_act_order(x), x_scale) if x_scale is not None else ref.fp8_quant(x)
         xf = torch.ldexp(xq.view(torch.float8_e4m3fn).float(), xe[:, None])
+    elif mx:
+        xf = ref.mxfp8_dequant(*((x, x_scale) if x_scale is not None else ref.mxfp8_quant(x)))
     else:
-        xf = ref.mxfp8_dequant(*ref.mxfp8_quant(x)) if mx else x.float()
+        xf = x.float()
     if S == 1:
         y = xf @ w.t()
-        return (ref.silu_mul(y) if glu else y).to(x.dtype)
+        y = (ref.silu_mul(y) if glu else y).to(odt)
+        return ref.mxfp8_quant(y) if quant_out else y
     ks = K // S
     return torch.stack([xf[:, s * ks:(s + 1) * ks] @ w[:, s * ks:(s + 1) * ks].t() for s in range(S)])
 

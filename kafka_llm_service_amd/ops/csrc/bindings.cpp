@@ -61,6 +61,48 @@ static void fused_add_rmsnorm(at::Tensor out, at::Tensor x, at::Tensor residual,
                                               residual.stride(0), bptr(w), T, d, eps, cur_stream()));
 }
 
+// RMSNorm (residual absent) or fused add + RMSNorm (x: bf16 [T, d] or slab [S, T, d]; residual updated in place) whose
+// output is quantised for the dense tile GEMMs: quant 1 = MXFP8 (xq uint8 [T, d], xe uint8 [T, d/32]), quant 2 = per-row
+// fp8 (xq uint8 [T, d] in fp8-tile K order, xe int32 [T]), what act_quant_mxfp8 / act_quant_fp8 make of the bf16 output
+static void rmsnorm_quant(at::Tensor x, c10::optional<at::Tensor> residual, at::Tensor w, double eps, at::Tensor xq,
+                          at::Tensor xe, int64_t quant) {
+  CHECK_CUDA(x); CHECK_CUDA(w); CHECK_DT(w, at::kBFloat16); CHECK_LASTDIM(x);
+  TORCH_CHECK(quant == 1 || quant == 2, "rmsnorm_quant: quant must be 1 (mxfp8) or 2 (fp8)");
+  const bool slab = is_slab(x);
+  if (slab) check_slab(x); else CHECK_DT(x, at::kBFloat16);
+  TORCH_CHECK(slab ? residual.has_value() : x.dim() == 2, "rmsnorm_quant: x must be bf16 [T, d], or a slab with a residual");
+  const int64_t T = x.size(slab ? 1 : 0), d = x.size(slab ? 2 : 1);
+  TORCH_CHECK(d % 256 == 0 && d <= 16384 && T < (1LL << 31), "rmsnorm_quant: needs d % 256 == 0 and d <= 16384");
+  TORCH_CHECK(w.is_contiguous() && w.numel() == d && w.device() == x.device(), "rmsnorm_quant: w must be bf16 [d]");
+  TORCH_CHECK(slab || (x.stride(0) % 8 == 0 && x.stride(0) >= d), "rmsnorm_quant: x needs 16-B aligned rows");
+  bf16* rp = nullptr;
+  int64_t rs = 0;
+  if (residual.has_value()) {
+    CHECK_CUDA(residual.value()); CHECK_DT(residual.value(), at::kBFloat16); CHECK_LASTDIM(residual.value());
+    TORCH_CHECK(residual->dim() == 2 && residual->size(0) == T && residual->size(1) == d &&
+                    residual->stride(0) % 8 == 0 && residual->stride(0) >= d && residual->device() == x.device(),
+                "rmsnorm_quant: residual must be bf16 [T, d] with 16-B aligned rows");
+    rp = bptr(residual.value());
+    rs = residual->stride(0);
+  }
+  CHECK_CUDA(xq); CHECK_DT(xq, at::kByte); CHECK_CUDA(xe);
+  TORCH_CHECK(xq.is_contiguous() && xq.dim() == 2 && xq.size(0) == T && xq.size(1) == d && xq.device() == x.device(),
+              "rmsnorm_quant: xq must be contiguous uint8 [T, d]");
+  if (quant == 1) {
+    TORCH_CHECK(xe.scalar_type() == at::kByte && xe.is_contiguous() && xe.dim() == 2 && xe.size(0) == T &&
+                    xe.size(1) == d / 32 && xe.device() == x.device(),
+                "rmsnorm_quant: xe must be contiguous uint8 [T, d/32]");
+  } else {
+    TORCH_CHECK(xe.scalar_type() == at::kInt && xe.is_contiguous() && xe.dim() == 1 && xe.size(0) == T &&
+                    xe.device() == x.device(), "rmsnorm_quant: xe must be contiguous int32 [T]");
+  }
+  if (T == 0) return;
+  CHECK_HIP(kafka_launch_rmsnorm_quant((int)quant, xq.data_ptr<uint8_t>(), xe.data_ptr(), slab ? nullptr : bptr(x),
+                                       slab ? d : x.stride(0), slab ? x.data_ptr<float>() : nullptr,
+                                       slab ? (int)x.size(0) : 0, slab ? T * d : 0, rp, rs, bptr(w), (int)T, (int)d,
+                                       (float)eps, cur_stream()));
+}
+
 // x: bf16 [T, 2F] or slab [S, T, 2F]
 static void silu_mul(at::Tensor out, at::Tensor x) {
   CHECK_CUDA(x); CHECK_DT(out, at::kBFloat16);
@@ -891,9 +933,12 @@ static void act_quant_mxfp8(at::Tensor x, at::Tensor xq, at::Tensor xe) {
 
 // Dense tile GEMM with MXFP8 activations on the MXFP4 tiles (csrc/tile_gemm_mx.hip): xq / xe as act_quant_mxfp8 leaves
 // them (xq rows may be strided, 16-B aligned), wt / scale the mxfp4 tiles and their block-scale image as uint8; y, p,
-// splits and glu as for tile_gemm
+// splits and glu
+// as for tile_gemm. aq / ae (both or neither; glu only, y must be None): the GLU output leaves in MXFP8 form instead of
+// bf16, aq uint8 [M, N/2] and ae uint8 [M, N/64], both contiguous: act_quant_mxfp8 of the y the same call would write
 static void tile_gemm_mx(at::Tensor xq, at::Tensor xe, at::Tensor wt, at::Tensor scale, c10::optional<at::Tensor> y,
-                         c10::optional<at::Tensor> p, int64_t splits, bool glu) {
+                         c10::optional<at::Tensor> p, int64_t splits, bool glu, c10::optional<at::Tensor> aq,
+                         c10::optional<at::Tensor> ae) {
   CHECK_CUDA(xq); CHECK_DT(xq, at::kByte); CHECK_LASTDIM(xq);
   TORCH_CHECK(xq.dim() == 2 && xq.stride(0) % 16 == 0, "tile_gemm_mx: xq must be uint8 [M, K] with 16-B rows");
   const int vk = check_wfmt("tile_gemm_mx", kafka::WF_MXFP4, wt, scale, 0);
@@ -910,7 +955,18 @@ static void tile_gemm_mx(at::Tensor xq, at::Tensor xe, at::Tensor wt, at::Tensor
   bf16* yp = nullptr;
   int64_t ldy = 0;
   float* pp = nullptr;
-  if (splits == 1) {
+  uint8_t *aqp = nullptr, *aep = nullptr;
+  TORCH_CHECK(aq.has_value() == ae.has_value(), "tile_gemm_mx: aq and ae go together");
+  if (aq.has_value()) {
+    TORCH_CHECK(glu && !y.has_value(), "tile_gemm_mx: the quantised output needs glu and replaces y");
+    CHECK_CUDA(aq.value()); CHECK_DT(aq.value(), at::kByte); CHECK_CUDA(ae.value()); CHECK_DT(ae.value(), at::kByte);
+    TORCH_CHECK(aq->is_contiguous() && aq->dim() == 2 && aq->size(0) == M && aq->size(1) == N / 2 &&
+                    aq->device() == xq.device(), "tile_gemm_mx: aq must be contiguous uint8 [M, N/2]");
+    TORCH_CHECK(ae->is_contiguous() && ae->dim() == 2 && ae->size(0) == M && ae->size(1) == N / 64 &&
+                    ae->device() == xq.device(), "tile_gemm_mx: ae must be contiguous uint8 [M, N/64]");
+    aqp = aq->data_ptr<uint8_t>();
+    aep = ae->data_ptr<uint8_t>();
+  } else if (splits == 1) {
     TORCH_CHECK(y.has_value(), "tile_gemm_mx: y required for one split");
     CHECK_CUDA(y.value()); CHECK_DT(y.value(), at::kBFloat16); CHECK_LASTDIM(y.value());
     TORCH_CHECK(y->dim() == 2 && y->size(0) == M && y->size(1) == (glu ? N / 2 : N) && y->stride(0) % 8 == 0 &&
@@ -926,7 +982,7 @@ static void tile_gemm_mx(at::Tensor xq, at::Tensor xe, at::Tensor wt, at::Tensor
   }
   CHECK_HIP(kafka_launch_tile_gemm_mx(xq.data_ptr<uint8_t>(), xq.stride(0), xe.data_ptr<uint8_t>(), wt.data_ptr(),
                                       scale.data_ptr(), (int)M, (int)N, (int)K, (int)splits, glu ? 1 : 0, yp, ldy, pp,
-                                      cur_stream()));
+                                      aqp, aep, cur_stream()));
 }
 
 // Per-row fp8 quantiser of the activations (csrc/tile_gemm_f8.hip): x bf16 [M, K] with 16-B rows -> xq uint8 [M, K]
@@ -1517,6 +1573,8 @@ PYBIND11_MODULE(_kafka_ops, m) {
   m.doc() = "kafka_llm_service_amd CDNA4 (gfx950) HIP kernels";
   m.def("rmsnorm", &rmsnorm);
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm);
+  m.def("rmsnorm_quant", &rmsnorm_quant, py::arg("x"), py::arg("residual"), py::arg("w"), py::arg("eps"), py::arg("xq"),
+        py::arg("xe"), py::arg("quant"));
   m.def("silu_mul", &silu_mul);
   m.def("rope_kv_write", &rope_kv_write);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"),
@@ -1573,7 +1631,7 @@ PYBIND11_MODULE(_kafka_ops, m) {
         py::arg("gather"), py::arg("y"), py::arg("out"), py::arg("pin") = true);
   m.def("act_quant_mxfp8", &act_quant_mxfp8, py::arg("x"), py::arg("xq"), py::arg("xe"));
   m.def("tile_gemm_mx", &tile_gemm_mx, py::arg("xq"), py::arg("xe"), py::arg("wt"), py::arg("scale"), py::arg("y"),
-        py::arg("p"), py::arg("splits"), py::arg("glu"));
+        py::arg("p"), py::arg("splits"), py::arg("glu"), py::arg("aq") = py::none(), py::arg("ae") = py::none());
   m.def("act_quant_fp8", &act_quant_fp8, py::arg("x"), py::arg("xq"), py::arg("xe"));
   m.def("tile_gemm_f8", &tile_gemm_f8, py::arg("xq"), py::arg("xe"), py::arg("wt"), py::arg("scale"), py::arg("y"),
         py::arg("p"), py::arg("splits"), py::arg("glu"));

@@ -216,32 +216,7 @@ __global__ __launch_bounds__(512, 1) void grouped_tile_gemm_mx_kernel(
     if constexpr (EPI == GMX_GLU) {
       tile_epilogue<EPI_GLU>(acc, tp, lane, mw, nw, ent0, rows, 0, N, 0, Y, ldy, nullptr);
     } else {
-      // (gate, up) = (tile 2 cg, 2 cg + 1): the 32 output columns at nw / 2 = MX block nw / 64 of the row. Per 32-row
-      // group a: [32 rows][32] bf16 exactly as tile_epilogue<EPI_GLU> rounds it, then 4 lanes a row (one wave's LDS
-      // accesses complete in order: its reads see its writes and the next group's writes follow the reads)
-      const int F = N >> 1;
-      bf16* t = reinterpret_cast<bf16*>(tp);
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float g = acc[a][0][i], u = acc[a][1][i];
-          t[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = (bf16)(g / (1.0f + __expf(-g)) * u);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int qi = j * 64 + lane, row = qi >> 2, c8 = qi & 3;
-          const u32x4 raw = *reinterpret_cast<const u32x4*>(t + row * 32 + 8 * c8);
-          uint32_t o[2];
-          const int eb = mxfp8_quant_lane(raw, o);  // (every lane takes part: rows past the segment are not stored)
-          const int m = mw + 32 * a + row;
-          if (m < rows) {
-            const int64_t ent = ent0 + m;
-            *reinterpret_cast<uint2*>(Aq + ent * F + (nw >> 1) + 8 * c8) = make_uint2(o[0], o[1]);
-            if (c8 == 0) Ae[ent * (F >> 5) + (nw >> 6)] = (uint8_t)eb;
-          }
-        }
-      }
+      tile_epilogue_glu_mx(acc, tp, lane, mw, nw, ent0, rows, N >> 1, Aq, Ae);  // (tile_epilogue.h: EPI_GLU_MX)
     }
   }
 }

@@ -131,6 +131,15 @@ hipError_t kafka_launch_fused_add_rmsnorm(bf16* out, int64_t os, const bf16* x, 
 // fused add + RMSNorm whose x input is S fp32 split-K slabs [S][T][d] (row stride d, slab stride ps)
 hipError_t kafka_launch_fused_add_rmsnorm_slab(bf16* out, int64_t os, const float* xp, int S, int64_t ps, bf16* resid,
                                                int64_t rs, const bf16* w, int T, int d, float eps, hipStream_t st);
+// RMSNorm / fused add + RMSNorm whose output leaves quantised for the dense tile GEMMs instead of as bf16: the bytes and
+// exponents the stand-alone quantisers make of the bf16 row the kernels above would have written. quant 1: MXFP8 (xq
+// e4m3 [T, d] natural K order, xe uint8 e8m0 [T, d/32]); quant 2: per-row fp8 (xq e4m3 [T, d] in fp8-tile K order, xe
+// int32 [T]); both contiguous. Input forms: x bf16 (row stride xs), or xp != null the S fp32 slabs [S][T][d] (slab
+// stride ps); resid == null: plain RMSNorm of x, else resid <- x + resid in place first. hipErrorInvalidValue for
+// d % 256 != 0, d > 16384, another quant, null or misaligned (16 B) pointers and row strides, slabs without resid.
+hipError_t kafka_launch_rmsnorm_quant(int quant, uint8_t* xq, void* xe, const bf16* x, int64_t xs, const float* xp, int S,
+                                      int64_t ps, bf16* resid, int64_t rs, const bf16* w, int T, int d, float eps,
+                                      hipStream_t st);
 hipError_t kafka_launch_silu_mul(bf16* out, const bf16* x, int64_t xs, int T, int F, hipStream_t st);
 // SwiGLU over S fp32 split-K slabs [S][T][2F]
 hipError_t kafka_launch_silu_mul_slab(bf16* out, const float* xp, int S, int64_t ps, int T, int F, hipStream_t st);
@@ -319,10 +328,11 @@ hipError_t kafka_launch_act_quant_mxfp8(const bf16* X, int64_t ldx, int M, int K
                                         hipStream_t st);
 // Y = Xq . W^T on the scaled fp8 x fp4 MFMA (see tile_gemm_mx_kernel): Xq / Xe as the quantiser leaves them (row stride
 // ldxq % 16 == 0), Wt4 / Se the WF_MXFP4 tiles and their block-scale image. M, N, K, splits, glu, Y, ldy and P as for
-// kafka_launch_tile_gemm, with its refusals.
+// kafka_launch_tile_gemm, with its refusals. With glu, Aq / Ae (both or neither) given INSTEAD of Y: the GLU output in
+// MXFP8 form, Aq e4m3 [M, N/2] and Ae e8m0 [M, N/64], contiguous; no bf16 output is written.
 hipError_t kafka_launch_tile_gemm_mx(const uint8_t* Xq, int64_t ldxq, const uint8_t* Xe, const void* Wt4, const void* Se,
                                      int M, int N, int K, int splits, int glu, bf16* Y, int64_t ldy, float* P,
-                                     hipStream_t st);
+                                     uint8_t* Aq, uint8_t* Ae, hipStream_t st);
 
 // ---- tile_gemm_f8.hip
 // Per-row fp8 quantiser of the activations: X bf16 [M, K] with row stride ldx -> Xq e4m3 bytes [M, K] in fp8-tile K

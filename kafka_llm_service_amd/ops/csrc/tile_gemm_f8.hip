@@ -43,9 +43,10 @@
 //     tiles, as integer exponents; the accumulators are scaled with v_ldexp_f32 (exact, and 2^ea * sw is never formed:
 //     it could leave fp32's range where the product does not).
 //   * LDS 160 KB, 1 workgroup per CU; VGPRs and the absence of scratch: profiles/act_fp8/resource_usage.txt.
-// Not built: the quantiser fused into RMSNorm or the attention epilogue; fp8 activations on the streaming or skinny
+// (The quantiser fused into RMSNorm: norm_act.hip rmsnorm_quant_kernel.) Not built: the quantiser in the attention epilogue; fp8 activations on the streaming or skinny
 // GEMMs; the lm_head. (The grouped expert kernel for fp8 Mixtral is grouped_tile_gemm_f8.hip.)
 #include "common.h"
+#include "mx_quant.h"
 #include "tile_epilogue.h"
 
 namespace kafka {
@@ -231,9 +232,7 @@ __global__ __launch_bounds__(256) void act_quant_fp8_kernel(const bf16* __restri
     __syncthreads();
     am = max(max(wam[0], wam[1]), max(wam[2], wam[3]));
   }
-  // amax = 1.f * 2^(E - 127): amax / 448 = (1.f / 1.75) * 2^(E - 135), whose frexp exponent is E - 135 + (1.f >= 1.75)
-  int e = am == 0 ? 0 : (int)(am >> 7) - 135 + ((am & 0x7f) >= 0x60 ? 1 : 0);
-  e = min(max(e, -100), 100);
+  const int e = fp8_row_exp(am);  // (mx_quant.h: the exponent rule and the element conversion, shared with RMSNorm)
   if (!live) return;
   const float inv = exp2i(-e);
   if (t == 0) Ea[row] = e;
@@ -243,20 +242,10 @@ __global__ __launch_bounds__(256) void act_quant_fp8_kernel(const bf16* __restri
       const int u = base + t + i * TPR;
       if (u >= units) continue;
       if constexpr (!HOLD) load(u, raw[i]);
-      uint32_t o[4];
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const uint32_t d0 = raw[i][c][2 * j], d1 = raw[i][c][2 * j + 1];
-          const float f0 = __builtin_amdgcn_fmed3f(__uint_as_float(d0 << 16) * inv, 448.f, -448.f);
-          const float f1 = __builtin_amdgcn_fmed3f(__uint_as_float(d0 & 0xffff0000u) * inv, 448.f, -448.f);
-          const float f2 = __builtin_amdgcn_fmed3f(__uint_as_float(d1 << 16) * inv, 448.f, -448.f);
-          const float f3 = __builtin_amdgcn_fmed3f(__uint_as_float(d1 & 0xffff0000u) * inv, 448.f, -448.f);
-          const int v = __builtin_amdgcn_cvt_pk_fp8_f32(f0, f1, 0, false);
-          o[2 * c + j] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(f2, f3, v, true);
-        }
-      *reinterpret_cast<u32x4*>(Xq + row * K + 16 * u) = u32x4{o[0], o[1], o[2], o[3]};
+      uint32_t lo[2], hi[2];
+      fp8_quant8(raw[i][0], inv, lo);
+      fp8_quant8(raw[i][1], inv, hi);
+      *reinterpret_cast<u32x4*>(Xq + row * K + 16 * u) = u32x4{lo[0], lo[1], hi[0], hi[1]};
     }
   }
 }

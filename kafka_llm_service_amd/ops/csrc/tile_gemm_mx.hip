@@ -38,7 +38,8 @@
 //     FP8 prologue has the reason).
 // Not built: a dword-granular DMA that would regroup the B blocks on the way in (64 DMA instructions per stage instead
 // of 16); a four-stage ring of 64-deep stages (twice the barriers); 256-deep stages (two would not leave the next
-// stage's DMA a free slot under 160 KB); the quantiser fused into the producers of X. fp8 weight tiles (their K order
+// stage's DMA a free slot under 160 KB); the quantiser in the attention epilogue (RMSNorm and the GLU epilogue have
+// it: norm_act.hip rmsnorm_quant_kernel, tile_epilogue.h EPI_GLU_MX). fp8 weight tiles (their K order
 // per lane differs) have their own unit, tile_gemm_f8.hip, which permutes the activations instead. Registers, LDS and occupancy: profiles/act_mxfp8/resource_usage.txt.
 #include <type_traits>
 
@@ -71,7 +72,8 @@ __global__ __launch_bounds__(512, 1) void tile_gemm_mx_kernel(const uint8_t* __r
                                                                const char* __restrict__ Wt,
                                                                const char* __restrict__ Se, int M, int N, int K,
                                                                int kper, int rts, bf16* __restrict__ Y, int64_t ldy,
-                                                               float* __restrict__ P) {
+                                                               float* __restrict__ P, uint8_t* __restrict__ Aq,
+                                                               uint8_t* __restrict__ Ae) {
   using namespace tmx;
   constexpr int RB = BK, CPR = BK / 16, KB = BK / 64;  // Xq row bytes / 16-B chunks / k-steps per stage
   static_assert(DX == 4 && DW == 2 && CPR == 8 && KB == 2, "stage shape");
@@ -176,7 +178,10 @@ __global__ __launch_bounds__(512, 1) void tile_gemm_mx_kernel(const uint8_t* __r
   // epilogues (tile_epilogue.h): each wave through its own 8 KB LDS tile once the ring is dead
   __syncthreads();
   if (2 * cg >= nbt) return;  // wave-uniform: the column group lies past N
-  tile_epilogue<EPI>(acc, smem + w * 8192, lane, 128 * rh, cb * BN + 64 * cg, row0, rows, M, N, blockIdx.y, Y, ldy, P);
+  if constexpr (EPI == EPI_GLU_MX)  // silu(g) * u as MXFP8 rows Aq [M, N/2] / Ae [M, N/64]: the down projection's input
+    tile_epilogue_glu_mx(acc, smem + w * 8192, lane, 128 * rh, cb * BN + 64 * cg, row0, rows, N >> 1, Aq, Ae);
+  else
+    tile_epilogue<EPI>(acc, smem + w * 8192, lane, 128 * rh, cb * BN + 64 * cg, row0, rows, M, N, blockIdx.y, Y, ldy, P);
 }
 
 // MXFP8 quantiser: X bf16 [M, K] (K % 256 == 0) -> Xq e4m3 [M, K] in natural order, Xe e8m0 [M, K/32]. The rule is
@@ -197,14 +202,10 @@ __global__ __launch_bounds__(256) void act_quant_mxfp8_kernel(const bf16* __rest
   if (live) raw = *reinterpret_cast<const u32x4*>(X + row * ldx + 8 * c);
   uint32_t o[2];
   const int eb = mxfp8_quant_lane(raw, o);  // (mx_quant.h: the block's amax over its 4 lanes, exponent rule, e4m3 bytes)
-  // the 8 exponents of the half-wave's 256 columns: a dword per 16 lanes, then the pair
-  uint32_t ev = (lane & 3) == 0 ? (uint32_t)eb << (8 * ((lane >> 2) & 3)) : 0u;
-  ev |= (uint32_t)__shfl_xor((int)ev, 4, 64);
-  ev |= (uint32_t)__shfl_xor((int)ev, 8, 64);
-  const uint32_t ev2 = (uint32_t)__shfl_xor((int)ev, 16, 64);
+  const uint2 ev = mxfp8_exps_halfwave(eb, lane);  // the 8 exponents of the half-wave's 256 columns
   if (live) {
     *reinterpret_cast<uint2*>(Xq + row * K + 8 * c) = make_uint2(o[0], o[1]);
-    if ((lane & 31) == 0) *reinterpret_cast<uint2*>(Xe + row * (K >> 5) + (c >> 2)) = make_uint2(ev, ev2);
+    if ((lane & 31) == 0) *reinterpret_cast<uint2*>(Xe + row * (K >> 5) + (c >> 2)) = ev;
   }
 }
 
@@ -221,28 +222,32 @@ extern "C" hipError_t kafka_launch_act_quant_mxfp8(const bf16* X, int64_t ldx, i
 }
 
 // Y = Xq . W^T with MXFP8 activations (Xq e4m3 [M, K], row stride ldxq % 16 == 0; Xe e8m0 [M, K/32] contiguous) on the
-// MXFP4 tiles Wt4 / Se (see tile_gemm_mx_kernel). Outputs, splits and glu as for kafka_launch_tile_gemm.
+// MXFP4 tiles Wt4 / Se (see tile_gemm_mx_kernel). Outputs, splits and glu as for kafka_launch_tile_gemm. With glu, Aq /
+// Ae given instead of Y: the GLU output in MXFP8 form (Aq e4m3 [M, N/2], Ae e8m0 [M, N/64], contiguous), the bytes the
+// quantiser above makes of the bf16 Y; exactly one of Y and the pair.
 extern "C" hipError_t kafka_launch_tile_gemm_mx(const uint8_t* Xq, int64_t ldxq, const uint8_t* Xe, const void* Wt4,
                                                const void* Se, int M, int N, int K, int splits, int glu, bf16* Y,
-                                               int64_t ldy, float* P, hipStream_t st) {
+                                               int64_t ldy, float* P, uint8_t* Aq, uint8_t* Ae, hipStream_t st) {
   using namespace tmx;
   if (M < 1 || N <= 0 || K <= 0 || N % 64 != 0 || K % 256 != 0 || ldxq % 16 != 0 || ldxq < K)
     return hipErrorInvalidValue;
   if (splits < 1 || splits > 8 || K % (256 * splits) != 0 || (glu && splits > 1)) return hipErrorInvalidValue;
   if (Xq == nullptr || Xe == nullptr || Wt4 == nullptr || Se == nullptr) return hipErrorInvalidValue;
-  if (splits > 1 ? P == nullptr : (Y == nullptr || ldy % 8 != 0)) return hipErrorInvalidValue;
+  if ((Aq != nullptr) != (Ae != nullptr) || (Aq != nullptr && (!glu || Y != nullptr))) return hipErrorInvalidValue;
+  if (Aq == nullptr && (splits > 1 ? P == nullptr : (Y == nullptr || ldy % 8 != 0))) return hipErrorInvalidValue;
   const int rts = (M + BM - 1) / BM;
   if ((int64_t)rts * ((N + BN - 1) / BN) > 0x7fffffffLL) return hipErrorInvalidValue;
   const dim3 grid((unsigned)rts * ((N + BN - 1) / BN), splits);
   const char* wt = static_cast<const char*>(Wt4);
   const char* se = static_cast<const char*>(Se);
   const int kper = K / splits;
-  if (glu)
-    tile_gemm_mx_kernel<EPI_GLU><<<grid, NW * 64, 0, st>>>(Xq, ldxq, Xe, wt, se, M, N, K, kper, rts, Y, ldy, P);
-  else if (splits > 1)
-    tile_gemm_mx_kernel<EPI_SLAB><<<grid, NW * 64, 0, st>>>(Xq, ldxq, Xe, wt, se, M, N, K, kper, rts, Y, ldy, P);
-  else
-    tile_gemm_mx_kernel<EPI_PLAIN><<<grid, NW * 64, 0, st>>>(Xq, ldxq, Xe, wt, se, M, N, K, kper, rts, Y, ldy, P);
+#define KAFKA_TGMX(EPI) \
+  tile_gemm_mx_kernel<EPI><<<grid, NW * 64, 0, st>>>(Xq, ldxq, Xe, wt, se, M, N, K, kper, rts, Y, ldy, P, Aq, Ae)
+  if (Aq != nullptr) KAFKA_TGMX(EPI_GLU_MX);
+  else if (glu) KAFKA_TGMX(EPI_GLU);
+  else if (splits > 1) KAFKA_TGMX(EPI_SLAB);
+  else KAFKA_TGMX(EPI_PLAIN);
+#undef KAFKA_TGMX
   return hipGetLastError();
 }
 
